@@ -1,8 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- interior-point iterations/sec + Schur-assembly roofline on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--limbs 5]          (N > 1: starts N ranks itself, one process per GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--limbs 5] [--dump-outputs DIR] [--full]    (N > 1: starts N ranks itself, one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
+
+A plain run measures the headline alone: it sets up the problem and its context, solves it once (the solve must end Optimal at pi^4/384
+before anything is timed; it also warms the context up), runs W warm-up iterations, times exactly K iterations and prints the JSON line
+(`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed iteration).  `--full` adds everything
+else described below: `full_solve`, `full_solve_two_data_limbs`, `hot_path` with its parity against the 320-bit oracle, `stage_us`, the
+other limb counts, `cpu_baseline`, `reference_documented_rate`, the rooflines, `fp64`, and with N GPUs the `multi_gpu` comparisons.
+`--dump-outputs DIR` writes what the last timed call of the solver returned (x, y, X, Y as planar fp64 limbs, the objectives' limbs, the
+iteration table) as DIR/<name>.npy (rank 0's share when sharded); the inputs depend only on the arguments, so two builds can be compared
+output for output.
 
 Workload (BASELINE.json: "SpherePacking d=8, 2d=30"): the Cohn-Elkies sphere-packing SDP cohnelkies(8, 15) of the reference's
 examples/SpherePacking.jl:117-185 -- 2 clusters of P = 32 constraints, PSD blocks 16x16 (rank-1 constraint matrices) + one 1x1
@@ -57,6 +66,15 @@ PI4_384 = math.pi ** 4 / 384
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(path, res):
+    """What `solvesdp_mw` returned to its caller, as path/<name>.npy in float64: x, y, X, Y and the objectives (dual, primal, gap) as planar
+    limbs (one row per limb), and the iteration table (one row per iteration, the columns of `SolveResult.history`)."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"x": res.x, "y": res.y, "X": res.X, "Y": res.Y, "objectives": res.timings["objectives_limbs"], "history": res.history}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def visible_gpus():
@@ -134,17 +152,22 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=560, help="interior-point iterations in the timed region")
     ap.add_argument("--warmup", type=int, default=56)
-    ap.add_argument("--pass-steps", type=int, default=200, help="hot-path passes of the secondary measurement (`hot_path`)")
+    ap.add_argument("--pass-steps", type=int, default=200, help="hot-path passes of the secondary measurement (`hot_path`, with --full)")
     ap.add_argument("--limbs", type=int, default=5, help="fp64 words per number (5 covers the reference's prec = 256)")
-    ap.add_argument("--skip-cpu", action="store_true")
-    ap.add_argument("--skip-fp64", action="store_true", help="skip the fp64 measurements (Schur-assembly HBM roofline, fp64 step on the problem's shapes)")
-    ap.add_argument("--mw-copies", type=int, default=1024, help="replication factor of the multi-word roofline instance (2 clusters each)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the secondary measurements and checks (CPU baseline, hot path and parity, other "
+                                                        "limb counts, rooflines, fp64, multi-GPU comparisons)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed solve returned as DIR/<name>.npy (float64)")
+    ap.add_argument("--skip-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--skip-fp64", action="store_true", help="with --full: skip the fp64 measurements (Schur-assembly HBM roofline, fp64 step on the problem's shapes)")
+    ap.add_argument("--mw-copies", type=int, default=1024, help="with --full: replication factor of the multi-word roofline instance (2 clusters each)")
     ap.add_argument("--split", action="store_true", help="with one GPU: still take the sharded code path (1-rank process group, RCCL all-gathers inside the library)")
     ap.add_argument("--clusters-per-rank", type=int, default=2, help="N-rank job: clusters a rank holds in the PRIMARY regime (2 = the named problem's share: `value` stays comparable with N = 1)")
-    ap.add_argument("--filled-clusters-per-rank", type=int, default=32, help="N-rank job: clusters per rank of the second regime reported under multi_gpu.filled_regime (0: skip it)")
+    ap.add_argument("--filled-clusters-per-rank", type=int, default=32, help="N-rank job with --full: clusters per rank of the second regime reported under multi_gpu.filled_regime (0: skip it)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={os.environ['WORLD_SIZE']}: launch with --nproc-per-node equal to --gpus")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -217,11 +240,13 @@ def main():
     def solve(**kw):
         return solvesdp_mw(prob, ctx=ctx, shard_info=shard_info, **thr, **kw)
 
-    # ---- the solve itself, untimed: cold (first) and warm, with the reference's default options at K = 5 ----
+    # ---- the solve itself, untimed, with the reference's default options at K = 5: cold (first; the check below is what the headline rests on)
+    #      and, with --full, warm ----
     t0 = time.perf_counter()
-    r_cold = solve()
+    r = r_cold = solve()
     t_cold = time.perf_counter() - t0
-    r = solve()
+    if args.full:
+        r = solve()
     n_it = r.iterations
     if not sharded:
         assert r.error_code == 0 and r.status == "Optimal", (r.status, r.error_code)
@@ -231,19 +256,22 @@ def main():
         # does not is not a measurement of this workload -- no JSON line, non-zero exit
         raise SystemExit(f"bench.py: rank {rank}: the sharded solve ended {r.status} (code {r.error_code}) after {r.iterations} iterations: nothing is reported")
     assert n_it > 0 and r_cold.iterations == n_it
-    full_solve = {"iterations": n_it, "status": r.status, "error_code": r.error_code, "primal_objective": r.primal_objective, "dual_objective": r.dual_objective,
-                  "expected": PI4_384 if not sharded else None, "tolerance": 1e-4, "first_solve_s": t_cold, "solve_s": r.time_total,
-                  "iterations_per_s": n_it / r.time_total, "ms_per_iteration": 1e3 * r.time_total / n_it,
-                  "what": "one whole solve from the reference's starting point with its default options (one call of clrs_mw_ipm_solve: iterations enqueued one "
-                          "ahead of the record the host reads, termination test on the device); first_solve_s includes context warm-up on a cold device"}
+    full_solve = None
+    if args.full:
+        full_solve = {"iterations": n_it, "status": r.status, "error_code": r.error_code, "primal_objective": r.primal_objective, "dual_objective": r.dual_objective,
+                      "expected": PI4_384 if not sharded else None, "tolerance": 1e-4, "first_solve_s": t_cold, "solve_s": r.time_total,
+                      "iterations_per_s": n_it / r.time_total, "ms_per_iteration": 1e3 * r.time_total / n_it,
+                      "what": "one whole solve from the reference's starting point with its default options (one call of clrs_mw_ipm_solve: iterations enqueued one "
+                              "ahead of the record the host reads, termination test on the device); first_solve_s includes context warm-up on a cold device"}
 
     def run_iterations(n):
-        """exactly n interior-point iterations: whole solves back to back, the last one cut at the remainder"""
-        done = 0
+        """exactly n interior-point iterations: whole solves back to back, the last one cut at the remainder; returns the last solve's result"""
+        done, rr = 0, None
         while done < n:
             rr = solve(maxiterations=n - done)
             assert rr.iterations > 0
             done += rr.iterations
+        return rr
 
     # ---- timed region: W warmup iterations + exactly K iterations, barrier + synchronize on both sides ----
     run_iterations(args.warmup)
@@ -252,7 +280,7 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    run_iterations(args.steps)
+    r_last = run_iterations(args.steps)
     torch.cuda.synchronize()
     if sharded:
         dist.barrier()
@@ -268,8 +296,10 @@ def main():
         assert torch.equal(ry0, ry_ref), "the free variables y differ between ranks"
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r_last)
     multi = None
-    if sharded:
+    if sharded and args.full:
         # what the exchanges of one iteration cost on this job's communicator (HIP events around all-gathers of the three message sizes, back to back:
         # clrs_mw_comm_probe), and the one-GPU rate of the named problem measured by rank 0 in this same job for comparison
         probe = ctx.comm_probe(50)
@@ -343,7 +373,7 @@ def main():
 
     # ---- the same solve with TWO data limbs (the form rounds 1-4 measured: a neighbouring problem, entries of B reach 1e27) for comparison ----
     data_k = None
-    if rank == 0 and not sharded and K > 2:
+    if args.full and rank == 0 and not sharded and K > 2:
         try:
             import copy as _copy
             flat_2 = _copy.copy(flat)
@@ -362,7 +392,7 @@ def main():
     # ---- secondary: the hot path alone (chol X + assembly + factorisation + 2 solves) on a mid-trajectory iterate, single GPU ----
     hot = None
     parity = {}
-    if rank == 0 and not sharded:
+    if args.full and rank == 0 and not sharded:
         mid = (n_it + 1) // 2
         r_mid = solve(maxiterations=mid)                                        # stops with code 2 after `mid` iterations; its iterate is (X, Y) of iteration mid + 1
         X, Y = r_mid.X, r_mid.Y
@@ -441,8 +471,9 @@ def main():
                                  "(three times: predictor, corrector and its refinement step) and three scalar records (objectives + mu + p; beta_c and errors; step lengths) inside the C ABI, two communicators "
                                  "(clrs_mw_comm_init, clrs_mw_comm_init_side, clrs_mw_ipm_set_global); y bit-identical on all ranks (asserted); hardware scaling curve: unmeasured by the builder (one-GPU boxes)") if sharded else "single GPU",
                    "launch": "eager, two streams, 35 kernels per iteration, one host wait per iteration on a record that is one iteration old"},
-        "full_solve": full_solve,
     }
+    if full_solve is not None:
+        out["full_solve"] = full_solve
     if data_k is not None:
         out["full_solve_two_data_limbs"] = data_k
     if multi is not None:
@@ -452,7 +483,7 @@ def main():
         out["parity"] = parity
         ms_pass = hot["ms_per_pass"]
 
-    if rank == 0 and not sharded:
+    if args.full and rank == 0 and not sharded:
         ctx.set_timing(True)
         for _ in range(3):
             step()

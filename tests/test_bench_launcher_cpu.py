@@ -73,3 +73,24 @@ def test_bench_refuses_more_gpus_than_the_node_has_instead_of_timing_one():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1"], capture_output=True, text=True, timeout=300,
                        env=dict(os.environ, WORLD_SIZE="1", RANK="0"))
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
+
+
+def test_bench_refuses_a_run_without_timed_steps():
+    # (checked before anything touches torch or the GPU: no JSON line, non-zero exit)
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), *bad], capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and r.stdout.strip() == "" and "--steps must be >= 1" in r.stderr
+
+
+def test_dump_outputs_writes_what_the_solver_returned_as_float64(tmp_path):
+    import types
+    import numpy as np
+    import bench
+    K = 5
+    res = types.SimpleNamespace(x=np.arange(2 * K, dtype=np.float64).reshape(K, 2), y=np.ones((K, 3)), X=np.full((K, 4), 2.0), Y=np.full((K, 4), 3.0),
+                                history=np.zeros((7, 11)), timings={"objectives_limbs": np.ones((3, K))})
+    bench.dump_outputs(str(tmp_path / "out"), res)
+    got = {p.name: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert sorted(got) == ["X.npy", "Y.npy", "history.npy", "objectives.npy", "x.npy", "y.npy"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["x.npy"], res.x) and got["history.npy"].shape == (7, 11) and got["objectives.npy"].shape == (3, K)
