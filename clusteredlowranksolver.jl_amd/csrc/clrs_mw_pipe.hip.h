@@ -466,7 +466,8 @@ __global__ __launch_bounds__(MWP_NT64) void k_mw_potrf_x_pipe(const MwDev q, con
     m.stamps = nullptr;
     int *info = second ? scrInfo + b : &q.info[1];
     const bool ok = big ? mwp_run<K, K, MWP_N64>(m, role, epoch, info, threadIdx.x) : mwp_run<K, K, MWP_N>(m, role, epoch, info, threadIdx.x);
-    if (second && role == 0 && threadIdx.x == 0) yfail[b] = ok ? 0 : 1;
+    // the status of Y_b comes from the first W workgroup: it looks at every pivot (a stage only at those up to the end of its columns -- stage 0 at 0 .. 7)
+    if (second && role == stages && threadIdx.x == 0) yfail[b] = ok ? 0 : 1;
     }
 }
 

@@ -424,6 +424,7 @@ def solvesdp_mw(sdp, limbs: Optional[int] = None, prec: Optional[int] = None, ct
         _lib.check(L.clrs_mw_ipm_objectives(ctx.h, _dp(o3)))
         d_obj, p_obj, gap = float(o3[0]), float(o3[K]), float(o3[2 * K])
     pd_feas = False
+    fail_status = (0, 0)
 
     def row(r):
         return [it, r.mu, d_obj, p_obj, gap, r.max_P, r.max_p, r.max_d, r.alpha_d, r.alpha_p, r.beta_c]
@@ -453,6 +454,7 @@ def solvesdp_mw(sdp, limbs: Optional[int] = None, prec: Optional[int] = None, ct
             refine_bits.append(int(r.refine_bits))
             dual_error, primal_error, pd_feas = r.dual_error, r.primal_error, bool(r.pd_feas)
             if r.error_code:
+                fail_status = (int(r.factor_status), int(r.cholesky_status))
                 break
             d_obj, p_obj, gap = r.d_obj, r.p_obj, r.gap
             it += 1
@@ -477,6 +479,7 @@ def solvesdp_mw(sdp, limbs: Optional[int] = None, prec: Optional[int] = None, ct
             dual_error, primal_error, pd_feas = rec.dual_error, rec.primal_error, bool(rec.pd_feas)
             if rec.error_code:
                 error_code = rec.error_code
+                fail_status = (int(rec.factor_status), int(rec.cholesky_status))
                 if verbose and rec.error_code == 1:
                     print("SolverFailure: factor status %d, Cholesky status %d" % (rec.factor_status, rec.cholesky_status))
                 break
@@ -506,4 +509,7 @@ def solvesdp_mw(sdp, limbs: Optional[int] = None, prec: Optional[int] = None, ct
                       np.array(hist).reshape(-1, 11), dict(loop="device", limbs=K))
     res.timings["objectives_limbs"] = obj.reshape(3, K)
     res.timings["refine_bits"] = refine_bits
+    # the record that ended the loop with an error: (factor status, Cholesky status) -- the code of the failed S_j / Q, of the failed block of X;
+    # (0, 0) with error_code 1: the Cholesky of a block of Y in the step length failed (src/solver.jl:1644-1646)
+    res.timings["fail_status"] = fail_status
     return res

@@ -132,6 +132,8 @@ typedef struct {
     /* starting iterate of the next oracle_solvesdp (oracle_set_start; the dualsol / primalsol keywords, src/solver.jl:202-239) */
     int start_k;
     const double *start_x, *start_y, *start_X, *start_Y;
+    /* where the last oracle_solvesdp met a failed Cholesky factorisation (its error_code 1; oracle_last_failure) */
+    int last_fail;
 } octx;
 
 static REAL ld(const double *hi, const double *lo, i64 i) { return lo ? (REAL)hi[i] + (REAL)lo[i] : (REAL)hi[i]; }
@@ -712,6 +714,9 @@ void oracle_set_start(octx *o, int k, const double *x, const double *y, const do
 void oracle_last_objectives_mw(octx *o, int k, double *out) {
     for (int i = 0; i < 3; i++) stk(out, 3, k, i, o->last_obj[i]);
 }
+/* where the last oracle_solvesdp failed with error_code 1: 0 it did not, 1 the Cholesky of a block of X (src/solver.jl:395-397), 2 the factorisation
+ * of S_j or Q (:1249, :1277), 3 the Cholesky of a block of X in the step length (:1644-1646), 4 that of a block of Y there */
+int oracle_last_failure(const octx *o) { return o->last_fail; }
 
 /* Dense restatement of S used as an independent structural check:
  * S[p,q] = sum_l Tr(A_p X^-1 A_q Y) with A_p = Matrix(::LowRankMat) (src/interface.jl:798-800). */
@@ -954,6 +959,7 @@ int oracle_solvesdp(octx *o, const oracle_params *prm, int *iters_out, double *o
         for (i64 i = 0; i < nxy; i++) { X[i] = ldk(o->start_X, nxy, o->start_k, i); Y[i] = ldk(o->start_Y, nxy, o->start_k, i); }
     }
     int iter = 1, error_code = 0, pd_feas = 0;
+    o->last_fail = 0;
     REAL d_obj, p_obj, gap, dual_error, primal_error, mu = 0, alpha_p = 0, alpha_d = 0, beta_c = 0;
     REAL sgn = o->maximize ? 1 : -1;
 
@@ -1005,10 +1011,10 @@ int oracle_solvesdp(octx *o, const oracle_params *prm, int *iters_out, double *o
         memcpy(Xc, X, sizeof(REAL) * nxy);
         int fail = 0;
         for (int b = 0; b < o->NB && !fail; b++) if (!cholesky_lower(o->blk[b].n, Xc + o->blk[b].off, o->blk[b].n)) fail = 1;
-        if (fail) { error_code = 1; break; }
+        if (fail) { error_code = 1; o->last_fail = 1; break; }
         /* decomposition (:406-408) */
         schur_assemble_real(o, Xc, Y);
-        if (schur_factor_real(o) != 0) { error_code = 1; break; }
+        if (schur_factor_real(o) != 0) { error_code = 1; o->last_fail = 2; break; }
         RESIDUALS(1);                                                              /* :415 */
         REAL xy = bdot(o, X, Y);
         for (int pass = 0; pass < 2; pass++) {
@@ -1061,7 +1067,7 @@ int oracle_solvesdp(octx *o, const oracle_params *prm, int *iters_out, double *o
         }
         alpha_d = step_length(o, X, dX, gamma, pd_feas && !prm->safe_step);       /* :462-463 */
         alpha_p = step_length(o, Y, dY, gamma, pd_feas && !prm->safe_step);
-        if (alpha_d < 0 || alpha_p < 0) { error_code = 1; break; }
+        if (alpha_d < 0 || alpha_p < 0) { error_code = 1; o->last_fail = alpha_d < 0 ? 3 : 4; break; }
         if (hist && iter <= hist_rows) {
             double *h = hist + (i64)(iter - 1) * HIST_COLS;
             h[0] = iter; h[1] = (double)mu; h[2] = (double)d_obj; h[3] = (double)p_obj; h[4] = (double)gap;

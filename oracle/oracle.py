@@ -106,6 +106,8 @@ def _lib(quad):
         L.oracle_kkt_backward_error_mw.argtypes = [C.c_void_p, C.c_int] + [_p_d] * 6
         L.oracle_last_objectives_mw.argtypes = [C.c_void_p, C.c_int, _p_d]
         L.oracle_snapshot_count.restype = C.c_int
+        L.oracle_last_failure.restype = C.c_int
+        L.oracle_last_failure.argtypes = [C.c_void_p]
         L.oracle_snapshot_count.argtypes = [C.c_void_p]
         L.oracle_num_threads.restype = C.c_int
         L.oracle_set_num_threads.argtypes = [C.c_int]
@@ -371,6 +373,11 @@ class Oracle:
         return dict(snap=snap, objectives_limbs=obj_limbs.T.copy(), error_code=int(code), iterations=int(iters.value), d_obj=out[0], p_obj=out[1], gap=out[2],
                     dual_error=out[3], primal_error=out[4], pd_feas=bool(out[5]), hist=hist[:n],
                     x=x, y=y[:f.n_free], X=X, Y=Y)
+
+    def last_failure(self) -> int:
+        """Where the last `solvesdp` ended with error_code 1: 0 it did not, 1 the Cholesky of X, 2 the factorisation of S_j or Q, 3 / 4 the Cholesky of a
+        block of X / of Y in the step length (src/solver.jl:395-397, 1249, 1277, 1644-1646)."""
+        return int(self.L.oracle_last_failure(self.ctx))
 
     @property
     def real_bits(self):

@@ -251,3 +251,68 @@ def load_flat(path):
         v = z[fl.name]
         kw[fl.name] = v if v.ndim else v.item()
     return sdpmod.FlatSDP(**kw), {k: z[k] for k in z.files if k not in kw}
+
+
+# ---- matrices whose Cholesky factorisation fails at a chosen pivot ---------------------------------------------------------
+def ldl_fixture(n, k, seed=0, variant="fail"):
+    """M = L D L^T (n x n, fp64, exactly symmetric) with L unit lower triangular (entries in [-1/2, 1/2]) and D_i in [1, 2]: the leading minors of M are
+    the partial products of D, so pivots 0 .. k - 1 are positive and pivot k is D_k.
+    variant "fail": D_k = -1/4 -- the first non-positive pivot, of a sign no rounding to K limbs flips.
+    variant "tiny": D_k = +2^-30 with row k of L zero left of the diagonal: no pivot cancels, pivot k is 2^-30 exactly and the factorisation must SUCCEED
+    (a kernel that reports a pivot as failed below some threshold over-reports)."""
+    assert 0 <= k < n and variant in ("fail", "tiny")
+    rng = np.random.default_rng(seed)
+    L = np.tril(rng.uniform(-0.5, 0.5, (n, n)), -1) + np.eye(n)
+    D = rng.uniform(1.0, 2.0, n)
+    if variant == "fail":
+        D[k] = -0.25
+    else:
+        D[k] = 2.0 ** -30
+        L[k, :k] = 0.0
+    M = (L * D) @ L.T
+    return np.tril(M) + np.tril(M, -1).T
+
+
+def rank1_flip(A, k, eps):
+    """The symmetric positive definite matrix A (planar limbs (K, n * n), column major) with pivot k of its own L D L^T replaced by -eps D_k:
+    A - (1 + eps) D_k l_k l_k^T, l_k = column k of L.  The leading k x k block is unchanged (l_k is zero there), pivots 0 .. k - 1 stay those of A,
+    pivot k is the first non-positive one.  Formed at 64 K + 128 bits from the exact value of the limbs and rounded back to K limbs."""
+    import mpmath as mp
+    from clrs_amd.mw import to_limbs
+    A = np.atleast_2d(A)
+    K = A.shape[0]
+    n = int(round(np.sqrt(A.shape[1])))
+    with mp.workprec(64 * K + 128):
+        M = [[mp.fsum(mp.mpf(float(A[l, i + j * n])) for l in range(K)) for j in range(n)] for i in range(n)]
+        W = [row[:] for row in M]                      # right-looking elimination: after step m, W[m][m] = D_m, W[i][m] / D_m = L_im
+        for m in range(k):
+            d = W[m][m]
+            assert d > 0, "A is not positive definite before pivot %d" % k
+            for i in range(m + 1, n):
+                f = W[i][m] / d
+                for j in range(m + 1, i + 1):
+                    W[i][j] -= f * W[j][m]
+        Dk = W[k][k]
+        assert Dk > 0
+        l = [mp.mpf(0)] * n
+        for i in range(k, n):
+            l[i] = W[i][k] / Dk
+        s = (1 + mp.mpf(eps)) * Dk
+        out = [M[i][j] - s * l[max(i, j)] * l[min(i, j)] for j in range(n) for i in range(n)]
+    return to_limbs(out, K), float(Dk)
+
+
+def place_block(flat, XY, b, M, K, seed=0):
+    """XY (planar (K, xy_len), or fp64 with K = 0) with block b replaced by the n x n matrix M: fp64 M gets random nested lower limbs (mw_with_tails),
+    planar limbs (K, n * n) go in as they are; every limb plane of the block is made exactly symmetric."""
+    n = int(flat.block_n[b])
+    sl = slice(int(flat.block_off[b]), int(flat.block_off[b + 1]))
+    XY = XY.copy()
+    if K == 0:
+        XY[sl] = np.asarray(M).reshape(-1, order="F")
+        return XY
+    Mk = np.atleast_2d(M) if np.ndim(M) == 2 and np.shape(M)[0] == K and np.shape(M)[1] == n * n else mw_with_tails(np.asarray(M).reshape(-1, order="F"), K, seed)
+    for l in range(K):
+        A = Mk[l].reshape(n, n, order="F")
+        XY[l, sl] = (np.tril(A) + np.tril(A, -1).T).reshape(-1, order="F")
+    return XY
