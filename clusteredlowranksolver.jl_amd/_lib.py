@@ -140,6 +140,10 @@ SYMBOLS = {
     "clrs_mw_debug_exact_stamps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "clrs_mw_debug_pipe_stamps": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "clrs_mw_get_factor": (C.c_int, [C.c_void_p, p_d, p_d, p_d]),
+    "clrs_mw_constraint_gram": (C.c_int, [C.c_void_p, p_d]),
+    "clrs_mw_free_gram": (C.c_int, [C.c_void_p, p_d]),
+    "clrs_mw_rank_reveal": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i32, p_i32, p_d, p_d, p_i32, p_i32, p_d, p_d]),
+    "clrs_mw_constraint_dependencies": (C.c_int, [C.c_void_p, p_d, p_i32, p_i32, p_d, p_d]),
     "clrs_mw_schur_solve": (C.c_int, [C.c_void_p, p_d, p_d, p_d, p_d]),
     "clrs_mw_cholesky_blocks_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "clrs_mw_sync_status_cholesky": (C.c_int, [C.c_void_p]),

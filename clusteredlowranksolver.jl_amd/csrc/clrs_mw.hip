@@ -26,6 +26,7 @@
 #include "clrs_mw_pipe.hip.h"
 #include "clrs_mw_exact.hip.h"
 #include "clrs_mw_ipm.hip.h"
+#include "clrs_mw_rank.hip.h"
 #include "clrs_mw_inst.h"
 #ifdef MW_SPLIT_UNITS        // the kernels of these limb counts are compiled in units of their own (clrs_mw_inst.hip)
 MW_KERNELS_ALL(extern template, 4)
@@ -1657,6 +1658,164 @@ extern "C" int clrs_mw_set_xchol_dev(clrs_mw_ctx *c, const double *d_Xchol) {
     if (!c || !d_Xchol) return mw_fail(CLRS_ERR_INVALID, "null argument");
     MWCHECK(hipSetDevice(c->device));
     return mw_launch_xrd(c, d_Xchol);
+}
+
+// ---- linear dependencies of the constraints (the reference's preprocess!, src/pre_postprocessing.jl) ----------------------------
+
+// X = Y = I in the xy layout (limb plane 0; the caller has cleared the planes): grid = blocks
+static __global__ void k_mw_fill_identity(const MwDev q, double *__restrict__ Xc, double *__restrict__ Y) {
+    const MwBlk &k = q.blk[blockIdx.x];
+    for (int i = threadIdx.x; i < k.n; i += blockDim.x) {
+        Xc[k.xyoff + i + (i64)i * k.n] = 1.0;
+        Y[k.xyoff + i + (i64)i * k.n] = 1.0;
+    }
+}
+// LB := B (the data's DK limb planes, the upper K - DK planes zero): grid-stride over the xlen x N entries
+static __global__ void k_mw_b_to_lb(const MwDev q, int K, int DK) {
+    const i64 plane = q.xlen * (i64)q.N;
+    for (i64 e = (i64)blockIdx.x * blockDim.x + threadIdx.x; e < plane; e += (i64)gridDim.x * blockDim.x)
+        for (int l = 0; l < K; l++) q.LB[l * plane + e] = l < DK ? q.B[l * q.Bp + e] : 0.0;
+}
+
+// G_j = S_j(X = I, Y = I) into the context's S buffer, by the context's own assembly kernels: entry (p, q) is sum_l <A_p, A_q>, the Gram matrix of
+// the cluster's constraint matrices.  Uses the staging buffers of the host-pointer entry points only.
+static int mw_constraint_gram_dev(clrs_mw_ctx *c) {
+    MWCHECK(hipSetDevice(c->device));
+    const size_t bytes = (size_t)std::max<i64>(c->d.xylen, 1) * c->K * sizeof(double);
+    MWCHECK(hipMemsetAsync(c->d_Xc, 0, bytes, c->stream));
+    MWCHECK(hipMemsetAsync(c->d_Y, 0, bytes, c->stream));
+    if (c->d.NB) hipLaunchKernelGGL(k_mw_fill_identity, dim3(c->d.NB), dim3(MW_NT), 0, c->stream, c->d, c->d_Xc, c->d_Y);
+    MWCHECK(hipGetLastError());
+    int rc;
+    if ((rc = mw_launch_xrd(c, c->d_Xc))) return rc;          // chol(I) = I with reciprocal diagonal 1: the assembly substitutes with unit factors
+    return clrs_mw_schur_assemble_dev(c, c->d_Xc, c->d_Y);
+}
+extern "C" int clrs_mw_constraint_gram(clrs_mw_ctx *c, double *G_out) {
+    if (!c || !G_out) return mw_fail(CLRS_ERR_INVALID, "null argument");
+    int rc = mw_constraint_gram_dev(c);
+    if (rc) return rc;
+    MWCHECK(hipMemcpyAsync(G_out, c->d.S, (size_t)c->d.Slen * c->K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    MWCHECK(hipStreamSynchronize(c->stream));
+    return 0;
+}
+// B^T B = sum_j B_j^T B_j (N x N, planar): the Q-Gram kernel of the factor stage applied to B itself (LinvB := B)
+extern "C" int clrs_mw_free_gram(clrs_mw_ctx *c, double *Q_out) {
+    if (!c || !Q_out) return mw_fail(CLRS_ERR_INVALID, "null argument");
+    if (c->d.world > 1) return mw_fail(CLRS_ERR_STATE, "clrs_mw_free_gram on a sharded context");
+    MWCHECK(hipSetDevice(c->device));
+    MwDev q = c->d;
+    if (q.N == 0) return 0;
+    q.kf = c->K;                                             // all limbs, whatever the factor stage runs in
+    const i64 plane = q.xlen * (i64)q.N;
+    hipLaunchKernelGGL(k_mw_b_to_lb, dim3((unsigned)std::min<i64>(1024, (plane + MW_NT - 1) / MW_NT)), dim3(MW_NT), 0, c->stream, q, c->K, c->DK);
+    MW_DISPATCH(c, { hipLaunchKernelGGL(k_mw_qgram<KK>, dim3((q.N * (q.N + 1) / 2 + MW_NT / MW_Q_W - 1) / (MW_NT / MW_Q_W)), dim3(MW_NT), 0, c->stream, q, MW_Q_W); });
+    MWCHECK(hipGetLastError());
+    MWCHECK(hipMemcpyAsync(Q_out, q.Qg + (i64)q.rank * c->K * q.N * q.N, (size_t)q.N * q.N * c->K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    MWCHECK(hipStreamSynchronize(c->stream));
+    c->factored = c->local_factored = false;                 // LB and the partial Q no longer belong to a factorisation
+    return 0;
+}
+
+// One launch of k_mw_rank_reveal over `mats` (host list; lds flags and the LDS size are set here).  d_G: the matrices (overwritten where a matrix is not
+// LDS-resident), d_Wk: workspace of the same shape, d_W / d_perm / d_rank / d_resid: outputs on the device.
+static int mw_rank_launch(int K, hipStream_t stream, std::vector<MwRankMat> &mats, double *d_G, double *d_Wk, i64 gplane, double *d_W, int *d_perm, int *d_rank,
+                          double *d_resid, i64 xplane) {
+    size_t lds = 0;
+    for (auto &m : mats) {
+        if (m.n < 0 || m.ncand < 0 || m.ncand > m.n) return mw_fail(CLRS_ERR_INVALID, "rank reveal: need 0 <= ncand <= n");
+        const size_t full = (size_t)MW_RANK_LDS(K, m.n);
+        m.lds = full <= MW_LDS_MAX ? 1 : 0;
+        lds = std::max(lds, m.lds ? full : (size_t)MW_RANK_SCR(K, m.n) * 8);
+    }
+    if (lds > MW_LDS_MAX) return mw_fail(CLRS_ERR_INVALID, "rank reveal: matrix too large (the pivots' scale factors and the permutation must fit in LDS)");
+    if (mats.empty()) return 0;
+    MwRankMat *d_m = nullptr;
+    MWCHECK(hipMalloc((void **)&d_m, mats.size() * sizeof(MwRankMat)));
+    hipError_t e = hipMemcpyAsync(d_m, mats.data(), mats.size() * sizeof(MwRankMat), hipMemcpyHostToDevice, stream);
+#define MW_RANK_CASE(Kc)                                                                                                                            \
+    case Kc:                                                                                                                                        \
+        if (e == hipSuccess && lds > 48 * 1024) e = hipFuncSetAttribute((const void *)k_mw_rank_reveal<Kc>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        if (e == hipSuccess) hipLaunchKernelGGL(k_mw_rank_reveal<Kc>, dim3((unsigned)mats.size()), dim3(MW_PT), lds, stream, d_m, d_G, d_Wk, gplane, d_W, d_perm, d_rank, d_resid, xplane); \
+        break;
+    switch (K) {
+        MW_RANK_CASE(4) MW_RANK_CASE(5) MW_RANK_CASE(6) MW_RANK_CASE(8) MW_RANK_CASE(10)
+        default: (void)hipFree(d_m); return mw_fail(CLRS_ERR_INVALID, "rank reveal: limbs must be 4, 5, 6, 8 or 10");
+    }
+#undef MW_RANK_CASE
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    (void)hipFree(d_m);
+    if (e != hipSuccess) return mw_fail(CLRS_ERR_HIP, std::string("rank reveal: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// device buffers of one call, released on every path
+struct MwRankBufs {
+    std::vector<void *> p;
+    ~MwRankBufs() { for (void *x : p) (void)hipFree(x); }
+    template <class T>
+    hipError_t get(T **d, size_t count) {
+        hipError_t e = hipMalloc((void **)d, std::max<size_t>(count, 1) * sizeof(T));
+        if (e == hipSuccess) p.push_back(*d);
+        return e;
+    }
+};
+
+extern "C" int clrs_mw_rank_reveal(int device, int limbs, int nmat, const int32_t *n, const int32_t *ncand, const double *G, const double *tau, int32_t *perm,
+                                   int32_t *rank, double *W, double *resid) {
+    if (nmat < 0 || (nmat > 0 && (!n || !ncand || !G || !tau || !perm || !rank || !W || !resid))) return mw_fail(CLRS_ERR_INVALID, "null argument");
+    if (nmat == 0) return 0;
+    MWCHECK(hipSetDevice(device));
+    std::vector<MwRankMat> mats(nmat);
+    i64 gplane = 0, xplane = 0;
+    for (int m = 0; m < nmat; m++) {
+        if (n[m] < 0) return mw_fail(CLRS_ERR_INVALID, "rank reveal: negative size");
+        mats[m] = MwRankMat{n[m], ncand[m], 0, 0, gplane, xplane, tau[m]};
+        gplane += (i64)n[m] * n[m];
+        xplane += n[m];
+    }
+    MwRankBufs bufs;
+    double *d_G = nullptr, *d_Wk = nullptr, *d_W = nullptr, *d_resid = nullptr;
+    int *d_perm = nullptr, *d_rank = nullptr;
+    const size_t gb = (size_t)gplane * limbs, xb = (size_t)xplane * limbs;
+    MWCHECK(bufs.get(&d_G, gb)); MWCHECK(bufs.get(&d_Wk, gb)); MWCHECK(bufs.get(&d_W, gb)); MWCHECK(bufs.get(&d_resid, xb));
+    MWCHECK(bufs.get(&d_perm, (size_t)xplane)); MWCHECK(bufs.get(&d_rank, (size_t)nmat));
+    MWCHECK(hipMemcpy(d_G, G, gb * sizeof(double), hipMemcpyHostToDevice));
+    MWCHECK(hipMemset(d_W, 0, std::max<size_t>(gb, 1) * sizeof(double)));
+    MWCHECK(hipMemset(d_resid, 0, std::max<size_t>(xb, 1) * sizeof(double)));
+    int rc = mw_rank_launch(limbs, nullptr, mats, d_G, d_Wk, gplane, d_W, d_perm, d_rank, d_resid, xplane);
+    if (rc) return rc;
+    MWCHECK(hipMemcpy(perm, d_perm, (size_t)xplane * sizeof(int), hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(rank, d_rank, (size_t)nmat * sizeof(int), hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(W, d_W, gb * sizeof(double), hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(resid, d_resid, xb * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Gram + rank reveal per cluster without the Gram matrices leaving the device: S holds G_j and is factored in place (LDS-resident clusters: in LDS), Si is
+// the workspace of the clusters beyond LDS, S0 receives the relations.  The context needs a new assembly before its next factorisation.
+extern "C" int clrs_mw_constraint_dependencies(clrs_mw_ctx *c, const double *tau, int32_t *perm, int32_t *rank, double *W, double *resid) {
+    if (!c || !tau || !perm || !rank || !W || !resid) return mw_fail(CLRS_ERR_INVALID, "null argument");
+    int rc = mw_constraint_gram_dev(c);
+    if (rc) return rc;
+    const MwDev &q = c->d;
+    const int K = c->K;
+    std::vector<MwRankMat> mats(q.J);
+    for (int j = 0; j < q.J; j++) mats[j] = MwRankMat{c->clu[j].P, c->clu[j].P, 0, 0, c->clu[j].Soff, c->clu[j].coff, tau[j]};
+    MwRankBufs bufs;
+    double *d_resid = nullptr;
+    int *d_perm = nullptr, *d_rank = nullptr;
+    MWCHECK(bufs.get(&d_resid, (size_t)q.xlen * K)); MWCHECK(bufs.get(&d_perm, (size_t)q.xlen)); MWCHECK(bufs.get(&d_rank, (size_t)q.J));
+    MWCHECK(hipMemsetAsync(q.S0, 0, (size_t)std::max<i64>(q.Slen, 1) * K * sizeof(double), c->stream));
+    MWCHECK(hipMemsetAsync(d_resid, 0, (size_t)std::max<i64>(q.xlen, 1) * K * sizeof(double), c->stream));
+    rc = mw_rank_launch(K, c->stream, mats, q.S, q.Si, q.Slen, q.S0, d_perm, d_rank, d_resid, q.xlen);
+    c->assembled = c->factored = c->local_factored = false;      // S, Si and S0 were used as work space
+    if (rc) return rc;
+    MWCHECK(hipMemcpy(perm, d_perm, (size_t)q.xlen * sizeof(int), hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(rank, d_rank, (size_t)q.J * sizeof(int), hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(W, q.S0, (size_t)q.Slen * K * sizeof(double), hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(resid, d_resid, (size_t)q.xlen * K * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 #include "clrs_mw_ipm_host.inc"

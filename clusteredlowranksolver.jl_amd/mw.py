@@ -227,6 +227,32 @@ class MwSchurContext:
         _lib.check(self.L.clrs_mw_schur_solve(self.h, _dp(rx), _dp(ry), _dp(dx), _dp(dy)))
         return dx, dy[:, :f.n_free]
 
+    # -- linear dependencies (preprocess.py) -----------------------------------
+    def constraint_gram(self) -> np.ndarray:
+        """G_j = S_j(X = I, Y = I): the Gram matrices <A_p, A_q> of the clusters' constraint matrices, planar S layout."""
+        G = np.zeros((self.limbs, self.flat.S_len))
+        _lib.check(self.L.clrs_mw_constraint_gram(self.h, _dp(G)))
+        return G
+
+    def free_gram(self) -> np.ndarray:
+        """B^T B = sum_j B_j^T B_j, planar (limbs, N * N) column-major."""
+        N = self.flat.n_free
+        Q = np.zeros((self.limbs, max(N * N, 1)))
+        _lib.check(self.L.clrs_mw_free_gram(self.h, _dp(Q)))
+        return Q[:, :N * N]
+
+    def constraint_dependencies(self, tau):
+        """Diagonally pivoted Cholesky of every G_j on the device (every constraint a candidate, stop at pivots <= tau[j]):
+        (perm [x layout], rank [J], W [planar S layout: per cluster r x (P - r), leading dimension r], resid [planar x layout])."""
+        f = self.flat
+        tau = np.ascontiguousarray(tau, dtype=np.float64)
+        if tau.shape != (f.n_clusters,):
+            raise ValueError("one threshold per cluster")
+        perm, rank = np.zeros(max(f.x_len, 1), np.int32), np.zeros(f.n_clusters, np.int32)
+        W, resid = np.zeros((self.limbs, max(f.S_len, 1))), np.zeros((self.limbs, max(f.x_len, 1)))
+        _lib.check(self.L.clrs_mw_constraint_dependencies(self.h, _dp(tau), perm.ctypes.data_as(_lib.p_i32), rank.ctypes.data_as(_lib.p_i32), _dp(W), _dp(resid)))
+        return perm[:f.x_len], rank, W[:, :f.S_len], resid[:, :f.x_len]
+
     # -- device pointers ---------------------------------------------------------------------------
     def cholesky_blocks_dev(self, d_X: int, d_Xchol: int):
         _lib.check(self.L.clrs_mw_cholesky_blocks_dev(self.h, C.c_void_p(d_X), C.c_void_p(d_Xchol)))
@@ -330,6 +356,32 @@ class LocalGroup:
             self.h = None
 
 
+def rank_reveal(G, n, ncand, tau, limbs: int, device: int = 0):
+    """Diagonally pivoted Cholesky of a batch of symmetric positive semidefinite matrices on the device (clrs_mw_rank_reveal): `G` planar
+    (limbs, sum n_m^2), matrix m column-major; only indices < ncand[m] become pivots; stop at pivots <= tau[m].  Returns, per matrix,
+    (perm, r, W, resid): the pivots in pivot order then the rest in original order, the rank, W = G11^-1 G12 as planar (limbs, r (n - r))
+    column-major r x (n - r), and the remaining diagonal of the n - r non-pivots as planar (limbs, n - r)."""
+    n, ncand = np.ascontiguousarray(n, np.int32).reshape(-1), np.ascontiguousarray(ncand, np.int32).reshape(-1)
+    tau = np.ascontiguousarray(tau, np.float64).reshape(-1)
+    nm = n.size
+    g_off = np.concatenate([[0], np.cumsum(n.astype(np.int64) ** 2)])
+    x_off = np.concatenate([[0], np.cumsum(n.astype(np.int64))])
+    G = _c(np.atleast_2d(G))
+    if ncand.size != nm or tau.size != nm or G.shape != (int(limbs), int(g_off[-1])):
+        raise ValueError("rank_reveal: G must be planar (limbs, sum n^2), with one ncand and one tau per matrix")
+    L = _lib.load()
+    perm, rank = np.zeros(max(int(x_off[-1]), 1), np.int32), np.zeros(max(nm, 1), np.int32)
+    W, resid = np.zeros((int(limbs), max(int(g_off[-1]), 1))), np.zeros((int(limbs), max(int(x_off[-1]), 1)))
+    Gp = G if G.size else np.zeros((int(limbs), 1))
+    _lib.check(L.clrs_mw_rank_reveal(int(device), int(limbs), nm, n.ctypes.data_as(_lib.p_i32), ncand.ctypes.data_as(_lib.p_i32), _dp(Gp), _dp(tau),
+                                     perm.ctypes.data_as(_lib.p_i32), rank.ctypes.data_as(_lib.p_i32), _dp(W), _dp(resid)))
+    out = []
+    for m in range(nm):
+        r, nn = int(rank[m]), int(n[m])
+        out.append((perm[x_off[m]:x_off[m + 1]].copy(), r, W[:, g_off[m]:g_off[m] + r * (nn - r)].copy(), resid[:, x_off[m]:x_off[m] + nn - r].copy()))
+    return out
+
+
 def shard_problem(full: FlatSDP, rank: int, world: int, parts=None):
     """The sub-problem of rank `rank` (its clusters by `partition_clusters`, all free variables) and what `solvesdp_mw` must tell the
     library about the whole: (shard, shard_info)."""
@@ -356,7 +408,8 @@ def solvesdp_mw(sdp, limbs: Optional[int] = None, prec: Optional[int] = None, ct
                 dual_error_threshold: float = 1e-30, primal_error_threshold: float = 1e-30, max_complementary_gap: float = 1e100,
                 need_dual_feasible: bool = False, need_primal_feasible: bool = False, verbose: bool = False,
                 step_length_threshold: float = 1e-7, safe_step: bool = True, step_by_step: bool = False, shard_info: Optional[dict] = None,
-                dualsol=None, primalsol=None, factor_limbs: Optional[int] = None, matmul_prec: Optional[int] = None, correctoronly: bool = False):
+                dualsol=None, primalsol=None, factor_limbs: Optional[int] = None, matmul_prec: Optional[int] = None, correctoronly: bool = False,
+                preprocess: bool = False):
     """`solvesdp(sdp; prec, ...)` (src/solver.jl:71-127) with the whole loop body on the GPU in multi-word fp64.
     `correctoronly`: the reference's keyword (src/solver.jl:121, 370-374, 945): mu_p = mu, and the loop ends on `need_dual_feasible` / `need_primal_feasible`, an
     error or `maxiterations` only.
@@ -371,6 +424,10 @@ def solvesdp_mw(sdp, limbs: Optional[int] = None, prec: Optional[int] = None, ct
     `dualsol` / `primalsol`: the warm start of src/solver.jl:202-239 (applied, as there, only when BOTH are given): `dualsol` supplies x and X,
     `primalsol` y and Y -- a previous `SolveResult` (or anything with those attributes), fp64 or planar limbs; through `clrs_mw_ipm_set`.  The errors of
     the starting iterate are known after the first iteration (the reference computes them before its loop): a warm-started solve runs at least one.
+    `preprocess`: the reference's keyword (src/solver.jl:123, 156-167; default False here, True there): detect linearly dependent constraints and free
+    variables they fix or that duplicate each other (`clrs_amd.preprocess`), solve the reduced problem and return x (zeros for the removed constraints)
+    and y (the eliminated variables put back) in the ORIGINAL numbering; `timings["preprocess"]` keeps the reduced iterate (x, y), `cs`, `var_rels` and the
+    time spent.  Not together with `ctx` (it belongs to the unreduced problem), with `shard_info`, or with a warm start once something was removed.
     Termination (src/solver.jl:921-950): by the library and the device together in one call (`clrs_mw_ipm_solve_cb`; `verbose` prints the table rows
     from its callback), or -- `step_by_step` -- on the host from one record per call of `clrs_mw_ipm_iterate`."""
     import time
@@ -378,6 +435,28 @@ def solvesdp_mw(sdp, limbs: Optional[int] = None, prec: Optional[int] = None, ct
     f = sdp if isinstance(sdp, FlatSDP) else flatten(sdp)
     if limbs is None:
         limbs = limbs_for_precision(prec) if prec is not None else 5
+    if preprocess:
+        if ctx is not None:
+            raise ValueError("preprocess=True cannot be combined with ctx=: the context belongs to the unreduced problem")
+        if shard_info is not None:
+            raise ValueError("preprocess=True is not available for a cluster-sharded solve (shard_info=): preprocess the whole problem before sharding it")
+        from .preprocess import postprocess as _postprocess, preprocess as _preprocess
+        t_pre = time.time()
+        reduced, cs, var_rels = _preprocess(f, prec=prec if prec is not None else LIMB_BITS[int(limbs)], device=device)
+        t_pre = time.time() - t_pre
+        if reduced is not f and dualsol is not None and primalsol is not None:
+            raise ValueError("preprocess=True removed constraints or free variables: a warm start (dualsol / primalsol) of the original problem does not fit "
+                             "the reduced one")
+        res = solvesdp_mw(reduced, limbs=limbs, device=device, data_limbs=data_limbs, maxiterations=maxiterations, beta_infeasible=beta_infeasible,
+                          beta_feasible=beta_feasible, gamma=gamma, omega_p=omega_p, omega_d=omega_d, duality_gap_threshold=duality_gap_threshold,
+                          dual_error_threshold=dual_error_threshold, primal_error_threshold=primal_error_threshold, max_complementary_gap=max_complementary_gap,
+                          need_dual_feasible=need_dual_feasible, need_primal_feasible=need_primal_feasible, verbose=verbose,
+                          step_length_threshold=step_length_threshold, safe_step=safe_step, step_by_step=step_by_step, dualsol=dualsol, primalsol=primalsol,
+                          factor_limbs=factor_limbs, matmul_prec=matmul_prec, correctoronly=correctoronly)
+        res.timings["preprocess"] = dict(x=res.x, y=res.y, cs=cs, var_rels=var_rels, time=t_pre, n_free=reduced.n_free)
+        if reduced is not f:
+            res.x, res.y = _postprocess(res.x, res.y, cs, var_rels)
+        return res
     own_ctx = ctx is None
     if ctx is None:
         ctx = MwSchurContext(f, limbs=limbs, device=device, data_limbs=data_limbs, factor_limbs=factor_limbs,

@@ -8,9 +8,9 @@ reference src/solver.jl:1089-1104 -- every MOI/JuMP problem does, ext/MOIExt.jl 
     toy_z_as_free()   the same with z modelled as a free variable = 1          test/runtests_solver.jl:31-38, src/interface.jl:652-752
 
 Written down directly in the solver's standard form  sum_l <A_p^l, Y_l> + (B y)_p = c_p  (src/interface.jl:478-483); the instances of
-the linear-dependency suite (test/runtests_solver.jl:249-314) are not reproduced: every one of them has a singular Schur complement as
-written (two constraints with the same 1 x 1 matrix: S = a [1 1; 1 1]) and is only solvable after `preprocess!` has eliminated free
-variables and constraints (src/pre_postprocessing.jl), which is outside the path.
+the linear-dependency suite (test/runtests_solver.jl:249-314) are `lindep_suite()`: every one of them has a singular Schur complement as
+written (two constraints with the same 1 x 1 matrix: S = a [1 1; 1 1]) and is only solvable after `preprocess` has eliminated free
+variables and constraints (clrs_amd.preprocess, `solvesdp_mw(..., preprocess=True)`; src/pre_postprocessing.jl).
 """
 from __future__ import annotations
 
@@ -121,3 +121,39 @@ def toy_z_as_free() -> ClusteredLowRankSDP:
     one = np.ones((1, 1))
     cons = [(1.0, {0: one}, [1.0]), (0.0, {1: one}, [-1.0])]
     return dense_sdp([1, 1], cons, {1: one}, maximize=True, free=["z"], b=[0.0], clusters=[[0], [1]], names=["z2", ("z", 1, 1)])
+
+
+def lindep_suite():
+    """The ten problems of the reference's linear-dependency suite (test/runtests_solver.jl:249-314) as it writes them: a list of
+    (name, sdp, expected objective or None when the reference expects an error, keywords of solvesdp).  Clusters as the reference's
+    clustering gives them: constraints that share a PSD variable share a cluster, a constraint without PSD part is a cluster of its own."""
+    one = np.ones((1, 1))
+    X, Y = "X", "Y"
+    cs1 = (1.0, {X: one}, {"x": 1, "y": 1}); cs2 = (2.0, {X: one}, {"x": 2, "y": 3}); cs3 = (1.0, {}, {"x": 2})
+    cs4 = (2.0, {X: 2 * one}, {"x": 2, "y": 2}); cs5 = (4.0, {X: one}, {"x": 1, "y": 1}); cs6 = (1.0, {Y: one}, {"x": 2, "y": 2})
+    cs7 = (1.0, {Y: one}, {"z": 1}); cs8 = (0.0, {}, {"x": 1}); cs9 = (0.5, {}, {"y": 1})
+    cs10 = (1.0, {X: one}, {}); cs11 = (0.0, {X: one}, {})
+    oX = (1.0, {X: one}, {}); oXY = (1.0, {X: one, Y: one}, {}); oF = (1.0, {X: one}, {"x": -1, "y": -2}); o0 = (0.0, {X: one}, {})
+    om = dict(omega_p=10.0, omega_d=10.0)
+    suite = [("two_constraints_one_block", oX, [cs1, cs2], 1.0, om), ("no_psd_variable", oX, [cs1, cs2, cs3], 1.25, om),
+             ("multiple_of_cs1", oX, [cs1, cs2, cs4], 1.0, om), ("infeasible_constant", oX, [cs1, cs2, cs5], None, {}),
+             ("dependent_free_variables", oX, [cs1, cs6], 1.5, {}), ("dependent_then_independent", oXY, [cs1, cs2, cs3, cs4, cs7], 1.25, {}),
+             ("free_variables_in_objective", oF, [cs1, cs2], 0.0, {}), ("incompatible_free_constraints", oF, [cs1, cs2, cs8, cs9, cs5], None, {}),
+             ("psd_only_different_rhs", o0, [cs10, cs11], None, {}), ("psd_only_duplicate", o0, [cs10, cs10], 1.0, {})]
+    out = []
+    for name, obj, cons, expect, kw in suite:
+        fv = sorted({k for c in cons for k in c[2]} | set(obj[2]))
+        bn = sorted({k for c in cons for k in c[1]} | set(obj[1]))
+        bi = {k: i for i, k in enumerate(bn)}
+        cc = [(c[0], {bi[k]: v for k, v in c[1].items()}, [float(c[2].get(v, 0)) for v in fv]) for c in cons]
+        groups, lone = {}, []
+        for i, c in enumerate(cc):
+            if c[1]:
+                groups.setdefault(min(c[1]), []).append(i)      # (no constraint of the suite uses two PSD variables)
+            else:
+                lone.append([i])
+        clusters = sorted(list(groups.values()) + lone)
+        sdp = dense_sdp([1] * len(bn), cc, {bi[k]: v for k, v in obj[1].items()}, maximize=False, free=fv,
+                        b=[float(obj[2].get(v, 0)) for v in fv] if fv else None, constant=obj[0], clusters=clusters, names=bn)
+        out.append((name, sdp, expect, dict(kw)))
+    return out

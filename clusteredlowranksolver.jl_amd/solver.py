@@ -313,9 +313,9 @@ def _raise_factor_failure(ctx: SchurContext, st: int):
     J = ctx.flat.n_clusters
     if st == J + 1:
         raise SolverFailure("Q was not decomposed correctly. Try restarting with a higher precision. If this occurred in the "
-                            "first iteration, remove linear dependencies between free variables or turn preprocessing on.")
+                            "first iteration, remove linear dependencies between free variables or turn preprocessing on (solvesdp_mw(..., preprocess=True)).")
     raise SolverFailure(f"S was not decomposed succesfully in block {st}, try again with higher precision. If this occurred in "
-                        f"the first iteration, remove linear dependencies in the PSD part of the constraints or turn preprocessing on.")
+                        f"the first iteration, remove linear dependencies in the PSD part of the constraints or turn preprocessing on (solvesdp_mw(..., preprocess=True)).")
 
 
 def compute_T_decomposition(ctx: SchurContext, X_inv: np.ndarray, Y: np.ndarray, want_S: bool = False, want_AY: bool = True):

@@ -343,6 +343,22 @@ int clrs_mw_get_factor(clrs_mw_ctx *ctx, double *L, double *LinvB, double *LQ);
 int clrs_mw_debug_exact_stamps(clrs_mw_ctx *ctx, unsigned long long *out /* [16] */);   /* diagnostic: first call arms, later calls read the phase stamps of k_mws_pair */
 int clrs_mw_debug_pipe_stamps(clrs_mw_ctx *ctx, unsigned long long *out /* [16 * 40] */);   /* diagnostic builds (-DCLRS_MW_STAMPS) only: DESIGN.md section 5.5 */
 int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and A_Y of the last (device-pointer) assembly -> host; NULL pointers are skipped */
+/* Linear dependencies of the constraints (the reference's preprocess!, src/pre_postprocessing.jl).
+ * clrs_mw_constraint_gram: G_j = S_j(X = I, Y = I), entry (p, q) = sum_l <A_p, A_q> -- the Gram matrix of the cluster's constraint matrices -- in the planar S
+ *   layout, by the context's own assembly kernels.  Only the staging buffers of the host-pointer entry points are written.
+ * clrs_mw_free_gram: B^T B = sum_j B_j^T B_j, N x N column-major, planar [limbs][N * N] (nothing is written when N = 0).
+ * clrs_mw_rank_reveal: diagonally pivoted Cholesky of `nmat` symmetric positive semidefinite matrices (host pointers; limbs 4, 5, 6, 8 or 10).  Matrix m is
+ *   n[m] x n[m] column-major at offset sum_{m' < m} n[m']^2 of G, planar [limbs][sum n^2]; only indices < ncand[m] may become pivots; the elimination stops when
+ *   the largest remaining candidate diagonal is <= tau[m].  Outputs: perm (concatenated, n[m] entries each: the pivots in pivot order, then the rest in original
+ *   order), rank[m] = r, W (same offsets and planes as G: the r x (n - r) matrix G11^-1 G12, column-major with leading dimension r, in the first r (n - r)
+ *   entries of the matrix's range) and resid (planar [limbs][sum n]: the remaining diagonal of the n - r non-pivots, in the first n - r entries of the range).
+ * clrs_mw_constraint_dependencies: Gram + rank reveal per cluster (every constraint a candidate) without the Gram matrices leaving the device; tau [J], perm and
+ *   resid in the x layout, rank [J], W in the planar S layout.  The context needs a new assembly before its next factorisation. */
+int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
+int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
+int clrs_mw_rank_reveal(int device, int limbs, int nmat, const int32_t *n, const int32_t *ncand, const double *G, const double *tau, int32_t *perm, int32_t *rank,
+                        double *W, double *resid);
+int clrs_mw_constraint_dependencies(clrs_mw_ctx *ctx, const double *tau, int32_t *perm, int32_t *rank, double *W, double *resid);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 
