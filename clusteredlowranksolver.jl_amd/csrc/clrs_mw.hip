@@ -38,6 +38,7 @@ MW_KERNELS_ALL(extern template, 10)
 
 typedef long long i64;
 
+extern int g_cfg_mw_chain_hop, g_cfg_mw_skip_xfb, g_cfg_mw_y_riders;   // clrs_hip.hip, clrs_config_set("mw_chain_hop", 0 / 1 / 2), ("mw_skip_xfb", 0 / 1), ("mw_y_riders", 0 / 1)
 extern int g_cfg_mw_stream_words;                        // clrs_hip.hip, clrs_config_set("mw_stream_words", 0 / 1); env CLRS_MW_STREAM_WORDS
 extern int g_cfg_mw_pipeline64;                          // clrs_hip.hip, clrs_config_set("mw_pipeline64", 0 / 1): the 64-row form for clusters of 33 .. 64 rows
 extern int g_cfg_mw_zt_small_maxn;                       // clrs_hip.hip, clrs_config_set("mw_zt_small_maxn", rows): k_mw_zt with two columns per workgroup and eight lanes per entry up to this block side
@@ -186,6 +187,9 @@ struct clrs_mw_ctx {
     int pipe_pcQ = 0;                    // index of Q's hand-off region in pipe_pc
     unsigned pipe_epoch = 0;             // launch counter: the tag of the hand-off granules
     bool stream_words = true;            // the interior-point iteration synchronises its two streams through words (clrs_mw_ipm_host.inc) where it can; false: events only
+    bool y_riders = true;                // the iteration may form the Y pairings on the Cholesky launch (clrs_config_set("mw_y_riders", ..) when the context was created)
+    const double *ride_y = nullptr;      // set by the iteration around its Cholesky of the X blocks: the Y of the assembly that follows, whose pairings ride on that launch
+    int chain_hop = 1;                   // form of the in-launch hand-offs of k_mwi_Zi / k_mwi_step (MwIpmDev::hop; clrs_config_set("mw_chain_hop", ..) when the context was created)
     bool refine_skip_next = false;       // the interior-point iteration's PREDICTOR solve: one pass (set by clrs_mw_ipm_host.inc for the next clrs_mw_schur_solve_dev only)
     int refine_predictor = 0;            // clrs_mw_options.refine_predictor: 1 = the predictor's solve is refined like every other
     int refine = 1;                      // iterative refinement of the solve stage (clrs_mw_options / clrs_config_set("mw_refine")): 0 off, 1 one step with the correction in all K limbs, 2 ... in mw_kc(K) limbs
@@ -515,7 +519,7 @@ extern "C" int clrs_mw_create_opts(const clrs_sdp_desc *d, int data_limbs, int d
         if (c->sm_fwd > MW_LDS_MAX || c->sm_mid > MW_LDS_MAX) MW_BAIL(CLRS_ERR_INVALID, "cluster too large for the multi-word solve kernels");
     }
     MW_DISPATCH(c, {
-        MW_TRY(mw_set_lds(k_mw_potrf_x<KK>, c->sm_x)); MW_TRY(mw_set_lds(k_mw_zt<KK, DD>, c->sm_zt)); MW_TRY(mw_set_lds((k_mw_dense_t<KK, DD>), c->sm_dense));
+        MW_TRY(mw_set_lds(k_mw_potrf_x<KK>, c->sm_x)); MW_TRY(mw_set_lds((k_mw_potrf_x_ride<KK, DD>), c->sm_x)); MW_TRY(mw_set_lds(k_mw_zt<KK, DD>, c->sm_zt)); MW_TRY(mw_set_lds((k_mw_dense_t<KK, DD>), c->sm_dense));
         // (only what can be launched: Q beyond LDS never rides k_mw_potrf_q, and systems whose dy and three cluster vectors exceed LDS take the
         // row-parallel solve (k_mw_solve_wide) -- sharded, they are refused at the launch, not here)
         constexpr int KC = mw_kc(KK);
@@ -771,6 +775,8 @@ extern "C" int clrs_mw_create_opts(const clrs_sdp_desc *d, int data_limbs, int d
     {
         const char *e = std::getenv("CLRS_MW_STREAM_WORDS");
         c->stream_words = e && *e ? std::atoi(e) != 0 : g_cfg_mw_stream_words != 0;
+        c->chain_hop = std::min(std::max(g_cfg_mw_chain_hop, 0), 2);
+        c->y_riders = g_cfg_mw_y_riders != 0;
     }
     c->wide_solve = c->maxP > 64 || N > 64;
     MW_TRY(mw_dmalloc(c, &c->d_Xin, xyoff * K)); MW_TRY(mw_dmalloc(c, &c->d_Xc, xyoff * K)); MW_TRY(mw_dmalloc(c, &c->d_Y, xyoff * K));
@@ -834,6 +840,10 @@ extern "C" int clrs_mw_create_opts(const clrs_sdp_desc *d, int data_limbs, int d
                 maxn_x = std::max(maxn_x, kb.n);
                 working += 2 * ((kb.n + MWP_W - 1) / MWP_W + (kb.n > MWP_N ? MWP_N64 / MWP_W : MWP_WW));
             }
+            // no reader of the scaled triangles Xf / Xb in such a context (k_mw_zt and k_mw_dense_t take the products with Xi, k_mwi_Z is not launched, k_mwi_step
+            // takes an inverse-factor path: clrs_mw_ipm_create_ex clears this where it would not) unless a dense block of more than one row substitutes for want of
+            // LDS; callers' own factors (k_mw_xrd) come with triangles of their own
+            q.no_xfb = (all_inv && (!q.dn_big || c->dense_two) && g_cfg_mw_skip_xfb != 0) ? 1 : 0;
             c->pipe_X = cfg_pipe != 0 && K <= 6 && all_inv && maxn_x <= MWP_N64 && g_cfg_mw_pipeline_x != 0 &&
                         (cfg_pipe >= 2 || (maxn_x >= g_cfg_mw_pipeline_x_min && working <= 256));
             if (c->pipe_X) {
@@ -953,6 +963,13 @@ extern "C" int clrs_mw_get_counters(const clrs_mw_ctx *c, double *assemble_mulad
     return 0;
 }
 
+// the assembly's small form of k_mw_zt (two columns per workgroup, eight lanes per entry), once the inverse factors of this context's Cholesky exist
+static bool mw_zt_small(const clrs_mw_ctx *c) { return c->all_inv && (i64)c->d.nlr * c->maxU <= 2048 && c->maxn <= g_cfg_mw_zt_small_maxn; }
+// ... and, in such a context, whether the Y half of the pairings can ride on the Cholesky launch of the X blocks: no block goes through the exact-product
+// kernels (they read T as a whole), one context holds the whole problem, the Cholesky is the one-workgroup kernel
+static bool mw_y_riders_ok(const clrs_mw_ctx *c) {
+    return c->y_riders && mw_zt_small(c) && c->d.nlr > 0 && c->mws_blocks == 0 && c->mwx_blocks == 0 && !c->pipe_X && !c->d.gathered && c->d.world <= 1;
+}
 static int mw_reset_info(clrs_mw_ctx *c, int which) {
     if (c->ipm_arms_info) return 0;
     MWCHECK(hipMemsetAsync(c->d.info + which, 0x7f, sizeof(int), c->stream));      // MW_INFO_NONE is the byte 0x7f four times
@@ -980,6 +997,10 @@ static int mw_cholesky_blocks_dev2(clrs_mw_ctx *c, const double *d_X, double *d_
         c->pipe_epoch = (c->pipe_epoch + 1) & 0x3ffffff;
         MW_DISPATCH(c, { if constexpr (KK <= 6) { hipLaunchKernelGGL(k_mw_potrf_x_pipe<KK>, dim3(mwp_blocks64(grid)), dim3(MWP_NT64), MWP_LDS_ALONE64, c->stream, c->d, d_X, d_Xchol, d_Y2, d_Yi, d_yfail,
                                                                      c->xpipe_L, c->xpipe_rd, c->xpipe_info, c->pipe_pcx, c->pipe_epoch); } });
+    } else if (c->ride_y && mw_y_riders_ok(c)) {           // (low-rank block, two unique vectors) tasks behind the factorisations: T = Y V and GY = V^T T of the assembly that follows
+        const int ntile = (c->maxU + 1) / 2;
+        MW_DISPATCH(c, hipLaunchKernelGGL((k_mw_potrf_x_ride<KK, DD>), dim3(grid + c->d.nlr * ntile, in_mem && c->lds_x ? MW_INV_WG : 1), dim3(MW_PT), c->sm_x, c->stream, c->d, d_X, d_Xchol,
+                                          c->lds_x ? 1 : 0, d_Y2, d_Yi, d_yfail, c->ride_y, grid, ntile));
     } else
     MW_DISPATCH(c, hipLaunchKernelGGL(k_mw_potrf_x<KK>, dim3(grid, in_mem && c->lds_x ? MW_INV_WG : 1), dim3(MW_PT), c->sm_x, c->stream, c->d, d_X, d_Xchol, c->lds_x ? 1 : 0, d_Y2, d_Yi, d_yfail));
     MWCHECK(hipGetLastError());
@@ -1012,7 +1033,7 @@ extern "C" int clrs_mw_schur_assemble_dev(clrs_mw_ctx *c, const double *d_Xchol,
             q2.mws_on = exact ? 1 : 0;
             const int gper = MW_NT / MW_GRAM_W;
             // few blocks, every one with its inverse factor: two columns per workgroup and eight lanes per entry
-            const int zt_ct = (c->xinv_valid && c->all_inv && (i64)q.nlr * c->maxU <= 2048 && c->maxn <= g_cfg_mw_zt_small_maxn) ? 2 : MW_CT;
+            const int zt_ct = (c->xinv_valid && mw_zt_small(c)) ? 2 : MW_CT;
             hipLaunchKernelGGL((k_mw_zt<KK, DD>), dim3((c->maxU + zt_ct - 1) / zt_ct, q.nlr), dim3(MW_NT), c->sm_zt, c->stream, q2, d_Y, c->lds_zt_L ? 1 : 0, c->xinv_valid ? 1 : 0, zt_ct);
             const bool ride_gram = !dense_done && q.ndn && !q.dn_big;      // ... or on that of the expansion kernel
             dense_done = dense_done || ride_gram;

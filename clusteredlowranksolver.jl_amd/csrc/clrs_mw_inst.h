@@ -42,6 +42,7 @@
 #define MW_KERNELS_KD(X, K, DK)                                                                                        \
     X __global__ void k_mw_zt<K, DK>(const MwDev, const double *, int, int, int);                                      \
     X __global__ void k_mw_gram<K, DK>(const MwDev, const double *);                                                                   \
+    X __global__ void k_mw_potrf_x_ride<K, DK>(const MwDev, const double *, double *, int, const double *, double *, int *, const double *, int, int); \
     X __global__ void k_mw_dense_t<K, DK>(const MwDev, const double *, int, int, int);                                 \
     X __global__ void k_mw_dense_tp<K, DK>(const MwDev, const double *);                                               \
     X __global__ void k_mw_dense_s<K, DK>(const MwDev, int);                                                           \

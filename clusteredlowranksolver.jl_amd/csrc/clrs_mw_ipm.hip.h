@@ -31,9 +31,11 @@ struct MwIpmDev {
     int *wcnt;                         // [2 NB] workgroups of a (block, which) that have delivered their panel
     double *rec;                       // fp64 record of the iteration
     int *flags;                        // [0] pd_feas, [1] error_code, [2] Cholesky failure inside the step length
-    int klow, pad4;                    // limbs of the arithmetic of THIS launch of k_mwi_wA / k_mwi_Zi / k_mwi_dots: K, or (the predictor's dX, dY and the dot products
+    int klow, hop;                     // limbs of the arithmetic of THIS launch of k_mwi_wA / k_mwi_Zi / k_mwi_dots: K, or (the predictor's dX, dY and the dot products
                                        // that lead to beta_c, when the factor stage runs reduced: clrs_mw_ipm_host.inc) mw_kf_of(K) -- the predictor's (dx, dy) come from
                                        // factors of that many limbs, unrefined, and feed beta_c and the second-order term of the corrector only
+                                       // hop: form of the "last workgroup continues" hand-offs of k_mwi_Zi and k_mwi_step (Zs, Wd, eig / flags[2]): 0 = release fences
+                                       // (mwk::wg_last_block), 1 = write-through stores, a drain and ONE lane's acquire, 2 = write-through stores and loads, no fence
     double *tau, *ttau, *utau;         // the corrector's right-hand side is affine in mu_c (mw_ipm_enqueue): tau_g = <A_g, X^-1> (xlen; k_mwi_rows mode 0 forms it beside d),
                                        // t_tau = Si tau (xlen), u_tau = LB^T t_tau (J x N slabs; both ride on the Cholesky of Q); null: the corrector waits for mu_c
     int *sync;                         // [3] "the dot products behind the predictor are complete" (stored by the corrector's first launch), [4] "mu_c is there" (side stream); [0] the number of the last iteration whose side-stream work (everything the predictor's solve reads) is complete (k_mwi_mark)
@@ -371,7 +373,13 @@ __device__ __noinline__ mwa::mw<K> mwi_sum_part(const MwDev &q, const MwIpmDev &
 // finishes last (a counter in flags[4]; every workgroup publishes its results with a fence before it counts itself) executes
 // the stage.  (The stages behind the block dot products stay separate launches: the fences cost those kernels more than the
 // launch saves -- measured 31 us against 10 + 9.5.)  `mwi_last_block` is uniform over the workgroup.
-__device__ __forceinline__ bool mwi_last_block(int *counter, unsigned total) { return mwk::wg_last_block(counter, total); }
+// With p.hop the payload was stored write-through (mwk::st_wt) and no release fence is executed (mwk::wg_last_block_wt).
+__device__ __forceinline__ bool mwi_last_block(const MwIpmDev &p, int *counter, unsigned total) {
+    return p.hop ? mwk::wg_last_block_wt(counter, total, p.hop == 1) : mwk::wg_last_block(counter, total);
+}
+// the results of k_mwi_step that its last workgroup reads (mwi_scalar_stage3)
+__device__ __forceinline__ void mwi_put_eig(const MwIpmDev &p, long idx, double v) { mwk::st_wt(p.eig + idx, v, p.hop != 0); }
+__device__ __forceinline__ void mwi_put_fail(const MwIpmDev &p) { mwk::st_wt(p.flags + 2, 1, p.hop != 0); }
 // sum over the ranks, in rank order, of the K-limb number at offset `off` of every slot of a gather buffer
 template <int K>
 __device__ __noinline__ mwa::mw<K> mwi_gsum(const MwDev &q, const double *gs, int GL, int off) {
@@ -399,9 +407,9 @@ __device__ __forceinline__ void mwi_scalar_stage3(const MwDev &q, const MwIpmDev
 #pragma unroll
     for (int w = 0; w < 2; w++)
 #pragma unroll
-        for (int b = 0; b < 8; b++) pev[w][b] = (pre && b < q.NB) ? p.eig[(long)w * q.NB + b] : 1e300;
+        for (int b = 0; b < 8; b++) pev[w][b] = (pre && b < q.NB) ? ld_wt(p.eig + (long)w * q.NB + b, p.hop == 2) : 1e300;
     const int f0 = p.flags[0];
-    int f1 = p.flags[1], f2 = p.flags[2];
+    int f1 = p.flags[1], f2 = ld_wt(p.flags + 2, p.hop == 2);
     unsigned long long rs[4] = {0ull, 0ull, 0ull, 0ull};
     if (q.refstat) {
         if (q.world > 1) {                             // the largest over the ranks (k_mwi_gpack stage 3): the same number on every rank
@@ -428,8 +436,8 @@ __device__ __forceinline__ void mwi_scalar_stage3(const MwDev &q, const MwIpmDev
 #pragma unroll
             for (int b = 1; b < 8; b++) mn = fmin(mn, pev[w][b]);
         } else {
-            mn = p.eig[(long)w * q.NB];
-            for (int b = 1; b < q.NB; b++) mn = fmin(mn, p.eig[(long)w * q.NB + b]);
+            mn = ld_wt(p.eig + (long)w * q.NB, p.hop == 2);
+            for (int b = 1; b < q.NB; b++) mn = fmin(mn, ld_wt(p.eig + (long)w * q.NB + b, p.hop == 2));
         }
         const bool unsafe = f0 && !p.safe_step;
         al[w] = (mn > -p.gamma && !unsafe) ? 1.0 : -p.gamma / mn;
@@ -1159,15 +1167,15 @@ __device__ __forceinline__ void mwi_Zi_body(const MwDev &q, const MwIpmDev &p, i
         acc_zero<KA>(s);
         for (int r = i + sub; r < n; r += MWI_ZL) acc_fma<KA, KA, KA>(s, ldx<KA>(Xi, q.xylen, r + (long)i * n), ldx<KA>(M2, np, r + (long)cl * n));
         const mw<KA> v = lanes_sum<KA, MWI_ZL>(acc_result<KA>(s));
-        if (live && sub == 0) stx<K>(p.Zs + k.xyoff, q.xylen, i + (long)(c0 + cl) * n, cvt<K, KA>(v));
+        if (live && sub == 0) stx_wt<K>(p.Zs + k.xyoff, q.xylen, i + (long)(c0 + cl) * n, cvt<K, KA>(v), p.hop != 0);
     }
     MWZ_STAMP();
-    if (!mwi_last_block(&p.zcnt[blockIdx.x], zs)) return;
+    if (!mwi_last_block(p, &p.zcnt[blockIdx.x], zs)) return;
     MWZ_STAMP();
     for (int e = tid; e < n * n; e += MW_PT) {
         const int i = e % n, c = e / n;
         if (c > i) continue;
-        const mw<K> v = cvt<K, KA>(mul_pow2<KA>(add<KA>(ldx<KA>(p.Zs + k.xyoff, q.xylen, i + (long)c * n), ldx<KA>(p.Zs + k.xyoff, q.xylen, c + (long)i * n)), 0.5));
+        const mw<K> v = cvt<K, KA>(mul_pow2<KA>(add<KA>(ldx_wt<KA>(p.Zs + k.xyoff, q.xylen, i + (long)c * n, p.hop == 2), ldx_wt<KA>(p.Zs + k.xyoff, q.xylen, c + (long)i * n, p.hop == 2)), 0.5));
         stx<K>(p.dY + k.xyoff, q.xylen, i + (long)c * n, v);
         stx<K>(p.dY + k.xyoff, q.xylen, c + (long)i * n, v);
     }
@@ -1346,10 +1354,10 @@ __device__ __forceinline__ bool mwi_step_panels_ka(const MwDev &q, const MwIpmDe
         if (i >= c)
             for (int r = sub; r <= i; r += SW) acc_fma<KA, KA, KA>(s, ldx<KA>(Li, q.xylen, i + (long)r * n), ldx<KA>(Us, np, r + (long)cl * n));
         const mw<KA> v = lanes_sum<KA, SW>(acc_result<KA>(s));
-        if (live && sub == 0 && i >= c) Wg[i + (long)c * n] = v.l[0];
+        if (live && sub == 0 && i >= c) st_wt(Wg + i + (long)c * n, v.l[0], p.hop != 0);
     }
     MWS_STAMP(2);
-    return mwi_last_block(&p.wcnt[which * q.NB + blockIdx.x], zs);
+    return mwi_last_block(p, &p.wcnt[which * q.NB + blockIdx.x], zs);
 }
 template <int K>
 __device__ __forceinline__ bool mwi_step_panels(const MwDev &q, const MwIpmDev &p, const MwBlk &k, int which, const double *Li, const double *dMg) {
@@ -1376,8 +1384,8 @@ __device__ __forceinline__ bool mwi_step_body(const MwDev &q, const MwIpmDev &p,
     if (n == 1) {
         if (tid == 0) {
             mw<K> m = ldx<K>(Mg, q.xylen, 0);
-            if (!(m.l[0] > 0.0)) { p.flags[2] = 1; p.eig[(long)which * q.NB + blockIdx.x] = 0.0; }
-            else p.eig[(long)which * q.NB + blockIdx.x] = div<K>(ldx<K>(dMg, q.xylen, 0), m).l[0];     // :1637-1641
+            if (!(m.l[0] > 0.0)) { mwi_put_fail(p); mwi_put_eig(p, (long)which * q.NB + blockIdx.x, 0.0); }
+            else mwi_put_eig(p, (long)which * q.NB + blockIdx.x, div<K>(ldx<K>(dMg, q.xylen, 0), m).l[0]);     // :1637-1641
         }
         return true;
     }
@@ -1385,7 +1393,7 @@ __device__ __forceinline__ bool mwi_step_body(const MwDev &q, const MwIpmDev &p,
         // both inverse factors are in memory (Xi from k_mw_potrf_x, Yi from its second half): LDS holds T1, the fp64 matrix, the eigenvalue work space
         lds_d *T1 = MW_LDS, *Wd = T1 + (long)K * nn, *work = Wd + nn;
         if (which == 1 && p.yfail[blockIdx.x]) {                                         // :1644-1646
-            if (tid == 0) { p.flags[2] = 1; p.eig[(long)which * q.NB + blockIdx.x] = 0.0; }
+            if (tid == 0) { mwi_put_fail(p); mwi_put_eig(p, (long)which * q.NB + blockIdx.x, 0.0); }
             return true;
         }
         if (gridDim.z > 1 || inv_path == 3) {             // 3: the congruence is in Wd already (tiled launches of k_mwi_bmm, large blocks)
@@ -1395,19 +1403,19 @@ __device__ __forceinline__ bool mwi_step_body(const MwDev &q, const MwIpmDev &p,
             const double *Wg = p.Wd + (long)which * q.xylen + k.xyoff;
             for (int e = tid; e < nn; e += MW_NT) {
                 const int i = e % n, c = e / n;
-                Wl[e] = i >= c ? Wg[e] : Wg[c + (long)i * n];
+                Wl[e] = ld_wt(i >= c ? Wg + e : Wg + c + (long)i * n, p.hop == 2);
             }
             __syncthreads();
             MWS_STAMP(4);
             const double ev = n <= 64 ? wg_min_eig32(Wl, n, wk, tid) : wg_min_eig(Wl, n, wk, tid);
-            if (tid == 0) p.eig[(long)which * q.NB + blockIdx.x] = ev - 1e-5;            // :1662
+            if (tid == 0) mwi_put_eig(p, (long)which * q.NB + blockIdx.x, ev - 1e-5);            // :1662
             MWS_STAMP(5);
             return true;
         }
         mwi_step_congruence_inv<K>((which == 0 ? q.Xi : p.Yi) + k.xyoff, q.xylen, n, dMg, q.xylen, T1, Wd, tid);
         __syncthreads();
         const double ev = n <= 64 ? wg_min_eig32(Wd, n, work, tid) : wg_min_eig(Wd, n, work, tid);
-        if (tid == 0) p.eig[(long)which * q.NB + blockIdx.x] = ev - 1e-5;                // :1662
+        if (tid == 0) mwi_put_eig(p, (long)which * q.NB + blockIdx.x, ev - 1e-5);                // :1662
         return true;
     }
     if (inv_path && k.inv == 1) {
@@ -1420,14 +1428,14 @@ __device__ __forceinline__ bool mwi_step_body(const MwDev &q, const MwIpmDev &p,
             wg_copy<K>(Mf, nn, n, Mg, q.xylen, n, n, n, tid);
             __syncthreads();
             if (!wg_potrf<K, true, MW_NT, false>(Mf, nn, n, n, rd, n, Li, nn, n, scr, tid)) {                // :1644-1646
-                if (tid == 0) { p.flags[2] = 1; p.eig[(long)which * q.NB + blockIdx.x] = 0.0; }
+                if (tid == 0) { mwi_put_fail(p); mwi_put_eig(p, (long)which * q.NB + blockIdx.x, 0.0); }
                 return true;
             }
             mwi_step_congruence_inv<K>(Li, nn, n, dMg, q.xylen, T1, Wd, tid);
         }
         __syncthreads();
         const double ev = n <= 64 ? wg_min_eig32(Wd, n, work, tid) : wg_min_eig(Wd, n, work, tid);
-        if (tid == 0) p.eig[(long)which * q.NB + blockIdx.x] = ev - 1e-5;                // :1662
+        if (tid == 0) mwi_put_eig(p, (long)which * q.NB + blockIdx.x, ev - 1e-5);                // :1662
         return true;
     }
     // LDS: F (row-scaled factor), [W], rd, the fp64 matrix and the eigenvalue work space, the broadcast slot of the factorisation.
@@ -1444,7 +1452,7 @@ __device__ __forceinline__ bool mwi_step_body(const MwDev &q, const MwIpmDev &p,
         wg_copy<K>(F, nn, n, Mg, q.xylen, n, n, n, tid);
         __syncthreads();
         if (!wg_potrf<K, false>(F, nn, n, n, rd, n, F, 0, 0, bc, tid)) {                                 // :1644-1646
-            if (tid == 0) { p.flags[2] = 1; p.eig[(long)which * q.NB + blockIdx.x] = 0.0; }
+            if (tid == 0) { mwi_put_fail(p); mwi_put_eig(p, (long)which * q.NB + blockIdx.x, 0.0); }
             return true;
         }
         for (int e = tid; e < nn; e += MW_NT) {                                          // row-scaled strict lower triangle, in place
@@ -1457,7 +1465,7 @@ __device__ __forceinline__ bool mwi_step_body(const MwDev &q, const MwIpmDev &p,
     else mwi_step_congruence<K>(F, rd, (which == 0 ? p.R : p.Pm) + k.xyoff, q.xylen, nn, n, dMg, q.xylen, Wd, tid);    // R and P are dead here; one each
     __syncthreads();
     const double ev = n <= 64 ? wg_min_eig32(Wd, n, work, tid) : wg_min_eig(Wd, n, work, tid);
-    if (tid == 0) p.eig[(long)which * q.NB + blockIdx.x] = ev - 1e-5;                    // :1662
+    if (tid == 0) mwi_put_eig(p, (long)which * q.NB + blockIdx.x, ev - 1e-5);                    // :1662
     return true;
 }
 
@@ -1504,7 +1512,7 @@ __global__ __launch_bounds__(MW_NT) void k_mwi_step(const MwDev q, const MwIpmDe
     // (moving the iterate here as well, by this one workgroup, is slower than the launch of k_mwi_update it saves: 45 against 35 + 6 us)
     if (q.world > 1) return;                            // sharded: the minima travel first (k_mwi_gpack, all-gather, k_mwi_scalar stage 3)
 #ifdef CLRS_MW_STAMPS
-    if (mwi_last_block(&p.flags[4], 2u * q.NB)) {
+    if (mwi_last_block(p, &p.flags[4], 2u * q.NB)) {
         if (threadIdx.x == 0) mwi_scalar_stage3<K>(q, p);
         if (threadIdx.x == 0 && p.stamps) {
             const int me = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
@@ -1518,7 +1526,7 @@ __global__ __launch_bounds__(MW_NT) void k_mwi_step(const MwDev q, const MwIpmDe
     }
     return;
 #endif
-    if (mwi_last_block(&p.flags[4], 2u * q.NB) && threadIdx.x == 0) mwi_scalar_stage3<K>(q, p);
+    if (mwi_last_block(p, &p.flags[4], 2u * q.NB) && threadIdx.x == 0) mwi_scalar_stage3<K>(q, p);
 }
 
 // X = omega_p I, Y = omega_d I, x = y = 0 (:187-201)

@@ -95,6 +95,7 @@ extern "C" int clrs_mw_ipm_create_ex(clrs_mw_ctx *c, const clrs_ipm_data *data, 
         p.sync = (int *)tmp;
         p.tau = p.ttau = p.utau = nullptr;
         p.klow = K;
+        p.hop = c->chain_hop;
         std::vector<int> row_clu((size_t)q.xlen);
         for (int j = 0; j < q.J; j++)
             for (int r = 0; r < c->clu[j].P; r++) row_clu[c->clu[j].coff + r] = j;
@@ -147,6 +148,7 @@ extern "C" int clrs_mw_ipm_create_ex(clrs_mw_ctx *c, const clrs_ipm_data *data, 
         st->step_inv = all_lds_inv && step_inv_need <= lim;      // the step length factors Y itself, everything in LDS
         const size_t step_need2 = nnK + maxn * maxn + 3 * maxn + 2 * MW_NT + 8;
         st->y_with_x = st->any_xinv && !st->any_xsub && step_need2 <= lim;      // every block has its inverse factor: chol(Y)^-1 rides on the chol(X) launch
+        if (!st->y_with_x && !st->step_inv) c->d.no_xfb = 0;      // the step length of X would substitute with Xf
         if (st->step_inv) st->sm_step = std::max(st->sm_step, step_inv_need * 8);
         if (st->y_with_x) st->sm_step = std::max(st->sm_step, step_need2 * 8);
         MW_DISPATCH(c, {
@@ -438,7 +440,11 @@ static int mw_ipm_enqueue_body(clrs_mw_ctx *c) {
     c->ipm_arms_info = true;
     c->d.mark_word = words ? p.sync + 2 : nullptr;
     c->d.mark_value = seq;
+    // ... and carries the Y half of the assembly's pairings as riders (T = Y V, GY = V^T T need the iterate only); k_mw_zt / k_mw_gram then skip it
+    const bool y_rides = mw_y_riders_ok(c);
+    c->ride_y = y_rides ? p.Y : nullptr;
     rc = mw_cholesky_blocks_dev2(c, p.X, p.Xc, st->y_with_x ? p.Y : nullptr, p.Yi, p.yfail);
+    c->ride_y = nullptr;
     c->d.mark_word = nullptr;
     if (rc) return rc;
     // S: the previous iteration's objectives and record lead this iteration's side work (they wait for that word, or for the event)
@@ -454,7 +460,10 @@ static int mw_ipm_enqueue_body(clrs_mw_ctx *c) {
     // M: the rest of the decomposition -- the longest chain of the iteration
     const bool aff = st->aff_ok && !q.gathered;            // (the corrector's right-hand side affine in mu_c: clrs_mw_ipm_create_ex)
     c->d.AX = aff ? st->AX : nullptr;
-    if ((rc = clrs_mw_schur_assemble_dev(c, p.Xc, p.Y))) return rc;
+    c->d.skip_y = y_rides ? 1 : 0;
+    rc = clrs_mw_schur_assemble_dev(c, p.Xc, p.Y);
+    c->d.skip_y = 0;
+    if (rc) return rc;
     if (!words) MWCHECK(hipEventRecord(st->ev[MwIpm::E_ASM], M));
     c->d.mark_word = words ? p.sync + 1 : nullptr;        // "the assembly is complete" (stored by the first launch of the factorisation): S waits for it below
     // the factorisation in its two halves, so that the Cholesky of Q is enqueued behind the side stream's work (below) and can carry
@@ -611,6 +620,8 @@ static int mw_ipm_enqueue(clrs_mw_ctx *c) {
     c->ipm_arms_info = false;
     c->ride_fwd = nullptr;
     c->ride_wait = nullptr;
+    c->ride_y = nullptr;
+    c->d.skip_y = 0;
     c->d.mark_word = nullptr;
     if (rc) { c->fwd_rode = false; c->ipm->tail_pending = false; }
     return rc;

@@ -129,13 +129,15 @@ struct MwDev {
     int *pcnt;                          // [2 J + 3] arrival counters of the workgroups that share one factorisation (cluster j; J: Q; J + 1 + slot: matrices of the blocked path)
     // cluster sharding over ranks (one process per GPU): this context holds the clusters of rank `rank`; the partial Q and the
     // partial u of every rank are gathered into world slots and summed in rank order by every rank (src/solver.jl:1268-1269, 1550-1553)
-    int rank, world, gathered, pad3;    // gathered: u comes from the gather slots (world > 1, or a communicator is attached)
+    int rank, world, gathered, no_xfb;  // gathered: u comes from the gather slots (world > 1, or a communicator is attached); no_xfb: every block has inv = 1 and nothing in this
+                                        // context substitutes with the scaled triangles Xf / Xb -- k_mw_potrf_x does not form them (nor U^T), as k_mw_potrf_x_pipe never does
     double *Qg, *ug;                    // [world][limbs * N * N], [world][limbs * N]
     // exact-product path of the pairing matrices (clrs_mw_exact.hip.h): blocks with mws_off[b] >= 0 are taken by k_mws_pair when mws_on
     const long long *mws_off;
     int mws_on, mwx_on;
     const long long *mwd_off;           // dense blocks with mwd_off[b] >= 0: X^-1 (A_e Y) by k_mwx_dense when mwd_on
-    int mwd_on, pad5;
+    int mwd_on, skip_y;                 // skip_y: T = Y V and GY = V^T T of this assembly were formed by the riders of the Cholesky launch (k_mw_potrf_x_ride): k_mw_zt and k_mw_gram
+                                        // form Z and GX only
     const long long *mwx_off;           // blocks with mwx_off[b] >= 0: pairing matrices of ANY size from the digits of Z, T, V (k_mwx_slice, k_mwx_gram) when mwx_on
 };
 
@@ -158,6 +160,31 @@ template <int K, class P>
 __device__ __forceinline__ void stx(P p, long plane, long i, const mw<K> &v) {
 #pragma unroll
     for (int l = 0; l < K; l++) p[(long)l * plane + i] = v.l[l];
+}
+
+// Write-through counterparts, for numbers that ANOTHER workgroup of the same launch reads behind wg_last_block_wt: a relaxed agent-scope
+// atomic store / load of an 8-byte (or 4-byte) word is a global_store / global_load with sc1 -- the store goes through this XCD's L2 to memory,
+// the load bypasses this compute unit's L1 and a stale line of this XCD's L2.  `wt` false: the plain access (the fence form of the hand-off).
+template <class T>
+__device__ __forceinline__ void st_wt(T *p, T v, bool wt) {
+    if (wt) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *p = v;
+}
+template <class T>
+__device__ __forceinline__ T ld_wt(const T *p, bool wt) {
+    return wt ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
+}
+template <int K>
+__device__ __forceinline__ void stx_wt(double *p, long plane, long i, const mw<K> &v, bool wt) {
+#pragma unroll
+    for (int l = 0; l < K; l++) st_wt(p + (long)l * plane + i, v.l[l], wt);
+}
+template <int K>
+__device__ __forceinline__ mw<K> ldx_wt(const double *p, long plane, long i, bool wt) {
+    mw<K> r;
+#pragma unroll
+    for (int l = 0; l < K; l++) r.l[l] = ld_wt(p + (long)l * plane + i, wt);
+    return r;
 }
 
 __device__ __forceinline__ void tri_index(int e, int &ii, int &jj) {      // e -> (ii >= jj) of a packed lower triangle
@@ -218,7 +245,7 @@ __device__ __forceinline__ void pivot_scale(double head, double &p1, double &ph)
 // the elimination of M (bit for bit the same) and share out the columns of W finish in the time of M plus a cnw-th of W.
 template <int K, bool INV, int NT = MW_NT, bool UT = !INV, class PM, class PR, class PW>
 __device__ __forceinline__ bool wg_potrf(PM M, long plane, int n, int ld, PR rd, long rdplane, PW W, long wplane, int ldw, lds_d *scr, int tid, int cw = 0,
-                                         int cnw = 1) {
+                                         int cnw = 1, bool ut = true) {      // ut false: no U^T although UT (decided at run time; nothing else depends on it)
     if (INV) {
         for (int e = tid; e < n * n; e += NT) {
             const int i = e % n, c = e / n;
@@ -280,7 +307,7 @@ __device__ __forceinline__ bool wg_potrf(PM M, long plane, int n, int ld, PR rd,
         stx<K>(rd, rdplane, k, rs);
         stx<K>(M, plane, kk, mul<K>(dt, f));
         stx<K>(fs, n, k, f);
-        if (UT) stx<K>(us, n, k, mul<K>(f, rs));
+        if (UT && ut) stx<K>(us, n, k, mul<K>(f, rs));
     }
     __syncthreads();
 #ifdef MW_STAMPS
@@ -294,7 +321,7 @@ __device__ __forceinline__ bool wg_potrf(PM M, long plane, int n, int ld, PR rd,
         i += 1;                                                          // strict lower triangle: i > c
         if (e < T) {
             const mw<K> a = ldx<K>(M, plane, i + (long)c * ld);
-            if (UT) stx<K>(M, plane, c + (long)i * ld, mul<K>(a, ldx<K>(us, n, c)));
+            if (UT && ut) stx<K>(M, plane, c + (long)i * ld, mul<K>(a, ldx<K>(us, n, c)));
             stx<K>(M, plane, i + (long)c * ld, mul<K>(a, ldx<K>(fs, n, c)));
         } else if (c % cnw == cw) {
             const long idx = w_index(i, c, n, ldw);
@@ -431,6 +458,30 @@ __device__ __forceinline__ bool wg_last_block(int *counter, unsigned total) {
     if (last) __threadfence();
     return last != 0;
 }
+// The same hand-off WITHOUT release fences, for payloads stored write-through (st_wt / stx_wt, every store of them): each storing wave waits
+// for its stores to complete, the workgroup meets, one lane counts with a relaxed agent-scope atomic.  The last arriver either reads every
+// handed-off byte with write-through loads (ld_wt / ldx_wt; `acquire` false), or one lane of it invalidates the compute unit's L1 and waits
+// for that in front of the barrier that releases the other waves' plain loads (`acquire` true).  __threadfence() is an L2 write-back plus an
+// invalidate executed by every wave, ~3.3 us per hand-off on gfx950; this form has neither.
+__device__ __forceinline__ bool wg_last_block_wt(int *counter, unsigned total, bool acquire) {
+    __shared__ int last;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned old = __hip_atomic_fetch_add((unsigned *)counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int l = (old == total - 1) ? 1 : 0;
+        if (l) {
+            __hip_atomic_store(counter, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (acquire) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
+        last = l;
+    }
+    __syncthreads();
+    return last != 0;
+}
 
 // copy a rows x cols planar matrix between two arrays (any address spaces)
 // Four elements per thread and pass, every load of a pass issued before its first store (the index of a thread past the end is clamped
@@ -486,7 +537,8 @@ __device__ __forceinline__ void mw_potrf_x_body(const MwDev &q, const MwBlk &k, 
     // first one writes the factor, each its columns of the inverse
     const bool share = w_in_place || (INV && mw_x_shares(k));
     const int cw = share ? blockIdx.y : 0, cnw = share ? gridDim.y : 1;
-    const bool ok = wg_potrf<K, INV, MW_PT, true>(M, plane, n, n, q.xrd + k.rd_off, q.xrdlen, W, wplane, w_in_place ? n : 0, bc, tid, cw, cnw);   // the LDS copy of W is packed
+    const bool xfb = !(INV && q.no_xfb);                  // the scaled triangles (and U^T for them) only where a substitution path can run
+    const bool ok = wg_potrf<K, INV, MW_PT, true>(M, plane, n, n, q.xrd + k.rd_off, q.xrdlen, W, wplane, w_in_place ? n : 0, bc, tid, cw, cnw, xfb);   // the LDS copy of W is packed
     if (!ok && tid == 0) atomicMin(&q.info[1], bid + 1);
     __syncthreads();
     if (INV && !w_in_place && cnw > 1) {                  // this workgroup's columns of the inverse, out of its LDS
@@ -498,7 +550,7 @@ __device__ __forceinline__ void mw_potrf_x_body(const MwDev &q, const MwBlk &k, 
         }
     }
     if (cw != 0) return;
-    if (ok) wg_scaled_factors_u<K, MW_PT>(M, plane, n, q.xrd + k.rd_off, q.xrdlen, n, q.Xf + k.xyoff, q.xylen, n, q.Xb + k.xyoff, q.xylen, n, tid);
+    if (ok && xfb) wg_scaled_factors_u<K, MW_PT>(M, plane, n, q.xrd + k.rd_off, q.xrdlen, n, q.Xf + k.xyoff, q.xylen, n, q.Xb + k.xyoff, q.xylen, n, tid);
     for (int e = tid; e < n * n; e += MW_PT) {
         const int i = e % n, c = e / n;
 #pragma unroll
@@ -513,8 +565,8 @@ __device__ __forceinline__ void mw_potrf_x_body(const MwDev &q, const MwBlk &k, 
 // (src/solver.jl:1644-1655) needs chol(Y)^-1, which depends on nothing computed during the iteration, so it rides along on
 // compute units the launch would leave idle.
 template <int K>
-__global__ __launch_bounds__(MW_PT) void k_mw_potrf_x(const MwDev q, const double *__restrict__ X, double *__restrict__ Xc, int lds, const double *__restrict__ Y2,
-                                                      double *__restrict__ Yi, int *__restrict__ yfail) {
+__device__ __forceinline__ void mw_potrf_x_main(const MwDev &q, const double *__restrict__ X, double *__restrict__ Xc, int lds, const double *__restrict__ Y2,
+                                                double *__restrict__ Yi, int *__restrict__ yfail) {
     using namespace mwk;
     mw_mark(q);
     const bool second = (int)blockIdx.x >= q.NB;
@@ -561,14 +613,20 @@ __global__ __launch_bounds__(MW_PT) void k_mw_potrf_x(const MwDev q, const doubl
     }
 }
 
+template <int K>
+__global__ __launch_bounds__(MW_PT) void k_mw_potrf_x(const MwDev q, const double *__restrict__ X, double *__restrict__ Xc, int lds, const double *__restrict__ Y2,
+                                                      double *__restrict__ Yi, int *__restrict__ yfail) {
+    mw_potrf_x_main<K>(q, X, Xc, lds, Y2, Yi, yfail);
+}
 // ---------------------------------------------------------------------------------------------------------------------
 // Per low-rank block and per tile of MW_CT unique vectors:  T = Y V  and  Z = L^-1 V  (L = chol X_b).
 // These are the reference's part_r products (src/solver.jl:1125, 1137) with X^-1 = L^-T L^-1 split over the two sides
 // of the pairing: V^T X^-1 V = Z^T Z, so the explicit inverse (inv_cho_precomp!, :1117) is never formed.
 // ---------------------------------------------------------------------------------------------------------------------
 // T[:, c] = Y[:, rows(c)] V[rows(c), c] and (inverse factors) Z[:, c] = Xi V[:, c] for the columns c0 .. c0 + nc - 1: ZW lanes per entry
+// (the T half alone: also what the riders of the Cholesky launch run, mw_y_pairings_rider)
 template <int K, int KM, int DK, int ZW>
-__device__ __forceinline__ void mw_zt_products_km(const MwDev &q, const MwBlk &k, const double *__restrict__ Y, int c0, int nc, bool with_z) {
+__device__ __forceinline__ void mw_zt_T_km(const MwDev &q, const MwBlk &k, const double *__restrict__ Y, int c0, int nc) {
     using namespace mwk;
     const int n = k.n, tid = threadIdx.x, dl = k.delta, sub = tid % ZW;
     const double *V = q.V + k.v_off;
@@ -584,6 +642,14 @@ __device__ __forceinline__ void mw_zt_products_km(const MwDev &q, const MwBlk &k
         mw<KM> v = lanes_sum<KM, ZW>(acc_result<KM>(s));
         if (live && sub == 0) stx<K>(q.Tm + k.z_off, q.zlen, i + (long)c * n, cvt<K, KM>(v));
     }
+}
+template <int K, int KM, int DK, int ZW>
+__device__ __forceinline__ void mw_zt_products_km(const MwDev &q, const MwBlk &k, const double *__restrict__ Y, int c0, int nc, bool with_z) {
+    using namespace mwk;
+    const int n = k.n, tid = threadIdx.x, sub = tid % ZW;
+    const double *V = q.V + k.v_off;
+    const int *vrow = q.vrow + k.vrow_off;
+    if (!q.skip_y) mw_zt_T_km<K, KM, DK, ZW>(q, k, Y, c0, nc);
     if (!with_z) return;
     const double *Xi = q.Xi + k.xyoff;                 // rows above the first nonzero row of the vector are zero
     for (int e0 = 0; e0 < n * nc; e0 += MW_NT / ZW) {
@@ -666,36 +732,83 @@ __device__ __forceinline__ void mw_dense_1x1(const MwDev &q, const MwBlk &k, con
         stx<K>(q.Sd + k.sd_off, q.sdlen, e2 + (long)e1 * cnt, v);
     }
 }
+// GY[a, b] = sum_i T[i, b] V[i, a] over the nonzero rows of vector a, `sub` of MW_GRAM_W lanes; the entry and its mirror stored from this ONE sum
+template <int K, int KM, int DK>
+__device__ __forceinline__ void mw_gram_gy_km(const MwDev &q, const MwBlk &k, int a, int b, int sub, bool live) {
+    using namespace mwk;
+    const int n = k.n, U = k.U, dl = k.delta;
+    const double *V = q.V + k.v_off, *T = q.Tm + k.z_off;
+    acc<KM> s;
+    acc_zero<KM>(s);
+    const int r0 = q.vrow[k.vrow_off + a];
+    for (int i = r0 + sub; i < r0 + dl; i += MW_GRAM_W) acc_fma<KM, KM, DK>(s, ldx<KM>(T, q.zlen, i + (long)b * n), ldx<DK>(V, q.Vp, i + (long)a * n));
+    const mw<K> gy = cvt<K, KM>(lanes_sum<KM, MW_GRAM_W>(acc_result<KM>(s)));
+    if (live && sub == 0) {
+        stx<K>(q.GY + k.g_off, q.glen, a + (long)b * U, gy);
+        stx<K>(q.GY + k.g_off, q.glen, b + (long)a * U, gy);
+    }
+}
 template <int K, int KM, int DK>
 __device__ __forceinline__ void mw_gram_km(const MwDev &q) {
     using namespace mwk;
     const MwBlk &k = q.blk[q.lr_list[blockIdx.y]];
-    const int n = k.n, U = k.U, dl = k.delta;
+    const int n = k.n, U = k.U;
     const int e = blockIdx.x * (MW_NT / MW_GRAM_W) + threadIdx.x / MW_GRAM_W, sub = threadIdx.x % MW_GRAM_W;
     const int tot = U * (U + 1) / 2;
     if (blockIdx.x * (MW_NT / MW_GRAM_W) >= tot) return;
     const bool live = e < tot;
     int a, b;
     tri_index(live ? e : 0, a, b);
-    const double *V = q.V + k.v_off;
     const int *vrow = q.vrow + k.vrow_off;
-    const double *Z = q.Z + k.z_off, *T = q.Tm + k.z_off;
+    const double *Z = q.Z + k.z_off;
     acc<KM> s;
     acc_zero<KM>(s);
     // rows above the first nonzero row of either vector are zero in Z = L^-1 V
     const int i0 = max(vrow[a], vrow[b]);
     for (int i = i0 + sub; i < n; i += MW_GRAM_W) acc_fma<KM, KM, KM>(s, ldx<KM>(Z, q.zlen, i + (long)a * n), ldx<KM>(Z, q.zlen, i + (long)b * n));
     const mw<K> gx = cvt<K, KM>(lanes_sum<KM, MW_GRAM_W>(acc_result<KM>(s)));
-    acc_zero<KM>(s);
-    const int r0 = vrow[a];
-    for (int i = r0 + sub; i < r0 + dl; i += MW_GRAM_W) acc_fma<KM, KM, DK>(s, ldx<KM>(T, q.zlen, i + (long)b * n), ldx<DK>(V, q.Vp, i + (long)a * n));
-    const mw<K> gy = cvt<K, KM>(lanes_sum<KM, MW_GRAM_W>(acc_result<KM>(s)));
     if (live && sub == 0) {
         stx<K>(q.GX + k.g_off, q.glen, a + (long)b * U, gx);
         stx<K>(q.GX + k.g_off, q.glen, b + (long)a * U, gx);
-        stx<K>(q.GY + k.g_off, q.glen, a + (long)b * U, gy);
-        stx<K>(q.GY + k.g_off, q.glen, b + (long)a * U, gy);
     }
+    if (!q.skip_y) mw_gram_gy_km<K, KM, DK>(q, k, a, b, sub, live);
+}
+// One rider of the Cholesky launch (k_mw_potrf_x_ride): T[:, c0 .. c0 + 1] = Y V of low-rank block `lb`, then -- behind one barrier: only this
+// workgroup's columns of T are read -- the entries GY[a, b], a >= b, of the same columns b and their mirrors.  Entry by entry the sums of
+// mw_zt_products_km (two columns, eight lanes per entry) and of mw_gram_km: the same lanes per entry, the same term order, the same limb counts.
+// Both need Y and the constant vectors only, nothing the Cholesky of X computes; the launch's other workgroups leave most compute units idle.
+// Launched with MW_PT threads: the waves beyond MW_NT only keep the barrier company.
+template <int K, int KM, int DK>
+__device__ __forceinline__ void mw_y_pairings_rider_km(const MwDev &q, const MwBlk &k, const double *__restrict__ Y, int c0, int nc) {
+    const bool work = threadIdx.x < MW_NT;
+    if (work) mw_zt_T_km<K, KM, DK, 8>(q, k, Y, c0, nc);
+    __syncthreads();
+    if (!work) return;
+    const int U = k.U, sub = threadIdx.x % MW_GRAM_W, n0 = U - c0, tot = n0 + (nc > 1 ? n0 - 1 : 0);
+    for (int e0 = 0; e0 < tot; e0 += MW_NT / MW_GRAM_W) {
+        const int e = e0 + threadIdx.x / MW_GRAM_W;
+        const bool live = e < tot;
+        const int ee = live ? e : 0;
+        const int b = ee < n0 ? c0 : c0 + 1, a = ee < n0 ? c0 + ee : c0 + 1 + (ee - n0);
+        mw_gram_gy_km<K, KM, DK>(q, k, a, b, sub, live);
+    }
+}
+template <int K, int DK>
+__device__ __forceinline__ void mw_y_pairings_rider(const MwDev &q, const double *__restrict__ Y, int r, int ntile) {
+    if (blockIdx.y != 0) return;
+    const MwBlk &k = q.blk[q.lr_list[r / ntile]];
+    const int c0 = (r % ntile) * 2;
+    if (c0 >= k.U) return;
+    const int nc = min(2, k.U - c0);
+    mw_km_switch<K>(q.km, [&](auto kmc) { mw_y_pairings_rider_km<K, decltype(kmc)::value, DK>(q, k, Y, c0, nc); });
+}
+// k_mw_potrf_x with the Y pairings of the assembly that follows as riders: workgroups `base` .. of the launch are (low-rank block, tile of two
+// unique vectors) tasks, `ntile` per block (the interior-point iteration, small contexts: clrs_mw_ipm_host.inc; Yr: the Y the assembly will be given)
+template <int K, int DK>
+__global__ __launch_bounds__(MW_PT) void k_mw_potrf_x_ride(const MwDev q, const double *__restrict__ X, double *__restrict__ Xc, int lds, const double *__restrict__ Y2,
+                                                           double *__restrict__ Yi, int *__restrict__ yfail, const double *__restrict__ Yr, int base, int ntile) {
+    if ((int)blockIdx.x >= base) { mw_y_pairings_rider<K, DK>(q, Yr, (int)blockIdx.x - base, ntile); return; }
+    mw_potrf_x_main<K>(q, X, Xc, lds, Y2, Yi, yfail);
 }
 template <int K, int DK>
 __global__ __launch_bounds__(MW_NT) void k_mw_gram(const MwDev q, const double *__restrict__ Y) {
