@@ -72,6 +72,12 @@ class MwOptions(C.Structure):
                 ("matmul_limbs", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class MwGemmJob(C.Structure):
+    """struct clrs_mw_gemm_job"""
+    _fields_ = [(n, C.c_int32) for n in ("m", "n", "k", "transa", "transb", "alpha", "beta", "lda", "ldb", "ldc")] + \
+               [(n, C.c_int64) for n in ("a_off", "b_off", "c_off")]
+
+
 class ClrsError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"clrs error {code}: {msg}")
@@ -144,6 +150,7 @@ SYMBOLS = {
     "clrs_mw_free_gram": (C.c_int, [C.c_void_p, p_d]),
     "clrs_mw_rank_reveal": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i32, p_i32, p_d, p_d, p_i32, p_i32, p_d, p_d]),
     "clrs_mw_constraint_dependencies": (C.c_int, [C.c_void_p, p_d, p_i32, p_i32, p_d, p_d]),
+    "clrs_mw_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(MwGemmJob), p_d, C.c_int64, p_d, C.c_int64, p_d, C.c_int64]),
     "clrs_mw_schur_solve": (C.c_int, [C.c_void_p, p_d, p_d, p_d, p_d]),
     "clrs_mw_cholesky_blocks_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "clrs_mw_sync_status_cholesky": (C.c_int, [C.c_void_p]),

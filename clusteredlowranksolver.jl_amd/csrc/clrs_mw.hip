@@ -27,6 +27,7 @@
 #include "clrs_mw_exact.hip.h"
 #include "clrs_mw_ipm.hip.h"
 #include "clrs_mw_rank.hip.h"
+#include "clrs_mw_gemm.hip.h"
 #include "clrs_mw_inst.h"
 #ifdef MW_SPLIT_UNITS        // the kernels of these limb counts are compiled in units of their own (clrs_mw_inst.hip)
 MW_KERNELS_ALL(extern template, 4)
@@ -1836,6 +1837,89 @@ extern "C" int clrs_mw_constraint_dependencies(clrs_mw_ctx *c, const double *tau
     MWCHECK(hipMemcpy(rank, d_rank, (size_t)q.J * sizeof(int), hipMemcpyDeviceToHost));
     MWCHECK(hipMemcpy(W, q.S0, (size_t)q.Slen * K * sizeof(double), hipMemcpyDeviceToHost));
     MWCHECK(hipMemcpy(resid, d_resid, (size_t)q.xlen * K * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// ---- the general batched product (clrs_mw_gemm.hip.h): no context, host pointers, the buffers of one call released on every path ----
+static_assert(sizeof(clrs_mw_gemm_job) == sizeof(MwGemmJob) && offsetof(clrs_mw_gemm_job, a_off) == offsetof(MwGemmJob, a_off) &&
+              offsetof(clrs_mw_gemm_job, ldc) == offsetof(MwGemmJob, ldc), "MwGemmJob is clrs_mw_gemm_job");
+
+// elements from the first to one past the last of a rows x cols column-major matrix with leading dimension ld (0 when it has none)
+static i64 mw_gemm_extent(i64 rows, i64 cols, i64 ld) { return rows > 0 && cols > 0 ? (cols - 1) * ld + rows : 0; }
+
+extern "C" int clrs_mw_gemm(int device, int limbs, int njobs, const clrs_mw_gemm_job *jobs, const double *A, int64_t a_plane, const double *B, int64_t b_plane,
+                            double *C, int64_t c_plane) {
+    if (limbs != 4 && limbs != 5 && limbs != 6 && limbs != 8 && limbs != 10) return mw_fail(CLRS_ERR_INVALID, "gemm: limbs must be 4, 5, 6, 8 or 10");
+    if (njobs < 0 || (njobs > 0 && !jobs)) return mw_fail(CLRS_ERR_INVALID, "gemm: null or negative job list");
+    if (a_plane < 0 || b_plane < 0 || c_plane < 0) return mw_fail(CLRS_ERR_INVALID, "gemm: negative plane length");
+    std::vector<int> tiles;                                   // (job, tile row, tile column) of every tile of every non-empty C
+    std::vector<std::pair<i64, i64>> ranges;                  // [first, end) of every non-empty C
+    bool reads_ab = false, reads_c = false;
+    for (int t = 0; t < njobs; t++) {
+        const clrs_mw_gemm_job &q = jobs[t];
+        const std::string at = "gemm: job " + std::to_string(t) + ": ";
+        if (q.m < 0 || q.n < 0 || q.k < 0) return mw_fail(CLRS_ERR_INVALID, at + "negative size");
+        if (q.alpha != 1 && q.alpha != -1) return mw_fail(CLRS_ERR_INVALID, at + "alpha must be -1 or +1");
+        if (q.beta < -1 || q.beta > 1) return mw_fail(CLRS_ERR_INVALID, at + "beta must be -1, 0 or +1");
+        if (q.a_off < 0 || q.b_off < 0 || q.c_off < 0) return mw_fail(CLRS_ERR_INVALID, at + "negative offset");
+        const i64 ra = q.transa ? q.k : q.m, ca = q.transa ? q.m : q.k, rb = q.transb ? q.n : q.k, cb = q.transb ? q.k : q.n;
+        if (q.lda < ra || q.ldb < rb || q.ldc < q.m) return mw_fail(CLRS_ERR_INVALID, at + "leading dimension smaller than the rows it holds");
+        const i64 ea = mw_gemm_extent(ra, ca, q.lda), eb = mw_gemm_extent(rb, cb, q.ldb), ec = mw_gemm_extent(q.m, q.n, q.ldc);
+        if (ec == 0) continue;                                 // m = 0 or n = 0: nothing is read, nothing is written
+        if (!C || (ea && !A) || (eb && !B)) return mw_fail(CLRS_ERR_INVALID, at + "null pool");
+        if (q.a_off > a_plane || ea > a_plane - q.a_off || q.b_off > b_plane || eb > b_plane - q.b_off || q.c_off > c_plane || ec > c_plane - q.c_off) return mw_fail(CLRS_ERR_INVALID, at + "matrix leaves its plane");
+        reads_ab = reads_ab || ea;
+        reads_c = reads_c || q.beta != 0;
+        ranges.emplace_back(q.c_off, q.c_off + ec);
+        for (int tj = 0; tj < (q.n + MW_GEMM_T - 1) / MW_GEMM_T; tj++)
+            for (int ti = 0; ti < (q.m + MW_GEMM_T - 1) / MW_GEMM_T; ti++) { tiles.push_back(t); tiles.push_back(ti); tiles.push_back(tj); }
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); i++)
+        if (ranges[i].first < ranges[i - 1].second) return mw_fail(CLRS_ERR_INVALID, "gemm: the C ranges of two jobs overlap");
+    if (tiles.empty()) return 0;
+    MWCHECK(hipSetDevice(device));
+    MwRankBufs bufs;
+    const bool same = A == B && a_plane == b_plane;
+    const size_t na = reads_ab ? (size_t)a_plane * limbs : 0, nb = reads_ab && !same ? (size_t)b_plane * limbs : 0, nc = (size_t)c_plane * limbs;
+    double *d_A = nullptr, *d_B = nullptr, *d_C = nullptr;
+    MwGemmJob *d_jobs = nullptr;
+    int *d_tiles = nullptr;
+    MWCHECK(bufs.get(&d_A, na)); MWCHECK(bufs.get(&d_B, nb)); MWCHECK(bufs.get(&d_C, nc));
+    MWCHECK(bufs.get(&d_jobs, (size_t)njobs)); MWCHECK(bufs.get(&d_tiles, tiles.size()));
+    if (na && A) MWCHECK(hipMemcpy(d_A, A, na * sizeof(double), hipMemcpyHostToDevice));
+    if (nb && B) MWCHECK(hipMemcpy(d_B, B, nb * sizeof(double), hipMemcpyHostToDevice));
+    // C goes up only when some job reads it (beta != 0); entries no job writes then come back as they went.  When no job reads C, the pool comes down into a
+    // buffer of its own and only the m x n entries the jobs wrote are copied over the caller's.
+    if (reads_c) MWCHECK(hipMemcpy(d_C, C, nc * sizeof(double), hipMemcpyHostToDevice));
+    MWCHECK(hipMemcpy(d_jobs, jobs, (size_t)njobs * sizeof(MwGemmJob), hipMemcpyHostToDevice));
+    MWCHECK(hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice));
+    const double *d_Bk = same ? d_A : d_B;
+    const unsigned grid = (unsigned)(tiles.size() / 3);
+#define MW_GEMM_CASE(Kc)                                                                                                                                          \
+    case Kc:                                                                                                                                                      \
+        hipLaunchKernelGGL(k_mw_gemm<Kc>, dim3(grid), dim3(MW_NT), MW_GEMM_LDS(Kc), nullptr, d_jobs, d_tiles, d_A, (mwi64)a_plane, \
+                           d_Bk, (mwi64)b_plane, d_C, (mwi64)c_plane);                                                                                           \
+        break;
+    switch (limbs) { MW_GEMM_CASE(4) MW_GEMM_CASE(5) MW_GEMM_CASE(6) MW_GEMM_CASE(8) MW_GEMM_CASE(10) }
+#undef MW_GEMM_CASE
+    MWCHECK(hipGetLastError());
+    MWCHECK(hipStreamSynchronize(nullptr));
+    if (reads_c) {
+        MWCHECK(hipMemcpy(C, d_C, nc * sizeof(double), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    std::vector<double> back(nc);
+    MWCHECK(hipMemcpy(back.data(), d_C, nc * sizeof(double), hipMemcpyDeviceToHost));
+    for (int t = 0; t < njobs; t++) {
+        const clrs_mw_gemm_job &q = jobs[t];
+        if (q.m == 0) continue;
+        for (int l = 0; l < limbs; l++)
+            for (i64 j = 0; j < q.n; j++) {
+                const i64 o = (i64)l * c_plane + q.c_off + j * q.ldc;
+                memcpy(C + o, back.data() + o, (size_t)q.m * sizeof(double));
+            }
+    }
     return 0;
 }
 

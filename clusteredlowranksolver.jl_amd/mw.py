@@ -382,6 +382,45 @@ def rank_reveal(G, n, ncand, tau, limbs: int, device: int = 0):
     return out
 
 
+def gemm_batch(jobs, limbs: int, device: int = 0):
+    """A batch of independent products C <- beta C + alpha op(A) op(B) in `limbs` limbs on the device, one library call (clrs_mw_gemm).
+    Each job is (A, B, C or None, transa, transb, alpha, beta): planar operands of shape (planes, rows, cols) with planes <= limbs (zero padded to
+    `limbs`), op = transpose where transa / transb is true, alpha -1 or +1, beta -1, 0 or +1 (beta = 0: C may be None and is never read).
+    Returns the list of results, each planar (limbs, m, n).  Every entry is summed in one fixed order: results are reproducible bit for bit."""
+    limbs = int(limbs)
+    ops, shapes, a_len, c_len = [], [], 0, 0
+    for A, B, Cm, ta, tb, alpha, beta in jobs:
+        A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+        if A.ndim != 3 or B.ndim != 3 or A.shape[0] > limbs or B.shape[0] > limbs:
+            raise ValueError("gemm_batch: operands must be planar (planes <= limbs, rows, cols)")
+        (m, k), (k2, n) = (A.shape[2:0:-1] if ta else A.shape[1:]), (B.shape[2:0:-1] if tb else B.shape[1:])
+        if k != k2:
+            raise ValueError(f"gemm_batch: op(A) is {m} x {k}, op(B) is {k2} x {n}")
+        if Cm is not None:
+            Cm = np.asarray(Cm, dtype=np.float64)
+            if Cm.ndim != 3 or Cm.shape[0] > limbs or Cm.shape[1:] != (m, n):
+                raise ValueError(f"gemm_batch: C must be planar (planes <= limbs, {m}, {n})")
+        elif beta:
+            raise ValueError("gemm_batch: beta != 0 needs C")
+        ops.append((A, B, Cm))
+        shapes.append((m, n, k, a_len, a_len + A[0].size, c_len))
+        a_len += A[0].size + B[0].size
+        c_len += m * n
+    if not ops:
+        return []
+    AB, Cp = np.zeros((limbs, max(a_len, 1))), np.zeros((limbs, max(c_len, 1)))
+    table = (_lib.MwGemmJob * len(ops))()
+    for t, ((A, B, Cm), (m, n, k, ao, bo, co), job) in enumerate(zip(ops, shapes, jobs)):
+        AB[:A.shape[0], ao:ao + A[0].size] = np.transpose(A, (0, 2, 1)).reshape(A.shape[0], -1)          # column-major, leading dimension = rows
+        AB[:B.shape[0], bo:bo + B[0].size] = np.transpose(B, (0, 2, 1)).reshape(B.shape[0], -1)
+        if Cm is not None and job[6]:
+            Cp[:Cm.shape[0], co:co + m * n] = np.transpose(Cm, (0, 2, 1)).reshape(Cm.shape[0], -1)
+        table[t] = _lib.MwGemmJob(m, n, k, int(bool(job[3])), int(bool(job[4])), int(job[5]), int(job[6]), max(A.shape[1], 1), max(B.shape[1], 1), max(m, 1),
+                                  ao, bo, co)
+    _lib.check(_lib.load().clrs_mw_gemm(int(device), limbs, len(ops), table, _dp(AB), AB.shape[1], _dp(AB), AB.shape[1], _dp(Cp), Cp.shape[1]))
+    return [np.ascontiguousarray(np.transpose(Cp[:, co:co + m * n].reshape(limbs, n, m), (0, 2, 1))) for m, n, k, ao, bo, co in shapes]
+
+
 def shard_problem(full: FlatSDP, rank: int, world: int, parts=None):
     """The sub-problem of rank `rank` (its clusters by `partition_clusters`, all free variables) and what `solvesdp_mw` must tell the
     library about the whole: (shard, shard_info)."""
@@ -409,7 +448,7 @@ def solvesdp_mw(sdp, limbs: Optional[int] = None, prec: Optional[int] = None, ct
                 need_dual_feasible: bool = False, need_primal_feasible: bool = False, verbose: bool = False,
                 step_length_threshold: float = 1e-7, safe_step: bool = True, step_by_step: bool = False, shard_info: Optional[dict] = None,
                 dualsol=None, primalsol=None, factor_limbs: Optional[int] = None, matmul_prec: Optional[int] = None, correctoronly: bool = False,
-                preprocess: bool = False):
+                preprocess: bool = False, preprocess_substitute: str = "host"):
     """`solvesdp(sdp; prec, ...)` (src/solver.jl:71-127) with the whole loop body on the GPU in multi-word fp64.
     `correctoronly`: the reference's keyword (src/solver.jl:121, 370-374, 945): mu_p = mu, and the loop ends on `need_dual_feasible` / `need_primal_feasible`, an
     error or `maxiterations` only.
@@ -427,7 +466,8 @@ def solvesdp_mw(sdp, limbs: Optional[int] = None, prec: Optional[int] = None, ct
     `preprocess`: the reference's keyword (src/solver.jl:123, 156-167; default False here, True there): detect linearly dependent constraints and free
     variables they fix or that duplicate each other (`clrs_amd.preprocess`), solve the reduced problem and return x (zeros for the removed constraints)
     and y (the eliminated variables put back) in the ORIGINAL numbering; `timings["preprocess"]` keeps the reduced iterate (x, y), `cs`, `var_rels` and the
-    time spent.  Not together with `ctx` (it belongs to the unreduced problem), with `shard_info`, or with a warm start once something was removed.
+    time spent.  `preprocess_substitute`: "host" (the substitution in mpmath) or "device" (batched multi-word products, `gemm_batch`); see
+    `clrs_amd.preprocess.preprocess`.  Not together with `ctx` (it belongs to the unreduced problem), with `shard_info`, or with a warm start once something was removed.
     Termination (src/solver.jl:921-950): by the library and the device together in one call (`clrs_mw_ipm_solve_cb`; `verbose` prints the table rows
     from its callback), or -- `step_by_step` -- on the host from one record per call of `clrs_mw_ipm_iterate`."""
     import time
@@ -435,6 +475,8 @@ def solvesdp_mw(sdp, limbs: Optional[int] = None, prec: Optional[int] = None, ct
     f = sdp if isinstance(sdp, FlatSDP) else flatten(sdp)
     if limbs is None:
         limbs = limbs_for_precision(prec) if prec is not None else 5
+    if preprocess_substitute not in ("host", "device"):
+        raise ValueError(f'preprocess_substitute must be "host" or "device", got {preprocess_substitute!r}')
     if preprocess:
         if ctx is not None:
             raise ValueError("preprocess=True cannot be combined with ctx=: the context belongs to the unreduced problem")
@@ -442,7 +484,7 @@ def solvesdp_mw(sdp, limbs: Optional[int] = None, prec: Optional[int] = None, ct
             raise ValueError("preprocess=True is not available for a cluster-sharded solve (shard_info=): preprocess the whole problem before sharding it")
         from .preprocess import postprocess as _postprocess, preprocess as _preprocess
         t_pre = time.time()
-        reduced, cs, var_rels = _preprocess(f, prec=prec if prec is not None else LIMB_BITS[int(limbs)], device=device)
+        reduced, cs, var_rels = _preprocess(f, prec=prec if prec is not None else LIMB_BITS[int(limbs)], device=device, substitute=preprocess_substitute)
         t_pre = time.time() - t_pre
         if reduced is not f and dualsol is not None and primalsol is not None:
             raise ValueError("preprocess=True removed constraints or free variables: a warm start (dualsol / primalsol) of the original problem does not fit "

@@ -28,6 +28,12 @@ value is `var_rels.constant`.
 
 The rank-revealing steps are a parameter (`reveal`): None = the device primitives of libclrs_hip.so.  The package has no CPU
 implementation of them; the tests drive the host-side steps with one of their own (tests/preprocess_host.py).
+
+The substitution is a parameter too (`substitute`).  "host" (the default) forms every quantity entry by entry in mpmath at 52 D bits.  "device" forms
+everything whose size grows with the number of constraints -- the conditions on the free variables, their Gram matrix, the Gram matrix of the
+remaining free variables and the reduced B and c -- as batched multi-word products on limb planes (`reveal.gemm_batch`, `clrs_mw_gemm`); only
+the r x (N + 1 - r) relation coefficients `var_rels` promises as mpmath numbers, the residual test, b and the constant stay in mpmath.  Both round
+the same exact values to D limbs, so the reduced problems agree to the accuracy of D limbs, not bit for bit.
 """
 from __future__ import annotations
 
@@ -90,6 +96,12 @@ class DeviceReveal:
     def rank_reveal(self, G, n: int, ncand: int, tau: float):
         from .mw import rank_reveal
         return rank_reveal(G, [n], [ncand], [tau], self.D, self.device)[0]
+
+    def gemm_batch(self, jobs):
+        """[(A, B, C or None, transa, transb, alpha, beta)] -> [C <- beta C + alpha op(A) op(B)] on planes (planes, rows, cols), D limbs, one call
+        (needs no context: `preprocess` still calls it after `close`)"""
+        from .mw import gemm_batch
+        return gemm_batch(jobs, self.D, self.device)
 
     def close(self):
         if self.ctx is not None:
@@ -244,11 +256,17 @@ def select_constraints(flat: FlatSDP, keep: List[np.ndarray], drop_empty: bool =
 
 # ---- the reference's three functions ------------------------------------------------------------------------------------------
 
-def find_linear_dependencies(flat: FlatSDP, prec: int = 256, reveal=None, device: int = 0):
+SUBSTITUTE = ("host", "device")
+
+
+def find_linear_dependencies(flat: FlatSDP, prec: int = 256, reveal=None, device: int = 0, substitute: str = "host"):
     """Steps 1, 2 and 4 of src/pre_postprocessing.jl:4-137 on Gram matrices.  Returns (cs, var_rels, work): the removed constraints, the
     relations between the free variables, and `work` = what `preprocess` needs to substitute (kept sets, D).
-    `reveal`: None = the device (`DeviceReveal`), or a callable (flat, D) -> an object with the same methods."""
+    `reveal`: None = the device (`DeviceReveal`), or a callable (flat, D) -> an object with the same methods.
+    `substitute`: "host" = every product in mpmath; "device" = the products over constraints through `reveal.gemm_batch` (module docstring)."""
     mp = _mp()
+    if substitute not in SUBSTITUTE:
+        raise ValueError(f"substitute must be one of {SUBSTITUTE}, got {substitute!r}")
     D = detect_limbs(prec)
     J, N = flat.n_clusters, flat.n_free
     has = _has_blocks(flat)
@@ -258,8 +276,13 @@ def find_linear_dependencies(flat: FlatSDP, prec: int = 256, reveal=None, device
     fdev = flat if len(dev_clusters) == J else _only_clusters(flat, dev_clusters)
     rv = (DeviceReveal(fdev, D, device) if reveal is None else reveal(fdev, D))
     try:
+        if substitute == "device":
+            if not hasattr(rv, "gemm_batch"):
+                raise ValueError('substitute="device" needs a `reveal` object with a gemm_batch method')
+            if _n_planes(flat) > D:
+                raise ValueError(f'substitute="device": the data carry {_n_planes(flat)} limb planes, the detection runs at {D}')
         with mp.workprec(52 * D):
-            return _find(flat, fdev, dev_clusters, rv, prec, D)
+            return _find(flat, fdev, dev_clusters, rv, prec, D, substitute == "device")
     finally:
         rv.close()
 
@@ -283,7 +306,7 @@ def _only_clusters(flat: FlatSDP, clusters: List[int]) -> FlatSDP:
     return g
 
 
-def _find(flat, fdev, dev_clusters, rv, prec, D):
+def _find(flat, fdev, dev_clusters, rv, prec, D, on_device=False):
     mp = _mp()
     J, N = flat.n_clusters, flat.n_free
     npl = _n_planes(flat)
@@ -298,6 +321,18 @@ def _find(flat, fdev, dev_clusters, rv, prec, D):
     def c_rows(j, rows):
         return _mp_sum(cpl[:, int(flat.cluster_off[j]) + np.asarray(rows, dtype=np.int64)])
 
+    def Bc_planes(j, rows):
+        """rows of [B_j | c_j] as planes (npl, len(rows), N + 1): gathers are exact on planes"""
+        o, P = int(flat.cluster_off[j]), int(flat.cluster_P[j])
+        rows = np.asarray(rows, dtype=np.int64)
+        out = np.empty((npl, len(rows), N + 1))
+        out[:, :, :N] = np.transpose(Bpl[:, o * N:(o + P) * N].reshape(npl, N, P)[:, :, rows], (0, 2, 1))
+        out[:, :, N] = cpl[:, o + rows]
+        return out
+
+    def padD(a):
+        return np.pad(a, ((0, D - a.shape[0]),) + ((0, 0),) * (a.ndim - 1))
+
     # 1. constraints: per cluster the kept set, the removed set and the relations W_j
     kept = [np.zeros(0, np.int64) for _ in range(J)]
     removed = [np.arange(int(flat.cluster_P[j]), dtype=np.int64) for j in range(J)]
@@ -307,48 +342,85 @@ def _find(flat, fdev, dev_clusters, rv, prec, D):
         for jd, (perm, r, W, _res) in enumerate(rv.dependencies(np.array(tau))):
             j = dev_clusters[jd]
             kept[j], removed[j] = np.asarray(perm[:r], dtype=np.int64), np.asarray(perm[r:], dtype=np.int64)
-            rel[j] = _mp_sum(W).reshape(len(removed[j]), r).T if r and len(removed[j]) else None      # r x removed (column-major r x (P - r))
+            if not (r and len(removed[j])):
+                rel[j] = None
+            elif on_device:
+                rel[j] = np.transpose(np.asarray(W).reshape(D, len(removed[j]), r), (0, 2, 1))        # the same as planes (D, r, removed)
+            else:
+                rel[j] = _mp_sum(W).reshape(len(removed[j]), r).T      # r x removed (column-major r x (P - r))
     cs = [(int(flat.cluster_off[j]) + int(p), j, int(p)) for j in range(J) for p in sorted(removed[j])]
     nrem = len(cs)
     # 2. conditions on the free variables: F y = g, one row per removed constraint
-    F, g = np.empty((nrem, N), dtype=object), np.empty(nrem, dtype=object)
-    row = 0
-    removed_B = []
-    for j in range(J):
-        if not len(removed[j]):
-            continue
-        rs = np.sort(removed[j])
-        order = {int(p): i for i, p in enumerate(removed[j])}
-        Br, cr = B_rows(j, rs), c_rows(j, rs)
-        removed_B.append(Br)
-        Bk, ck = (B_rows(j, kept[j]), c_rows(j, kept[j])) if len(kept[j]) else (None, None)
-        for i, p in enumerate(rs):
-            w = rel[j][:, order[int(p)]] if rel[j] is not None else None
-            for a in range(N):
-                F[row, a] = Br[i, a] - (_dot(w, Bk[:, a]) if w is not None else 0)
-            g[row] = cr[i] - (_dot(w, ck) if w is not None else 0)
-            row += 1
+    Mpl = None
+    if on_device:
+        if nrem:
+            # [F | g]_j = [B | c]_removed - W_j^T [B | c]_kept as one batch over the clusters (C preloaded with the removed rows), stacked into Mpl (D, nrem, N + 1)
+            parts, jobs = [], []
+            for j in range(J):
+                if not len(removed[j]):
+                    continue
+                rs = np.sort(removed[j])
+                Cr = Bc_planes(j, rs)
+                if rel[j] is None:
+                    parts.append(padD(Cr))
+                    continue
+                order = {int(p): i for i, p in enumerate(removed[j])}
+                parts.append(len(jobs))
+                jobs.append((rel[j][:, :, [order[int(p)] for p in rs]], Bc_planes(j, kept[j]), Cr, 1, 0, -1, 1))
+            done = rv.gemm_batch(jobs) if jobs else []
+            Mpl = np.concatenate([done[x] if isinstance(x, int) else x for x in parts], axis=1)
+    else:
+        F, g = np.empty((nrem, N), dtype=object), np.empty(nrem, dtype=object)
+        row = 0
+        removed_B = []
+        for j in range(J):
+            if not len(removed[j]):
+                continue
+            rs = np.sort(removed[j])
+            order = {int(p): i for i, p in enumerate(removed[j])}
+            Br, cr = B_rows(j, rs), c_rows(j, rs)
+            removed_B.append(Br)
+            Bk, ck = (B_rows(j, kept[j]), c_rows(j, kept[j])) if len(kept[j]) else (None, None)
+            for i, p in enumerate(rs):
+                w = rel[j][:, order[int(p)]] if rel[j] is not None else None
+                for a in range(N):
+                    F[row, a] = Br[i, a] - (_dot(w, Bk[:, a]) if w is not None else 0)
+                g[row] = cr[i] - (_dot(w, ck) if w is not None else 0)
+                row += 1
     nf, ff = [], list(range(N))
     Rref, rhs = np.empty((0, N), dtype=object), np.empty(0, dtype=object)
+    Rref_pl, rhs_pl = np.zeros((D, 0, N)), np.zeros((D, 0))
     if nrem:
-        M = np.concatenate([F, g.reshape(-1, 1)], axis=1)
         n = N + 1
-        G = np.empty((n, n), dtype=object)
-        for a in range(n):
-            for b in range(a + 1):
-                G[a, b] = G[b, a] = _dot(M[:, a], M[:, b])
-        tau2 = threshold(prec, D, max([float(G[a, a]) for a in range(N)] + [0.0]))
-        perm, r, W, res = rv.rank_reveal(_split(G.reshape(-1, order="F"), D), n, N, tau2)
+        if on_device:
+            Gp = rv.gemm_batch([(Mpl, Mpl, None, 1, 0, 1, 0)])[0]                      # [F g]^T [F g], (D, n, n)
+            tau2 = threshold(prec, D, max([float(v) for v in Gp[0].diagonal()[:N]] + [0.0]))
+            perm, r, W, res = rv.rank_reveal(np.transpose(Gp, (0, 2, 1)).reshape(D, -1), n, N, tau2)
+            Gnn = _mp_sum(Gp[:, N, N].reshape(D, 1))[0]
+        else:
+            M = np.concatenate([F, g.reshape(-1, 1)], axis=1)
+            G = np.empty((n, n), dtype=object)
+            for a in range(n):
+                for b in range(a + 1):
+                    G[a, b] = G[b, a] = _dot(M[:, a], M[:, b])
+            tau2 = threshold(prec, D, max([float(G[a, a]) for a in range(N)] + [0.0]))
+            perm, r, W, res = rv.rank_reveal(_split(G.reshape(-1, order="F"), D), n, N, tau2)
+            Gnn = G[N, N]
         perm = [int(v) for v in perm]
         nf, rest = perm[:r], perm[r:]
         gi = rest.index(N)
         resid_g = _mp_sum(res)[gi]
-        if resid_g > max(mp.mpf(2) ** -(prec - 1), mp.mpf(2) ** -(52 * D - 32) * max(mp.mpf(1), G[N, N])):
+        if resid_g > max(mp.mpf(2) ** -(prec - 1), mp.mpf(2) ** -(52 * D - 32) * max(mp.mpf(1), Gnn)):
             raise ValueError(LINDEP_MESSAGE)
         ff = [v for v in rest if v != N]
         Wm = _mp_sum(W).reshape(len(rest), r).T if r else np.empty((0, len(rest)), dtype=object)
         Rref = Wm[:, [rest.index(v) for v in ff]] if r else np.empty((0, len(ff)), dtype=object)
         rhs = Wm[:, gi] if r else np.empty(0, dtype=object)
+        if on_device and r:                      # the same coefficients as the planes rank_reveal returned (never through mpmath and back)
+            Wp = np.transpose(np.asarray(W).reshape(D, len(rest), r), (0, 2, 1))
+            Rref_pl, rhs_pl = Wp[:, :, [rest.index(v) for v in ff]], Wp[:, :, gi]
+        elif on_device:
+            Rref_pl = np.zeros((D, 0, len(ff)))
     # 4. free variables that do the same job: rank of B[kept] changemat through its Gram matrix
     nff = len(ff)
     fv_nonzeros, fv_zeros = list(range(nff)), []
@@ -357,7 +429,24 @@ def _find(flat, fdev, dev_clusters, rv, prec, D):
             Q = rv.free_gram()
         else:
             Q = np.zeros((D, N * N))
-        if nrem or nf:
+        if on_device and (nrem or nf):
+            Qp = np.transpose(np.asarray(Q).reshape(D, N, N), (0, 2, 1))
+            rows = [Bc_planes(j, np.sort(removed[j]))[:, :, :N] for j in range(J) if len(removed[j]) and j in dev_clusters]
+            if rows:                                # minus the removed rows' outer products, all clusters stacked: one product
+                Br = np.concatenate(rows, axis=1)
+                Qp = rv.gemm_batch([(Br, Br, Qp, 1, 0, -1, 1)])[0]
+            # changemat^T Q changemat as two products; changemat is written as planes: unit rows for ff, the negated planes of Rref for nf
+            T = np.zeros((D, N, nff))
+            T[0, ff, np.arange(nff)] = 1.0
+            if nf:
+                T[:, nf, :] = -Rref_pl
+            QT = rv.gemm_batch([(Qp, T, None, 0, 0, 1, 0)])[0]
+            Gf = rv.gemm_batch([(T, QT, None, 1, 0, 1, 0)])[0]
+            # T^T (Q T) is symmetric only up to the rounding of D limbs: the lower triangle is mirrored, as the host path builds it, so that the pivoting
+            # cannot depend on which triangle an elimination reads
+            Gf = np.stack([np.tril(P) + np.tril(P, -1).T for P in Gf])
+            Gl = np.transpose(Gf, (0, 2, 1)).reshape(D, -1)
+        elif nrem or nf:
             Qm = _mp_sum(Q).reshape(N, N, order="F") if np.any(Q != 0.0) else np.full((N, N), mp.mpf(0), dtype=object)
             for j in range(J):                      # minus the removed rows' outer products (clusters the device saw only)
                 if not len(removed[j]) or j not in dev_clusters:
@@ -384,16 +473,20 @@ def _find(flat, fdev, dev_clusters, rv, prec, D):
         fv_zeros = sorted(int(v) for v in perm[r:])
     var_rels = VarRels((fv_zeros, fv_nonzeros, Rref, rhs, nf, ff))
     work = dict(D=D, kept=[np.sort(k) for k in kept], B_rows=B_rows, c_rows=c_rows)
+    if on_device:
+        work.update(Bc_planes=Bc_planes, Rref_pl=Rref_pl, rhs_pl=rhs_pl, gemm_batch=rv.gemm_batch)
     return cs, var_rels, work
 
 
-def preprocess(sdp, prec: int = 256, reveal=None, device: int = 0):
+def preprocess(sdp, prec: int = 256, reveal=None, device: int = 0, substitute: str = "host"):
     """The reference's `preprocess!` on a FlatSDP: returns (reduced FlatSDP, cs, var_rels); the input object itself when nothing was found.
     The substitution (remove_lindep_freevars!, :215-235) runs in mpmath at 52 D bits; its results keep D limb planes (hi, lo, `tails`), so
-    that a solve with data_limbs = limbs sees them unrounded.  `reduced.constant` is the fp64 rounding of `var_rels.constant`."""
+    that a solve with data_limbs = limbs sees them unrounded.  `reduced.constant` is the fp64 rounding of `var_rels.constant`.
+    `substitute` = "device": the reduced B and c are one batch of multi-word products over the clusters, [B | c]_kept [changemat(:, kept columns) | -rhs],
+    on the planes `rank_reveal` returned (`find_linear_dependencies`); b and the constant stay in mpmath."""
     mp = _mp()
     flat = sdp if isinstance(sdp, FlatSDP) else flatten(sdp)
-    cs, vr, work = find_linear_dependencies(flat, prec=prec, reveal=reveal, device=device)
+    cs, vr, work = find_linear_dependencies(flat, prec=prec, reveal=reveal, device=device, substitute=substitute)
     fv_zeros, fv_nonzeros, Rref, rhs, nf, ff = vr
     D, kept = work["D"], work["kept"]
     with mp.workprec(52 * D):
@@ -407,18 +500,33 @@ def preprocess(sdp, prec: int = 256, reveal=None, device: int = 0):
         npl = _n_planes(flat)
         b = _mp_sum(flat.data_planes_of("b", npl))
         B_pl, c_pl = [], []
-        for j in range(J):
-            rows = kept[j]
-            Bk = work["B_rows"](j, rows) if len(rows) else np.empty((0, N), dtype=object)
-            ck = work["c_rows"](j, rows) if len(rows) else np.empty(0, dtype=object)
-            Bn, cn = np.empty((len(rows), len(cols)), dtype=object), np.empty(len(rows), dtype=object)
-            for i in range(len(rows)):
-                Bnf = [Bk[i, k] for k in nf]
-                for a, pos in enumerate(fv_nonzeros):
-                    Bn[i, a] = Bk[i, cols[a]] - (_dot(Bnf, Rref[:, pos]) if nf else 0)
-                cn[i] = ck[i] - (_dot(Bnf, rhs) if nf else 0)
-            B_pl.append(_split(Bn, max(D, 2)))
-            c_pl.append(_split(cn, max(D, 2)))
+        if substitute == "device":
+            nnz, nn = len(cols), len(nf)
+            S = np.zeros((D, N + 1, nnz + 1))           # [changemat(:, kept columns) | -rhs] over a last row (0 .. 0 1) that carries c
+            S[0, cols, np.arange(nnz)] = 1.0
+            S[0, N, nnz] = 1.0
+            if nn:
+                S[:, nf, :nnz] = -work["Rref_pl"][:, :, fv_nonzeros]
+                S[:, nf, nnz] = -work["rhs_pl"]
+            jobs = [(work["Bc_planes"](j, kept[j]), S, None, 0, 0, 1, 0) for j in range(J) if len(kept[j])]
+            done = iter(work["gemm_batch"](jobs) if jobs else [])
+            for j in range(J):
+                R = next(done) if len(kept[j]) else np.zeros((D, 0, nnz + 1))
+                B_pl.append(np.ascontiguousarray(R[:, :, :nnz]))
+                c_pl.append(np.ascontiguousarray(R[:, :, nnz]))
+        else:
+            for j in range(J):
+                rows = kept[j]
+                Bk = work["B_rows"](j, rows) if len(rows) else np.empty((0, N), dtype=object)
+                ck = work["c_rows"](j, rows) if len(rows) else np.empty(0, dtype=object)
+                Bn, cn = np.empty((len(rows), len(cols)), dtype=object), np.empty(len(rows), dtype=object)
+                for i in range(len(rows)):
+                    Bnf = [Bk[i, k] for k in nf]
+                    for a, pos in enumerate(fv_nonzeros):
+                        Bn[i, a] = Bk[i, cols[a]] - (_dot(Bnf, Rref[:, pos]) if nf else 0)
+                    cn[i] = ck[i] - (_dot(Bnf, rhs) if nf else 0)
+                B_pl.append(_split(Bn, max(D, 2)))
+                c_pl.append(_split(cn, max(D, 2)))
         bnf = [b[k] for k in nf]
         bn = np.array([b[cols[a]] - (_dot(bnf, Rref[:, pos]) if nf else 0) for a, pos in enumerate(fv_nonzeros)], dtype=object)
         vr.constant = mp.mpf(flat.constant) + (_dot(bnf, rhs) if nf else 0)

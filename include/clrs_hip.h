@@ -353,12 +353,27 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   order), rank[m] = r, W (same offsets and planes as G: the r x (n - r) matrix G11^-1 G12, column-major with leading dimension r, in the first r (n - r)
  *   entries of the matrix's range) and resid (planar [limbs][sum n]: the remaining diagonal of the n - r non-pivots, in the first n - r entries of the range).
  * clrs_mw_constraint_dependencies: Gram + rank reveal per cluster (every constraint a candidate) without the Gram matrices leaving the device; tau [J], perm and
- *   resid in the x layout, rank [J], W in the planar S layout.  The context needs a new assembly before its next factorisation. */
+ *   resid in the x layout, rank [J], W in the planar S layout.  The context needs a new assembly before its next factorisation.
+ * clrs_mw_gemm: a batch of independent products C <- beta C + alpha op(A) op(B) in `limbs` limbs (4, 5, 6, 8 or 10), one launch, no context (host pointers): the
+ *   substitution of the preprocessing and any other product of matrices outside a context.  A, B, C are planar pools: limb l of element o of a pool is
+ *   pool[l * plane + o], so a pool is limbs * plane doubles; A and B may be the same pool.  Job i: op(A) is m x k, op(B) is k x n, C is m x n; the matrices are
+ *   column-major with leading dimensions lda, ldb, ldc at element offsets a_off, b_off, c_off of their pools (op = transpose when transa / transb is nonzero: A is
+ *   then stored k x m); alpha is -1 or +1, beta is -1, 0 or +1 (exact scalings).  Every entry is summed in one fixed order (r ascending, one renormalisation, then
+ *   one multi-word add of beta C), so results are reproducible bit for bit.  beta = 0 never reads C; rows m .. ldc - 1 of C are never written; k = 0 gives
+ *   C <- beta C; m = 0 or n = 0 is a no-op.  CLRS_ERR_INVALID (message: clrs_last_error): limbs not on offer, alpha / beta out of range, a negative size or offset,
+ *   a leading dimension smaller than the rows it holds, a matrix that leaves its plane, null pools with a non-empty job, or two jobs whose C ranges
+ *   [c_off, c_off + (n - 1) ldc + m) overlap (the ranges as intervals: interleaved outputs are refused too). */
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
 int clrs_mw_rank_reveal(int device, int limbs, int nmat, const int32_t *n, const int32_t *ncand, const double *G, const double *tau, int32_t *perm, int32_t *rank,
                         double *W, double *resid);
 int clrs_mw_constraint_dependencies(clrs_mw_ctx *ctx, const double *tau, int32_t *perm, int32_t *rank, double *W, double *resid);
+typedef struct clrs_mw_gemm_job {
+    int32_t m, n, k, transa, transb, alpha, beta, lda, ldb, ldc;
+    int64_t a_off, b_off, c_off;
+} clrs_mw_gemm_job;
+int clrs_mw_gemm(int device, int limbs, int njobs, const clrs_mw_gemm_job *jobs, const double *A, int64_t a_plane, const double *B, int64_t b_plane, double *C,
+                 int64_t c_plane);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 

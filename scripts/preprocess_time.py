@@ -2,6 +2,9 @@
 without planted dependencies, and the time of one stand-alone rank-revealing call (copies included) on a matrix beyond LDS and on LDS-resident ones; writes profiles/preprocess/times.json.
 
     python scripts/preprocess_time.py [--limbs 5] [--out profiles/preprocess/times.json]
+
+`--substitute device` / `both`: the substitution on the device (preprocess(substitute="device")), alone or next to the host substitution in the same
+process; per instance and mode the total seconds and the seconds spent outside the device steps (host: mpmath); writes profiles/preprocess/times_device.json.
 """
 import argparse
 import json
@@ -34,7 +37,7 @@ def timed_reveal(log):
             finally:
                 log[name] = log.get(name, 0.0) + time.perf_counter() - t
         return f
-    for name in ("__init__", "gram_diag", "dependencies", "free_gram", "rank_reveal"):
+    for name in ("__init__", "gram_diag", "dependencies", "free_gram", "rank_reveal", "gemm_batch"):
         setattr(Timed, name, wrap(name))
     return Timed
 
@@ -42,14 +45,46 @@ def timed_reveal(log):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--limbs", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "preprocess", "times.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--substitute", choices=("host", "device", "both"), default="host")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "preprocess", "times.json" if args.substitute == "host" else "times_device.json")
     import clrs_amd
     from clrs_amd.mw import rank_reveal, solvesdp_mw
     from clrs_amd.preprocess import preprocess
     from tests.preprocess_host import plant_dependencies
     from tests.util import instance
     out = dict(limbs=args.limbs, instances={})
+    if args.substitute != "host":
+        from clrs_amd.preprocess import detect_limbs
+        out = dict(prec=256, detect_limbs=detect_limbs(256), instances={})          # (no solve here: --limbs is not used)
+        modes = ("host", "device") if args.substitute == "both" else ("device",)
+        for name, plants in PLANTS.items():
+            base = instance(name)
+            for tag, sdp in (("as_is", base), ("planted", plant_dependencies(base, plants))):
+                f = clrs_amd.flatten(sdp)
+                rec = dict(clusters=int(f.n_clusters), max_P=int(np.max(f.cluster_P)), n_free=int(f.n_free))
+                for mode in modes:
+                    preprocess(f, prec=256, substitute=mode)              # (first call: loads the code objects)
+                    best = None
+                    for _ in range(3):
+                        log = {}
+                        t = time.perf_counter()
+                        red, cs, vr = preprocess(f, prec=256, reveal=timed_reveal(log), substitute=mode)
+                        t_pre = time.perf_counter() - t
+                        if best is None or t_pre < best["total_seconds"]:
+                            best = dict(total_seconds=t_pre, host_mpmath_seconds=t_pre - sum(log.values()), device_steps_seconds=log,
+                                        removed_constraints=len(cs), removed_variables=int(f.n_free - red.n_free))
+                    rec[mode] = best
+                if len(modes) == 2:
+                    rec["host_over_device"] = rec["host"]["total_seconds"] / rec["device"]["total_seconds"]
+                out["instances"][f"{name}/{tag}"] = rec
+                print(name, tag, json.dumps(rec), flush=True)
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        json.dump(out, open(args.out, "w"), indent=1, sort_keys=True)
+        print("wrote", args.out)
+        return
     for name, plants in PLANTS.items():
         base = instance(name)
         for tag, sdp in (("as_is", base), ("planted", plant_dependencies(base, plants))):
