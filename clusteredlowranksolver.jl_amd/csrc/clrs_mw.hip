@@ -2,11 +2,9 @@
 // (include/clrs_hip.h, clrs_mw_*).  Compiled with -ffp-contract=off (clrs_mw_arith.h) and linked into libclrs_hip.so.
 //
 // A context of its own (clrs_mw_ctx), created from the same clrs_sdp_desc as the fp64 context: the de-duplication of
-// the sampled vectors (precompute_matrices_bilinear_pairings, src/solver.jl:985-1059) is redone here into ONE table of
-// expanded unique vectors per PSD block -- a vector of sub-block r is stored with its delta entries at rows
-// r*delta.. and zeros elsewhere, duplicates removed by exact equality as the reference does (src/tools.jl:128-145) -- so
-// that both pairing matrices of a block are plain symmetric products V^T X^-1 V and V^T Y V, and the reference's
-// pointers_left / pointers_right dictionaries become two integers per term.
+// the sampled vectors (precompute_matrices_bilinear_pairings, src/solver.jl:985-1059) is redone into ONE table of
+// expanded unique vectors per PSD block by the host-only table builder (clrs_mw_tables.h, which says what the tables
+// hold); creation here is the sequence of stages around it (clrs_mw_create_opts).
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -15,10 +13,9 @@
 #include <condition_variable>
 #include <cstdio>
 #include <cstring>
-#include <map>
+#include <memory>
 #include <mutex>
 #include <string>
-#include <tuple>
 #include <vector>
 
 #include "../../include/clrs_hip.h"
@@ -29,6 +26,7 @@
 #include "clrs_mw_rank.hip.h"
 #include "clrs_mw_gemm.hip.h"
 #include "clrs_mw_inst.h"
+#include "clrs_mw_tables.h"      // host only: mw_build_tables, mw_cut_digits
 #ifdef MW_SPLIT_UNITS        // the kernels of these limb counts are compiled in units of their own (clrs_mw_inst.hip)
 MW_KERNELS_ALL(extern template, 4)
 MW_KERNELS_ALL(extern template, 5)
@@ -251,233 +249,67 @@ extern "C" int clrs_mw_create_ex(const clrs_sdp_desc *d, int data_limbs, int dev
     return clrs_mw_create_opts(d, data_limbs, device, limbs, nullptr, out);
 }
 
+// ---- context creation: clrs_mw_create_opts is the sequence of the stages below; a stage returns 0 or the error code (its message is set), and the
+// caller's guard destroys the half-built context on every failure ----
+#define MW_RET(call) do { if (int rc_ = (call)) return rc_; } while (0)
+static int mw_hip(hipError_t e, const char *what) {
+    return e == hipSuccess ? 0 : mw_fail(CLRS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+// `count` elements with every byte set to `byte`, owned by the context
+template <class T>
+static int mw_alloc_fill(clrs_mw_ctx *c, T **p, size_t count, int byte) {
+    if (hipMalloc((void **)p, count * sizeof(T)) != hipSuccess) return mw_fail(CLRS_ERR_HIP, "hipMalloc failed");
+    c->allocs.push_back(*p);
+    if (hipMemset(*p, byte, count * sizeof(T)) != hipSuccess) return mw_fail(CLRS_ERR_HIP, "hipMemset failed");
+    return 0;
+}
+
 // opts: per-context choices (a field < 0, or opts == NULL: the process-wide default of clrs_config_set) -- contexts created side by side from
 // several threads do not share a knob this way
-extern "C" int clrs_mw_create_opts(const clrs_sdp_desc *d, int data_limbs, int device, int limbs, const clrs_mw_options *opts, clrs_mw_ctx **out) {
-    if (!d || !out) return mw_fail(CLRS_ERR_INVALID, "null argument");
-    int cfg_exact = opts && opts->exact_products >= 0 ? opts->exact_products : g_cfg_mw_exact_products;
-    const int cfg_refine = opts && opts->refine >= 0 ? opts->refine : g_cfg_mw_refine;
-    const int cfg_pipe = opts && opts->pipeline >= 0 ? opts->pipeline : g_cfg_mw_pipeline;
-    const int cfg_refine_pred = opts && opts->refine_predictor >= 0 ? opts->refine_predictor : g_cfg_mw_refine_predictor;
-    const int cfg_factor_limbs = opts && opts->factor_limbs >= 0 ? opts->factor_limbs : g_cfg_mw_factor_limbs;
+struct MwOpts { int exact, refine, pipe, refine_pred, factor_limbs, km; };
+static int mw_resolve_opts(const clrs_mw_options *opts, int limbs, int data_limbs, MwOpts &o) {
+    o.exact = opts && opts->exact_products >= 0 ? opts->exact_products : g_cfg_mw_exact_products;
+    o.refine = opts && opts->refine >= 0 ? opts->refine : g_cfg_mw_refine;
+    o.pipe = opts && opts->pipeline >= 0 ? opts->pipeline : g_cfg_mw_pipeline;
+    o.refine_pred = opts && opts->refine_predictor >= 0 ? opts->refine_predictor : g_cfg_mw_refine_predictor;
+    o.factor_limbs = opts && opts->factor_limbs >= 0 ? opts->factor_limbs : g_cfg_mw_factor_limbs;
     // matmul_prec of the reference (src/solver.jl:125): limbs of the pairing products, rounded UP to the next count on offer (mw_km_ok); 0 = the context's limbs
-    int cfg_km = opts && opts->matmul_limbs > 0 ? opts->matmul_limbs : limbs;
-    if (cfg_km > limbs) cfg_km = limbs;
-    while (cfg_km < limbs && !mw_km_ok(limbs, cfg_km)) cfg_km++;
-    if (data_limbs > 2) cfg_exact = 0;                     // (the static digits of the exact slice products are cut from two data limbs)
-    if (cfg_km < limbs) cfg_exact = 0;                     // (the exact slice products have one slice count per limb count: the expansion kernels take the reduced products)
-    if (cfg_exact > 2 || cfg_refine > 2) return mw_fail(CLRS_ERR_INVALID, "clrs_mw_options: exact_products and refine are 0, 1 or 2 (or < 0 for the default)");
+    o.km = opts && opts->matmul_limbs > 0 ? opts->matmul_limbs : limbs;
+    if (o.km > limbs) o.km = limbs;
+    while (o.km < limbs && !mw_km_ok(limbs, o.km)) o.km++;
+    if (data_limbs > 2) o.exact = 0;                     // (the static digits of the exact slice products are cut from two data limbs)
+    if (o.km < limbs) o.exact = 0;                       // (the exact slice products have one slice count per limb count: the expansion kernels take the reduced products)
+    if (o.exact > 2 || o.refine > 2) return mw_fail(CLRS_ERR_INVALID, "clrs_mw_options: exact_products and refine are 0, 1 or 2 (or < 0 for the default)");
     if (limbs < 2 || limbs > 10 || limbs == 7 || limbs == 9) return mw_fail(CLRS_ERR_INVALID, "limbs must be 2..6, 8 or 10");
     if (data_limbs < 1 || data_limbs > limbs || (data_limbs > 2 && data_limbs != limbs))
         return mw_fail(CLRS_ERR_INVALID, "data limbs must be 1, 2 or the context's limbs (the problem data at the working precision: src/interface.jl:1078-1112)");
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device >= ndev) return mw_fail(CLRS_ERR_NO_DEVICE, "no usable HIP device");
-    MWCHECK(hipSetDevice(device));
-    clrs_mw_ctx *c = new clrs_mw_ctx();
-    c->device = device;
-    c->K = limbs;
-    c->DK = data_limbs;
-    const int K = limbs, DK = data_limbs;
-    const int J = d->n_clusters, N = d->n_free, NB = d->n_blocks;
-    if (J <= 0 || N < 0 || NB < 0) { delete c; return mw_fail(CLRS_ERR_INVALID, "bad sizes"); }
-    int rc = 0;
-#define MW_BAIL(code, msg) do { clrs_mw_destroy(c); return mw_fail(code, msg); } while (0)
-#define MW_TRY(call) do { if ((rc = (call))) { clrs_mw_destroy(c); return rc; } } while (0)
+    return 0;
+}
+
+static int mw_stage_stream(clrs_mw_ctx *c) {
     {   // The context's stream at the HIGHEST priority, the side stream of the interior-point iteration (clrs_mw_ipm_host.inc) at the default one: the runtime
         // maps streams onto a few hardware queues PER PRIORITY (GPU_MAX_HW_QUEUES, 4 by default), and two streams of one iteration that land on one queue run
         // its packets in submission order -- measured: the second context of a process, whose side stream shared a queue, 0.58 ms per iteration against
         // 0.45 (profiles/r05).  Different priorities never share; and the main stream carries the longest chain of the iteration.
         int least = 0, greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { least = greatest = 0; (void)hipGetLastError(); }
-        if (hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, greatest) != hipSuccess) MW_BAIL(CLRS_ERR_HIP, "hipStreamCreateWithPriority failed");
+        if (hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, greatest) != hipSuccess) return mw_fail(CLRS_ERR_HIP, "hipStreamCreateWithPriority failed");
     }
-    if (hipHostMalloc((void **)&c->h_info, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess) MW_BAIL(CLRS_ERR_HIP, "hipHostMalloc failed");
-    // ---- clusters ----
-    c->clu.resize(J);
-    i64 xlen = 0, Slen = 0;
-    for (int j = 0; j < J; j++) {
-        MwClu &q = c->clu[j];
-        q.P = d->cluster_P[j];
-        if (q.P <= 0) MW_BAIL(CLRS_ERR_INVALID, "cluster without constraints");
-        q.coff = xlen; q.Soff = Slen; q.b0 = NB; q.b1 = 0;
-        xlen += q.P; Slen += (i64)q.P * q.P;
-        c->maxP = std::max(c->maxP, q.P);
-    }
-    // ---- blocks, unique expanded vectors, term tables ----
-    c->blk.resize(NB);
-    const i64 T = NB ? d->term_ptr[NB] : 0, D = NB ? d->dense_ptr[NB] : 0;
-    // planes of the description's data arrays (data_limbs planes each)
-    const i64 vec_plane = T ? d->term_vec_ptr[T] : 0, dA_plane = D ? d->dense_A_ptr[D] : 0;
-    std::vector<double> hV;          // limb 0 while the tables are built; the other limbs follow below
-    std::vector<int> hvrow, st_a(std::max<i64>(T, 1)), st_b(std::max<i64>(T, 1)), htptr, ay_a(std::max<i64>(T, 1), 0), ay_b(std::max<i64>(T, 1), 0),
-        ay_blk(std::max<i64>(T, 1), -1), hdmap, lr_list, dn_list;
-    std::vector<std::tuple<i64, int, int>> drow_pairs;       // (stacked row, block, entry) of every dense matrix
-    std::vector<double> st_lam((size_t)std::max<i64>(T, 1) * DK), hdA;
-    std::vector<std::vector<double>> hVl(DK), hdAl(DK);     // per limb
-    // for the interior-point iteration around the path (clrs_mw_ipm.hip.h), sorted term order: original term, vs at sub-block r / ws at
-    // sub-block s (compute_weighted_A!, src/solver.jl:1433-1459), ws at r / vs at s (trace_A, :1334-1341), and the flags s <= r, r != s
-    std::vector<int> st_orig(std::max<i64>(T, 1)), st_war(std::max<i64>(T, 1)), st_wac(std::max<i64>(T, 1)), st_trl(std::max<i64>(T, 1)),
-        st_trd(std::max<i64>(T, 1)), st_flag(std::max<i64>(T, 1)), st_p(std::max<i64>(T, 1));
-    i64 xyoff = 0, rdoff = 0, zoff = 0, goff = 0, sdoff = 0, woff = 0;
-    double cnt_mul = 0;
-    for (int b = 0; b < NB; b++) {
-        MwBlk &k = c->blk[b];
-        std::memset(&k, 0, sizeof(k));
-        k.j = d->block_cluster[b];
-        if (k.j < 0 || k.j >= J || (b > 0 && k.j < c->blk[b - 1].j)) MW_BAIL(CLRS_ERR_INVALID, "block_cluster must be non-decreasing and within range");
-        const int m = d->block_m[b];
-        k.delta = d->block_delta[b];
-        k.n = m * k.delta;
-        k.kind = d->block_kind[b];
-        k.m = m;
-        k.P = c->clu[k.j].P;
-        if (k.n <= 0 || (k.kind != 0 && m != 1)) MW_BAIL(CLRS_ERR_INVALID, "bad block shape");
-        k.xyoff = xyoff; xyoff += (i64)k.n * k.n;
-        k.rd_off = rdoff; rdoff += k.n;
-        c->clu[k.j].b0 = std::min(c->clu[k.j].b0, b);
-        c->clu[k.j].b1 = std::max(c->clu[k.j].b1, b + 1);
-        c->maxn = std::max(c->maxn, k.n);
-        if (k.kind != 0) c->maxn_dense = std::max(c->maxn_dense, k.n);
-        const int P = k.P, n = k.n, dl = k.delta;
-        if (k.kind == 0) {
-            lr_list.push_back(b);
-            const i64 t0 = d->term_ptr[b], t1 = d->term_ptr[b + 1];
-            k.t0 = t0;
-            c->maxTb = std::max(c->maxTb, (int)(t1 - t0));
-            // unique expanded vectors: (sub-block, delta values), exact equality, first occurrence wins
-            std::vector<std::pair<int, const double *>> uniq;      // (sub-block, pointer to limb 0 of the vector inside term_vs / term_ws)
-            auto find_or_add = [&](int r, const double *v) -> int {
-                for (size_t u = 0; u < uniq.size(); u++) {
-                    if (uniq[u].first != r) continue;
-                    bool eq = true;
-                    for (int l = 0; l < DK && eq; l++)
-                        for (int i = 0; i < dl && eq; i++) eq = uniq[u].second[(i64)l * vec_plane + i] == v[(i64)l * vec_plane + i];
-                    if (eq) return (int)u;
-                }
-                uniq.push_back({r, v});
-                return (int)uniq.size() - 1;
-            };
-            std::map<std::tuple<int, int, int, int>, i64> index;
-            for (i64 t = t0; t < t1; t++) {
-                if (d->term_p[t] < 0 || d->term_p[t] >= P || d->term_r[t] < 0 || d->term_r[t] >= m || d->term_s[t] < 0 || d->term_s[t] >= m)
-                    MW_BAIL(CLRS_ERR_INVALID, "term index out of range");
-                if (d->term_vec_ptr[t + 1] - d->term_vec_ptr[t] != dl) MW_BAIL(CLRS_ERR_INVALID, "term vectors must have delta entries");
-                index[std::make_tuple(d->term_p[t], d->term_r[t], d->term_s[t], d->term_rank[t])] = t;
-            }
-            // R(t): vs of the term at sub-block r; Lself(t): ws of the term at sub-block r   (rightvecs[r] / leftvecs[r], src/solver.jl:1011, 1032)
-            std::vector<int> Rt(t1 - t0), Ls(t1 - t0), Cs(t1 - t0), Ds(t1 - t0);
-            std::vector<i64> partner(t1 - t0);
-            for (i64 t = t0; t < t1; t++) {
-                Rt[t - t0] = find_or_add(d->term_r[t], d->term_vs + d->term_vec_ptr[t]);
-                Ls[t - t0] = find_or_add(d->term_r[t], d->term_ws + d->term_vec_ptr[t]);
-                Cs[t - t0] = find_or_add(d->term_s[t], d->term_ws + d->term_vec_ptr[t]);
-                Ds[t - t0] = find_or_add(d->term_s[t], d->term_vs + d->term_vec_ptr[t]);
-                auto it = index.find(std::make_tuple(d->term_p[t], d->term_s[t], d->term_r[t], d->term_rank[t]));
-                if (it == index.end()) MW_BAIL(CLRS_ERR_INVALID, "term without transposed partner: A[r,s][p] must equal A[s,r][p]^T");
-                partner[t - t0] = it->second;
-            }
-            k.U = (int)uniq.size();
-            c->maxU = std::max(c->maxU, k.U);
-            k.v_off = (i64)hVl[0].size();
-            k.vrow_off = (i64)hvrow.size();
-            for (int l = 0; l < DK; l++) hVl[l].resize(hVl[l].size() + (size_t)n * k.U, 0.0);
-            for (int u = 0; u < k.U; u++) {
-                hvrow.push_back(uniq[u].first * dl);
-                for (int l = 0; l < DK; l++)
-                    for (int i = 0; i < dl; i++) hVl[l][k.v_off + (i64)u * n + uniq[u].first * dl + i] = uniq[u].second[(i64)l * vec_plane + i];
-            }
-            k.z_off = zoff; zoff += (i64)n * k.U;
-            k.g_off = goff; goff += (i64)k.U * k.U;
-            // terms sorted by constraint (stable), CSR over p
-            std::vector<i64> order(t1 - t0);
-            for (i64 t = t0; t < t1; t++) order[t - t0] = t;
-            std::stable_sort(order.begin(), order.end(), [&](i64 a, i64 b2) { return d->term_p[a] < d->term_p[b2]; });
-            k.tptr_off = (i64)htptr.size();
-            htptr.resize(htptr.size() + P + 1, 0);
-            int *tp = htptr.data() + k.tptr_off;
-            for (i64 i = 0; i < t1 - t0; i++) tp[d->term_p[order[i]] + 1]++;
-            tp[0] = (int)t0;
-            for (int p = 0; p < P; p++) tp[p + 1] += tp[p];
-            for (i64 i = 0; i < t1 - t0; i++) {
-                const i64 t = order[i];
-                st_a[t0 + i] = Ls[partner[t - t0] - t0];      // pointers_left[s][(r,p,k)] = ws of A[s,r][p]
-                st_b[t0 + i] = Rt[t - t0];                    // pointers_right[r][(s,p,k)] = vs of A[r,s][p]
-                for (int l = 0; l < DK; l++) st_lam[(size_t)l * std::max<i64>(T, 1) + t0 + i] = d->term_lambda[(i64)l * T + t];
-                st_orig[t0 + i] = (int)t;
-                st_p[t0 + i] = d->term_p[t];
-                st_war[t0 + i] = Rt[t - t0]; st_wac[t0 + i] = Cs[t - t0];
-                st_trl[t0 + i] = Ls[t - t0]; st_trd[t0 + i] = Ds[t - t0];
-                st_flag[t0 + i] = (d->term_s[t] <= d->term_r[t] ? 1 : 0) | (d->term_s[t] != d->term_r[t] ? 2 : 0);
-            }
-            for (i64 t = t0; t < t1; t++) {                    // A_Y[r,s][idx] = bpY[r,s][left_r(s,p,k), right_s(r,p,k)]  (src/solver.jl:1162)
-                ay_blk[t] = b;
-                ay_a[t] = Ls[t - t0];
-                ay_b[t] = Rt[partner[t - t0] - t0];
-            }
-            // algorithmic multi-word multiply-adds of the assembly of this block: T = Y V, Z = L^-1 V, GX, GY (lower triangles), S
-            cnt_mul += (double)n * dl * k.U + 0.5 * (double)n * n * k.U + 0.5 * (double)k.U * k.U * (n + dl);
-            for (int p = 0; p < P; p++)
-                for (int q2 = p; q2 < P; q2++) cnt_mul += (double)(tp[p + 1] - tp[p]) * (tp[q2 + 1] - tp[q2]);
-        } else {
-            dn_list.push_back(b);
-            const i64 d0 = d->dense_ptr[b], d1 = d->dense_ptr[b + 1];
-            k.cnt = (int)(d1 - d0);
-            k.d0 = d0;
-            k.a_off = (i64)hdAl[0].size();
-            k.dmap_off = (i64)hdmap.size();
-            hdmap.resize(hdmap.size() + P, -1);
-            for (i64 e = d0; e < d1; e++) {
-                const int p = d->dense_p[e];
-                if (p < 0 || p >= P) MW_BAIL(CLRS_ERR_INVALID, "dense constraint index out of range");
-                if (d->dense_A_ptr[e + 1] - d->dense_A_ptr[e] != (i64)n * n) MW_BAIL(CLRS_ERR_INVALID, "dense matrix must have n*n entries");
-                for (int l = 0; l < DK; l++) {          // symmetric, as the reference's constructor makes them (src/interface.jl:1010-1017)
-                    const double *Ae = d->dense_A + (i64)l * dA_plane + d->dense_A_ptr[e];
-                    for (int cc = 0; cc < n; cc++)
-                        for (int rr = cc + 1; rr < n; rr++)
-                            if (Ae[rr + (i64)cc * n] != Ae[cc + (i64)rr * n]) MW_BAIL(CLRS_ERR_INVALID, "dense constraint matrices must be symmetric");
-                }
-                hdmap[k.dmap_off + p] = (int)(e - d0);
-                drow_pairs.push_back(std::make_tuple(c->clu[k.j].coff + p, b, (int)(e - d0)));
-                for (int l = 0; l < DK; l++)
-                    hdAl[l].insert(hdAl[l].end(), d->dense_A + (i64)l * dA_plane + d->dense_A_ptr[e], d->dense_A + (i64)l * dA_plane + d->dense_A_ptr[e + 1]);
-            }
-            k.sd_off = sdoff; sdoff += (i64)k.cnt * k.cnt;
-            k.w_off = woff; woff += (i64)k.cnt * n * n;
-            cnt_mul += (double)k.cnt * (2.0 * n * n * n + 0.5 * (double)k.cnt * n * n);
-        }
-    }
-    for (int j = 0; j < J; j++)
-        if (c->clu[j].b0 > c->clu[j].b1) { c->clu[j].b0 = c->clu[j].b1 = 0; }
-    {
-        int mostb = 1;
-        for (int j = 0; j < J; j++) mostb = std::max(mostb, c->clu[j].b1 - c->clu[j].b0);
-        c->sa_lanes = mostb >= 3 ? 4 : mostb;
-        // (one lane per entry when the launch fills the chip anyway was tried at 2048 clusters: 30 M wave instructions instead of 90 M, and
-        // 390 us instead of 245: the chains of dependent loads of a cluster's blocks, one after the other, cost more than the idle lanes)
-        // clusters with at most four blocks and at most one low-rank term per (constraint, block): k_mw_saccum_one
-        for (int j = 0; j < J; j++) {
-            MwClu &cl = c->clu[j];
-            bool one = J >= 32 && cl.b1 - cl.b0 >= 1 && cl.b1 - cl.b0 <= 4;      // (with a few clusters the launch is latency bound and a lane per block wins: 6.9 against 9.1 us on the named problem)
-            for (int b = cl.b0; b < cl.b1 && one; b++) {
-                const MwBlk &k = c->blk[b];
-                if (k.kind != 0) continue;
-                const int *tp = htptr.data() + k.tptr_off;
-                for (int p = 0; p < cl.P && one; p++) one = tp[p + 1] - tp[p] <= 1;
-            }
-            cl.one_term = one ? 1 : 0;
-            (one ? c->n_one_term : c->n_many_term)++;
-        }
-    }
-    c->cnt_mul = cnt_mul;
-    for (int j = 0; j < J; j++) {
-        const double P = c->clu[j].P;
-        c->cnt_factor += P * P * P / 6.0 + 0.5 * P * P * N + 0.5 * P * (double)N * N;
-        c->cnt_solve += P * P + 2.0 * P * N;
-    }
-    c->cnt_factor += (double)N * N * N / 6.0;
-    c->cnt_solve += (double)N * N;
-    // ---- LDS plans ----
+    if (hipHostMalloc((void **)&c->h_info, 2 * sizeof(int), hipHostMallocDefault) != hipSuccess) return mw_fail(CLRS_ERR_HIP, "hipHostMalloc failed");
+    return 0;
+}
+
+// the block and cluster records move into the context (the LDS plans below fill MwBlk::inv and MwClu::lds), the sizes and counters are copied
+static void mw_adopt_tables(clrs_mw_ctx *c, MwTables &t) {
+    c->blk.swap(t.blk); c->clu.swap(t.clu);
+    c->maxU = t.maxU; c->maxP = t.maxP; c->maxn = t.maxn; c->maxn_dense = t.maxn_dense; c->maxTb = t.maxTb; c->maxcnt = t.maxcnt;
+    c->sa_lanes = t.sa_lanes; c->n_one_term = t.n_one_term; c->n_many_term = t.n_many_term;
+    c->cnt_mul = t.cnt_mul; c->cnt_factor = t.cnt_factor; c->cnt_solve = t.cnt_solve;
+    c->wide_solve = c->maxP > 64 || t.N > 64;
+}
+
+static int mw_stage_lds(clrs_mw_ctx *c, const MwTables &t) {
+    const int K = c->K, J = t.J, N = t.N;
     const size_t lim = MW_LDS_MAX / sizeof(double);
     {
         size_t nn = (size_t)c->maxn * c->maxn * K;
@@ -496,10 +328,10 @@ extern "C" int clrs_mw_create_opts(const clrs_sdp_desc *d, int data_limbs, int d
         size_t zt = (size_t)c->maxn * MW_CT * K;
         c->lds_zt_L = zt + nn <= lim;
         c->sm_zt = (zt + (c->lds_zt_L ? nn : 0)) * 8;
-        if (zt > lim) MW_BAIL(CLRS_ERR_INVALID, "PSD block too large for the multi-word kernels");
+        if (zt > lim) return mw_fail(CLRS_ERR_INVALID, "PSD block too large for the multi-word kernels");
         size_t maxnd = 0;
         for (auto &k : c->blk) if (k.kind != 0 && k.n > 1) maxnd = std::max(maxnd, (size_t)k.n);
-        if (maxnd * maxnd * K > lim) MW_BAIL(CLRS_ERR_INVALID, "dense block too large for the multi-word kernels");
+        if (maxnd * maxnd * K > lim) return mw_fail(CLRS_ERR_INVALID, "dense block too large for the multi-word kernels");
         c->dense_two = 2 * maxnd * maxnd * K <= lim;        // room for the two buffers of the product form of X^-1 A
         c->sm_dense = (c->dense_two ? 2 : 1) * maxnd * maxnd * K * 8;
         size_t fmax = 0;
@@ -517,404 +349,373 @@ extern "C" int clrs_mw_create_opts(const clrs_sdp_desc *d, int data_limbs, int d
         c->lds_q = qneed <= lim;
         c->sm_q = (c->lds_q ? qneed : 1) * 8;
         c->sm_mid = 2 * (size_t)std::max(N, 1) * K * 8;
-        if (c->sm_fwd > MW_LDS_MAX || c->sm_mid > MW_LDS_MAX) MW_BAIL(CLRS_ERR_INVALID, "cluster too large for the multi-word solve kernels");
+        if (c->sm_fwd > MW_LDS_MAX || c->sm_mid > MW_LDS_MAX) return mw_fail(CLRS_ERR_INVALID, "cluster too large for the multi-word solve kernels");
     }
     MW_DISPATCH(c, {
-        MW_TRY(mw_set_lds(k_mw_potrf_x<KK>, c->sm_x)); MW_TRY(mw_set_lds((k_mw_potrf_x_ride<KK, DD>), c->sm_x)); MW_TRY(mw_set_lds(k_mw_zt<KK, DD>, c->sm_zt)); MW_TRY(mw_set_lds((k_mw_dense_t<KK, DD>), c->sm_dense));
+        MW_RET(mw_set_lds(k_mw_potrf_x<KK>, c->sm_x)); MW_RET(mw_set_lds((k_mw_potrf_x_ride<KK, DD>), c->sm_x)); MW_RET(mw_set_lds(k_mw_zt<KK, DD>, c->sm_zt)); MW_RET(mw_set_lds((k_mw_dense_t<KK, DD>), c->sm_dense));
         // (only what can be launched: Q beyond LDS never rides k_mw_potrf_q, and systems whose dy and three cluster vectors exceed LDS take the
         // row-parallel solve (k_mw_solve_wide) -- sharded, they are refused at the launch, not here)
         constexpr int KC = mw_kc(KK);
         const size_t bw = std::min(c->sm_mid + c->sm_bwd, MW_LDS_MAX);
-        MW_TRY(mw_set_lds(k_mw_factor<KK>, c->sm_factor)); MW_TRY(mw_set_lds(k_mw_potrf_q<KK>, c->lds_q ? std::max(c->sm_q, c->sm_fwd) : c->sm_fwd));
-        MW_TRY(mw_set_lds(k_mw_solve_fwd<KK>, c->sm_fwd)); MW_TRY(mw_set_lds((k_mw_solve_mid<KK, KK>), c->sm_mid)); MW_TRY(mw_set_lds((k_mw_solve_mid<KK, KC>), c->sm_mid));
-        MW_TRY(mw_set_lds((k_mw_solve_bwd<KK, KK, DD, 0>), bw)); MW_TRY(mw_set_lds((k_mw_solve_bwd<KK, KK, DD, 1>), bw)); MW_TRY(mw_set_lds((k_mw_solve_bwd<KK, KK, DD, 2>), bw));
-        MW_TRY(mw_set_lds((k_mw_solve_bwd<KK, KC, DD, 1>), bw)); MW_TRY(mw_set_lds((k_mw_solve_bwd<KK, KC, DD, 2>), bw));
+        MW_RET(mw_set_lds(k_mw_factor<KK>, c->sm_factor)); MW_RET(mw_set_lds(k_mw_potrf_q<KK>, c->lds_q ? std::max(c->sm_q, c->sm_fwd) : c->sm_fwd));
+        MW_RET(mw_set_lds(k_mw_solve_fwd<KK>, c->sm_fwd)); MW_RET(mw_set_lds((k_mw_solve_mid<KK, KK>), c->sm_mid)); MW_RET(mw_set_lds((k_mw_solve_mid<KK, KC>), c->sm_mid));
+        MW_RET(mw_set_lds((k_mw_solve_bwd<KK, KK, DD, 0>), bw)); MW_RET(mw_set_lds((k_mw_solve_bwd<KK, KK, DD, 1>), bw)); MW_RET(mw_set_lds((k_mw_solve_bwd<KK, KK, DD, 2>), bw));
+        MW_RET(mw_set_lds((k_mw_solve_bwd<KK, KC, DD, 1>), bw)); MW_RET(mw_set_lds((k_mw_solve_bwd<KK, KC, DD, 2>), bw));
     });
-    // ---- exact-product path (clrs_mw_exact.hip.h): static slices of V of the eligible blocks ----
-    std::vector<long long> mws_off((size_t)std::max(NB, 1), -1);
-    {
-        const int S = mws_slices(K);
-        std::vector<float> hVs;
-        std::vector<int> hVe, hve_off((size_t)std::max(NB, 1), 0), hsv((size_t)std::max(NB, 1), 0);
-        for (int b = 0; b < NB; b++) {
-            const MwBlk &k = c->blk[b];
-            if (k.kind != 0 || !k.inv || k.n > 32) continue;
-            const int n = k.n, U = k.U, np = (n + 3) & ~3, n16 = (n + 15) & ~15, U16 = (U + 15) & ~15, rV = mws_rowstride(U16);
-            if ((n16 / 16) * (U16 / 16) > 4 || mws_lds_bytes(S, mws_sv_class(S, 1), n, U) > MW_LDS_MAX) continue;
-            if (2 * (n16 / 16) * (U16 / 16) > 4) c->mws_turns = 2;
-            mws_off[b] = (long long)hVs.size();
-            hve_off[b] = (int)hVe.size();
-            hVs.resize(hVs.size() + (size_t)S * np * rV, 0.0f);
-            hVe.resize(hVe.size() + U16, 0);
-            float *dst = hVs.data() + mws_off[b];
-            int sv = 0;
-            for (int u = 0; u < U; u++) {
-                double mx = 0;
-                for (int i = 0; i < n; i++) mx = std::max(mx, std::fabs(hVl[0][k.v_off + (i64)u * n + i]));
-                const int e = mwk::mws_exponent(mx);
-                hVe[hve_off[b] + u] = e;
-                for (int i = 0; i < n; i++) {
-                    mwa::mw<2> x;
-                    x.l[0] = hVl[0][k.v_off + (i64)u * n + i];
-                    x.l[1] = DK > 1 ? hVl[1][k.v_off + (i64)u * n + i] : 0.0;
-                    double r0 = std::ldexp(x.l[0], -e), r1 = std::ldexp(x.l[1], -e);
-                    for (int s = 0; s < S; s++) {
-                        const double g = std::ldexp(1.0, -(s + 1) * MWS_BETA), C = 0x1.8p52 * g;
-                        volatile double tv = r0 + C;               // (no contraction or reassociation of the rounding trick on the host)
-                        const double t = tv - C;
-                        const float dgt = (float)(t * std::ldexp(1.0, (s + 1) * MWS_BETA));
-                        dst[(size_t)s * np * rV + (size_t)i * rV + mws_col(i, u, U16)] = dgt;      // [s][k = row i of V][col = u]
-                        if (dgt != 0.0f) sv = std::max(sv, s + 1);
-                        r0 -= t;
-                        double sm, er;
-                        mwa::two_sum(r0, r1, sm, er);
-                        r0 = sm; r1 = er;
-                    }
-                }
-            }
-            if (mws_lds_bytes(S, mws_sv_class(S, sv), n, U) > MW_LDS_MAX) {      // (the test above assumed the fewest slices of V)
-                hVs.resize((size_t)mws_off[b]); hVe.resize((size_t)hve_off[b]);
-                mws_off[b] = -1;
-                continue;
-            }
-            hsv[b] = sv;
-            c->mws_blocks++;
-            c->sm_mws = std::max(c->sm_mws, mws_lds_bytes(S, mws_sv_class(S, sv), n, U));
+    return 0;
+}
+
+// the static digits of a column of n numbers of V or of a dense matrix: data(l, i) = plane l of entry i; the column's window exponent goes to *e_out,
+// every digit to put(i, s, digit)
+template <class DATA, class PUT>
+static void mw_cut_column(int n, int DK, int S, DATA &&data, int *e_out, PUT &&put) {
+    double mx = 0;
+    for (int i = 0; i < n; i++) mx = std::max(mx, std::fabs(data(0, i)));
+    const int e = *e_out = mwk::mws_exponent(mx);
+    for (int i = 0; i < n; i++)
+        mw_cut_digits(data(0, i), DK > 1 ? data(1, i) : 0.0, e, S, [&](int s, float dgt) { put(i, s, dgt); });
+}
+
+// ---- exact-product path (clrs_mw_exact.hip.h): static slices of V of the eligible blocks; mws_off[b] >= 0: block b goes through k_mws_pair ----
+static int mw_stage_mws(clrs_mw_ctx *c, const MwTables &t, const MwOpts &o, std::vector<long long> &mws_off) {
+    const int K = c->K, DK = c->DK, NB = t.NB;
+    mws_off.assign((size_t)std::max(NB, 1), -1);
+    const int S = mws_slices(K);
+    std::vector<float> hVs;
+    std::vector<int> hVe, hve_off((size_t)std::max(NB, 1), 0), hsv((size_t)std::max(NB, 1), 0);
+    for (int b = 0; b < NB; b++) {
+        const MwBlk &k = c->blk[b];
+        if (k.kind != 0 || !k.inv || k.n > 32) continue;
+        const int n = k.n, U = k.U, np = (n + 3) & ~3, n16 = (n + 15) & ~15, U16 = (U + 15) & ~15, rV = mws_rowstride(U16);
+        if ((n16 / 16) * (U16 / 16) > 4 || mws_lds_bytes(S, mws_sv_class(S, 1), n, U) > MW_LDS_MAX) continue;
+        if (2 * (n16 / 16) * (U16 / 16) > 4) c->mws_turns = 2;
+        mws_off[b] = (long long)hVs.size();
+        hve_off[b] = (int)hVe.size();
+        hVs.resize(hVs.size() + (size_t)S * np * rV, 0.0f);
+        hVe.resize(hVe.size() + U16, 0);
+        float *dst = hVs.data() + mws_off[b];
+        int sv = 0;
+        for (int u = 0; u < U; u++)
+            mw_cut_column(n, DK, S, [&](int l, int i) { return t.V[(size_t)l * t.Vp + k.v_off + (i64)u * n + i]; }, &hVe[hve_off[b] + u], [&](int i, int s, float dgt) {
+                dst[(size_t)s * np * rV + (size_t)i * rV + mws_col(i, u, U16)] = dgt;      // [s][k = row i of V][col = u]
+                if (dgt != 0.0f) sv = std::max(sv, s + 1);
+            });
+        if (mws_lds_bytes(S, mws_sv_class(S, sv), n, U) > MW_LDS_MAX) {      // (the test above assumed the fewest slices of V)
+            hVs.resize((size_t)mws_off[b]); hVe.resize((size_t)hve_off[b]);
+            mws_off[b] = -1;
+            continue;
         }
-        const bool on = cfg_exact == 2 ? c->mws_blocks > 0 : (cfg_exact == 1 && c->mws_blocks >= 256);
-        if (!on) { c->mws_blocks = 0; std::fill(mws_off.begin(), mws_off.end(), -1); }
-        else {
-            MW_TRY(mw_upload(c, hVs, &c->mws.Vs)); MW_TRY(mw_upload(c, hVe, &c->mws.Vexp));
-            MW_TRY(mw_upload(c, hve_off, &c->mws.ve_off)); MW_TRY(mw_upload(c, hsv, &c->mws.sv));
-            MW_DISPATCH(c, { if constexpr (DD <= 2) { MW_TRY(mw_set_lds((k_mws_pair<KK, DD, 1>), c->sm_mws)); MW_TRY(mw_set_lds((k_mws_pair<KK, DD, 2>), c->sm_mws)); } });
-        }
-        MW_TRY(mw_upload(c, mws_off, &c->mws.vs_off));
+        hsv[b] = sv;
+        c->mws_blocks++;
+        c->sm_mws = std::max(c->sm_mws, mws_lds_bytes(S, mws_sv_class(S, sv), n, U));
     }
-    // ---- pairing matrices of blocks of any size through digits in global memory (k_mwx_slice, k_mwx_gram): blocks without sub-blocks that
-    // k_mws_pair does not take and that have enough unique vectors for their U x U Gram products to matter ----
+    const bool on = o.exact == 2 ? c->mws_blocks > 0 : (o.exact == 1 && c->mws_blocks >= 256);
+    if (!on) { c->mws_blocks = 0; std::fill(mws_off.begin(), mws_off.end(), -1); }
+    else {
+        MW_RET(mw_upload(c, hVs, &c->mws.Vs)); MW_RET(mw_upload(c, hVe, &c->mws.Vexp));
+        MW_RET(mw_upload(c, hve_off, &c->mws.ve_off)); MW_RET(mw_upload(c, hsv, &c->mws.sv));
+        MW_DISPATCH(c, { if constexpr (DD <= 2) { MW_RET(mw_set_lds((k_mws_pair<KK, DD, 1>), c->sm_mws)); MW_RET(mw_set_lds((k_mws_pair<KK, DD, 2>), c->sm_mws)); } });
+    }
+    return mw_upload(c, mws_off, &c->mws.vs_off);
+}
+
+// ---- pairing matrices of blocks of any size through digits in global memory (k_mwx_slice, k_mwx_gram): blocks without sub-blocks that
+// k_mws_pair does not take and that have enough unique vectors for their U x U Gram products to matter ----
+static int mw_stage_mwx(clrs_mw_ctx *c, const MwTables &t, const MwOpts &o, const std::vector<long long> &mws_off) {
+    const int K = c->K, DK = c->DK, NB = t.NB;
     std::vector<long long> mwx_off((size_t)std::max(NB, 1), -1);
-    if (cfg_exact != 0) {
-        const int S = mws_slices(K);
-        std::vector<float> hVd;
-        std::vector<int> heV, he_off((size_t)std::max(NB, 1), 0), hsv((size_t)std::max(NB, 1), 0);
-        for (int b = 0; b < NB; b++) {
-            const MwBlk &k = c->blk[b];
-            if (k.kind != 0 || k.m != 1 || mws_off[b] >= 0) continue;
-            if (k.U < (cfg_exact == 2 ? 16 : 64) || k.n < 8) continue;
-            const int n = k.n, U = k.U, np = (n + 3) & ~3, U16 = (U + 15) & ~15;
-            mwx_off[b] = (long long)hVd.size();
-            he_off[b] = (int)heV.size();
-            hVd.resize(hVd.size() + (size_t)S * np * U16, 0.0f);
-            heV.resize(heV.size() + U16, 0);
-            float *dst = hVd.data() + mwx_off[b];
-            int sv = 0;
-            for (int u = 0; u < U; u++) {
-                double mx = 0;
-                for (int i = 0; i < n; i++) mx = std::max(mx, std::fabs(hVl[0][k.v_off + (i64)u * n + i]));
-                const int e = mwk::mws_exponent(mx);
-                heV[he_off[b] + u] = e;
-                for (int i = 0; i < n; i++) {
-                    double r0 = std::ldexp(hVl[0][k.v_off + (i64)u * n + i], -e), r1 = DK > 1 ? std::ldexp(hVl[1][k.v_off + (i64)u * n + i], -e) : 0.0;
-                    for (int s2 = 0; s2 < S; s2++) {
-                        const double g = std::ldexp(1.0, -(s2 + 1) * MWS_BETA), C = 0x1.8p52 * g;
-                        volatile double tv = r0 + C;
-                        const double t = tv - C;
-                        const float dgt = (float)(t * std::ldexp(1.0, (s2 + 1) * MWS_BETA));
-                        dst[(size_t)s2 * np * U16 + (size_t)i * U16 + u] = dgt;
-                        if (dgt != 0.0f) sv = std::max(sv, s2 + 1);
-                        r0 -= t;
-                        double sm, er;
-                        mwa::two_sum(r0, r1, sm, er);
-                        r0 = sm; r1 = er;
-                    }
-                }
-            }
-            hsv[b] = sv;
-            c->mwx_blocks++;
-            c->mwx_maxU16 = std::max(c->mwx_maxU16, U16);
-        }
-        if (c->mwx_blocks > 0) {
-            MW_TRY(mw_upload(c, hVd, &c->mwx.Vd)); MW_TRY(mw_upload(c, heV, &c->mwx.eV));
-            MW_TRY(mw_upload(c, he_off, &c->mwx.e_off)); MW_TRY(mw_upload(c, hsv, &c->mwx.sv));
-            double *zd = nullptr, *td = nullptr, *ez = nullptr, *et = nullptr;      // (the allocator counts doubles)
-            MW_TRY(mw_dmalloc(c, &zd, (i64)(hVd.size() + 1) / 2)); MW_TRY(mw_dmalloc(c, &td, (i64)(hVd.size() + 1) / 2));
-            MW_TRY(mw_dmalloc(c, &ez, (i64)(heV.size() + 1) / 2)); MW_TRY(mw_dmalloc(c, &et, (i64)(heV.size() + 1) / 2));
-            c->mwx.Zd = (float *)zd; c->mwx.Td = (float *)td; c->mwx.eZ = (int *)ez; c->mwx.eT = (int *)et;
-            MWCHECK(hipMemset(zd, 0, hVd.size() * sizeof(float))); MWCHECK(hipMemset(td, 0, hVd.size() * sizeof(float)));      // the padding rows and columns stay zero
-            MWCHECK(hipMemset(ez, 0, heV.size() * sizeof(int))); MWCHECK(hipMemset(et, 0, heV.size() * sizeof(int)));
-        }
-        MW_TRY(mw_upload(c, mwx_off, &c->mwx.d_off));
-    } else {
-        MW_TRY(mw_upload(c, mwx_off, &c->mwx.d_off));
+    if (o.exact == 0) return mw_upload(c, mwx_off, &c->mwx.d_off);
+    const int S = mws_slices(K);
+    std::vector<float> hVd;
+    std::vector<int> heV, he_off((size_t)std::max(NB, 1), 0), hsv((size_t)std::max(NB, 1), 0);
+    for (int b = 0; b < NB; b++) {
+        const MwBlk &k = c->blk[b];
+        if (k.kind != 0 || k.m != 1 || mws_off[b] >= 0) continue;
+        if (k.U < (o.exact == 2 ? 16 : 64) || k.n < 8) continue;
+        const int n = k.n, U = k.U, np = (n + 3) & ~3, U16 = (U + 15) & ~15;
+        mwx_off[b] = (long long)hVd.size();
+        he_off[b] = (int)heV.size();
+        hVd.resize(hVd.size() + (size_t)S * np * U16, 0.0f);
+        heV.resize(heV.size() + U16, 0);
+        float *dst = hVd.data() + mwx_off[b];
+        int sv = 0;
+        for (int u = 0; u < U; u++)
+            mw_cut_column(n, DK, S, [&](int l, int i) { return t.V[(size_t)l * t.Vp + k.v_off + (i64)u * n + i]; }, &heV[he_off[b] + u], [&](int i, int s, float dgt) {
+                dst[(size_t)s * np * U16 + (size_t)i * U16 + u] = dgt;
+                if (dgt != 0.0f) sv = std::max(sv, s + 1);
+            });
+        hsv[b] = sv;
+        c->mwx_blocks++;
+        c->mwx_maxU16 = std::max(c->mwx_maxU16, U16);
     }
-    // ---- dense blocks with 16 < n <= 32 and inverse factors: X^-1 (A_e Y) through exact slice products (k_mwx_dense), static digits of the A_e ----
+    if (c->mwx_blocks > 0) {
+        MW_RET(mw_upload(c, hVd, &c->mwx.Vd)); MW_RET(mw_upload(c, heV, &c->mwx.eV));
+        MW_RET(mw_upload(c, he_off, &c->mwx.e_off)); MW_RET(mw_upload(c, hsv, &c->mwx.sv));
+        double *zd = nullptr, *td = nullptr, *ez = nullptr, *et = nullptr;      // (the allocator counts doubles)
+        MW_RET(mw_dmalloc(c, &zd, (i64)(hVd.size() + 1) / 2)); MW_RET(mw_dmalloc(c, &td, (i64)(hVd.size() + 1) / 2));
+        MW_RET(mw_dmalloc(c, &ez, (i64)(heV.size() + 1) / 2)); MW_RET(mw_dmalloc(c, &et, (i64)(heV.size() + 1) / 2));
+        c->mwx.Zd = (float *)zd; c->mwx.Td = (float *)td; c->mwx.eZ = (int *)ez; c->mwx.eT = (int *)et;
+        MW_RET(mw_hip(hipMemset(zd, 0, hVd.size() * sizeof(float)), "hipMemset")); MW_RET(mw_hip(hipMemset(td, 0, hVd.size() * sizeof(float)), "hipMemset"));      // the padding rows and columns stay zero
+        MW_RET(mw_hip(hipMemset(ez, 0, heV.size() * sizeof(int)), "hipMemset")); MW_RET(mw_hip(hipMemset(et, 0, heV.size() * sizeof(int)), "hipMemset"));
+    }
+    return mw_upload(c, mwx_off, &c->mwx.d_off);
+}
+
+// ---- dense blocks with 16 < n <= 32 and inverse factors: X^-1 (A_e Y) through exact slice products (k_mwx_dense), static digits of the A_e ----
+static int mw_stage_mwd(clrs_mw_ctx *c, const MwTables &t, const MwOpts &o) {
+    const int K = c->K, DK = c->DK, NB = t.NB;
     std::vector<long long> mwd_off((size_t)std::max(NB, 1), -1);
-    if (cfg_exact != 0 && K <= 6) {
-        const int S = mws_slices(K), S1 = (S + 1) / 2, sN = 32 * 32;
-        std::vector<float> hAd;
-        std::vector<int> heA, he_off((size_t)std::max(NB, 1), 0);
-        for (int b = 0; b < NB; b++) {
-            const MwBlk &k = c->blk[b];
-            if (k.kind == 0 || !k.inv || k.n <= 16 || k.n > 32 || k.cnt <= 0) continue;
-            const int n = k.n;
-            const size_t base = hAd.size(), ebase = heA.size();
-            hAd.resize(base + (size_t)k.cnt * S1 * sN, 0.0f);
-            heA.resize(ebase + (size_t)k.cnt * 32, 0);
-            bool fits = true;
-            for (int e = 0; e < k.cnt && fits; e++) {
-                float *dst = hAd.data() + base + (size_t)e * S1 * sN;
-                const i64 a0 = k.a_off + (i64)e * n * n;
-                for (int col = 0; col < n; col++) {
-                    double mx = 0;
-                    for (int kk = 0; kk < n; kk++) mx = std::max(mx, std::fabs(hdAl[0][a0 + kk + (i64)col * n]));
-                    const int ex = mwk::mws_exponent(mx);
-                    heA[ebase + (size_t)e * 32 + col] = ex;
-                    for (int kk = 0; kk < n; kk++) {
-                        double r0 = std::ldexp(hdAl[0][a0 + kk + (i64)col * n], -ex), r1 = DK > 1 ? std::ldexp(hdAl[1][a0 + kk + (i64)col * n], -ex) : 0.0;
-                        for (int s2 = 0; s2 < S; s2++) {
-                            const double g = std::ldexp(1.0, -(s2 + 1) * MWS_BETA), C = 0x1.8p52 * g;
-                            volatile double tv = r0 + C;
-                            const double t = tv - C;
-                            const float dgt = (float)(t * std::ldexp(1.0, (s2 + 1) * MWS_BETA));
-                            if (s2 < S1) dst[(size_t)s2 * sN + (size_t)kk * 32 + mws_col(kk, col, 32)] = dgt;
-                            else if (dgt != 0.0f) fits = false;      // data beyond the slices kept: leave the block to the expansion kernels
-                            r0 -= t;
-                            double sm, er;
-                            mwa::two_sum(r0, r1, sm, er);
-                            r0 = sm; r1 = er;
-                        }
-                    }
-                }
-            }
-            if (!fits) { hAd.resize(base); heA.resize(ebase); continue; }
-            mwd_off[b] = (long long)base;
-            he_off[b] = (int)ebase;
-            c->mwd_blocks++;
+    if (o.exact == 0 || K > 6) return mw_upload(c, mwd_off, &c->mwd.a_off);
+    const int S = mws_slices(K), S1 = (S + 1) / 2, sN = 32 * 32;
+    std::vector<float> hAd;
+    std::vector<int> heA, he_off((size_t)std::max(NB, 1), 0);
+    for (int b = 0; b < NB; b++) {
+        const MwBlk &k = c->blk[b];
+        if (k.kind == 0 || !k.inv || k.n <= 16 || k.n > 32 || k.cnt <= 0) continue;
+        const int n = k.n;
+        const size_t base = hAd.size(), ebase = heA.size();
+        hAd.resize(base + (size_t)k.cnt * S1 * sN, 0.0f);
+        heA.resize(ebase + (size_t)k.cnt * 32, 0);
+        bool fits = true;
+        for (int e = 0; e < k.cnt && fits; e++) {
+            float *dst = hAd.data() + base + (size_t)e * S1 * sN;
+            const i64 a0 = k.a_off + (i64)e * n * n;
+            for (int col = 0; col < n; col++)
+                mw_cut_column(n, DK, S, [&](int l, int kk) { return t.dA[(size_t)l * t.dAp + a0 + kk + (i64)col * n]; }, &heA[ebase + (size_t)e * 32 + col], [&](int kk, int s, float dgt) {
+                    if (s < S1) dst[(size_t)s * sN + (size_t)kk * 32 + mws_col(kk, col, 32)] = dgt;
+                    else if (dgt != 0.0f) fits = false;      // data beyond the slices kept: leave the block to the expansion kernels
+                });
         }
-        if (c->mwd_blocks > 0) {
-            std::vector<int> tasks;
-            for (size_t di = 0; di < dn_list.size(); di++) {
-                const int b = dn_list[di];
-                if (mwd_off[b] < 0) continue;
-                for (int e = 0; e < c->blk[b].cnt; e++) { tasks.push_back((int)di); tasks.push_back(e); }
-            }
-            c->mwd_tasks = (int)tasks.size() / 2;
-            MW_TRY(mw_upload(c, tasks, &c->mwd.tasks));
-            MW_TRY(mw_upload(c, hAd, &c->mwd.Ad)); MW_TRY(mw_upload(c, heA, &c->mwd.eA)); MW_TRY(mw_upload(c, he_off, &c->mwd.e_off));
-            c->sm_mwd = (size_t)2 * S * sN * sizeof(float) + 128 * sizeof(int);
-            MW_DISPATCH(c, { if constexpr (DD <= 2) { MW_TRY(mw_set_lds((k_mwx_dense<KK, DD>), c->sm_mwd)); } });
-        }
+        if (!fits) { hAd.resize(base); heA.resize(ebase); continue; }
+        mwd_off[b] = (long long)base;
+        he_off[b] = (int)ebase;
+        c->mwd_blocks++;
     }
-    MW_TRY(mw_upload(c, mwd_off, &c->mwd.a_off));
-    // ---- upload ----
+    if (c->mwd_blocks > 0) {
+        std::vector<int> tasks;
+        for (size_t di = 0; di < t.dn_list.size(); di++) {
+            const int b = t.dn_list[di];
+            if (mwd_off[b] < 0) continue;
+            for (int e = 0; e < c->blk[b].cnt; e++) { tasks.push_back((int)di); tasks.push_back(e); }
+        }
+        c->mwd_tasks = (int)tasks.size() / 2;
+        MW_RET(mw_upload(c, tasks, &c->mwd.tasks));
+        MW_RET(mw_upload(c, hAd, &c->mwd.Ad)); MW_RET(mw_upload(c, heA, &c->mwd.eA)); MW_RET(mw_upload(c, he_off, &c->mwd.e_off));
+        c->sm_mwd = (size_t)2 * S * sN * sizeof(float) + 128 * sizeof(int);
+        MW_DISPATCH(c, { if constexpr (DD <= 2) { MW_RET(mw_set_lds((k_mwx_dense<KK, DD>), c->sm_mwd)); } });
+    }
+    return mw_upload(c, mwd_off, &c->mwd.a_off);
+}
+
+// ---- upload: the tables of mw_build_tables behind the pointers of MwDev ----
+static int mw_stage_upload(clrs_mw_ctx *c, const MwTables &t) {
     MwDev &q = c->d;
     q.mws_off = c->mws.vs_off; q.mws_on = c->mws_blocks > 0 ? 1 : 0;
     q.mwx_off = c->mwx.d_off; q.mwx_on = c->mwx_blocks > 0 ? 1 : 0;
     q.mwd_off = c->mwd.a_off; q.mwd_on = 0;            // (switched on per assembly: the kernel needs the inverse factors of this context's chol X)
-    q.J = J; q.N = N; q.NB = NB; q.nlr = (int)lr_list.size(); q.ndn = (int)dn_list.size();
-    q.xylen = xyoff; q.xlen = xlen; q.Slen = Slen; q.T = T; q.xrdlen = rdoff;
-    q.zlen = std::max<i64>(zoff, 1); q.glen = std::max<i64>(goff, 1); q.wlen = std::max<i64>(woff, 1); q.sdlen = std::max<i64>(sdoff, 1);
-    std::vector<int> hdense_p(d->dense_p, d->dense_p + D);
-    // B arrives per cluster (P_j x N column-major, concatenated); the kernels read one stacked xlen x N matrix
-    const i64 Bp = xlen * (i64)N;
-    std::vector<double> hBs((size_t)std::max<i64>(Bp, 1) * DK, 0.0);
-    for (int l = 0; l < DK; l++) {
-        i64 off = 0;
-        for (int j = 0; j < J; j++) {
-            const int P = c->clu[j].P;
-            for (int a = 0; a < N; a++)
-                for (int r = 0; r < P; r++) hBs[(size_t)l * std::max<i64>(Bp, 1) + c->clu[j].coff + r + (i64)a * xlen] = d->B[(i64)l * Bp + off + r + (i64)a * P];
-            off += (i64)P * N;
-        }
-    }
-    q.Vp = std::max<i64>((i64)hVl[0].size(), 1); q.dAp = std::max<i64>((i64)hdAl[0].size(), 1); q.lamp = std::max<i64>(T, 1); q.Bp = std::max<i64>(Bp, 1);
-    hV.assign((size_t)q.Vp * DK, 0.0);
-    hdA.assign((size_t)q.dAp * DK, 0.0);
-    for (int l = 0; l < DK; l++) {
-        std::copy(hVl[l].begin(), hVl[l].end(), hV.begin() + (size_t)l * q.Vp);
-        std::copy(hdAl[l].begin(), hdAl[l].end(), hdA.begin() + (size_t)l * q.dAp);
-    }
-    MW_TRY(mw_upload(c, c->blk, &q.blk)); MW_TRY(mw_upload(c, c->clu, &q.clu));
-    MW_TRY(mw_upload(c, lr_list, &q.lr_list)); MW_TRY(mw_upload(c, dn_list, &q.dn_list));
-    MW_TRY(mw_upload(c, hV, &q.V)); MW_TRY(mw_upload(c, hvrow, &q.vrow));
-    MW_TRY(mw_upload(c, st_a, &q.st_a)); MW_TRY(mw_upload(c, st_b, &q.st_b)); MW_TRY(mw_upload(c, st_lam, &q.st_lam));
-    MW_TRY(mw_upload(c, htptr, &q.tptr));
-    MW_TRY(mw_upload(c, st_orig, &q.st_orig)); MW_TRY(mw_upload(c, st_p, &q.st_p)); MW_TRY(mw_upload(c, st_war, &q.st_war)); MW_TRY(mw_upload(c, st_wac, &q.st_wac));
-    MW_TRY(mw_upload(c, st_trl, &q.st_trl)); MW_TRY(mw_upload(c, st_trd, &q.st_trd)); MW_TRY(mw_upload(c, st_flag, &q.st_flag));
-    MW_TRY(mw_upload(c, ay_a, &q.ay_a)); MW_TRY(mw_upload(c, ay_b, &q.ay_b)); MW_TRY(mw_upload(c, ay_blk, &q.ay_blk));
-    MW_TRY(mw_upload(c, hdA, &q.dA)); MW_TRY(mw_upload(c, hdmap, &q.dmap)); MW_TRY(mw_upload(c, hdense_p, &q.dense_p));
-    {
-        std::sort(drow_pairs.begin(), drow_pairs.end());
-        std::vector<int> hptr((size_t)xlen + 1, 0), hblk, hen;
-        for (auto &t : drow_pairs) hptr[(size_t)std::get<0>(t) + 1]++;
-        for (i64 g = 0; g < xlen; g++) hptr[(size_t)g + 1] += hptr[(size_t)g];
-        for (auto &t : drow_pairs) { hblk.push_back(std::get<1>(t)); hen.push_back(std::get<2>(t)); }
-        MW_TRY(mw_upload(c, hptr, &q.drow_ptr)); MW_TRY(mw_upload(c, hblk, &q.drow_blk)); MW_TRY(mw_upload(c, hen, &q.drow_en));
-        q.dn_big = 0;
-        for (auto &k : c->blk) if (k.kind != 0) { c->maxcnt = std::max(c->maxcnt, k.cnt); if (k.n > 1) q.dn_big = 1; }
-        q.maxcnt = c->maxcnt;
-    }
-    MW_TRY(mw_upload(c, hBs, &q.B));
-    MW_TRY(mw_dmalloc(c, &q.Z, q.zlen * K)); MW_TRY(mw_dmalloc(c, &q.Tm, q.zlen * K));
-    MW_TRY(mw_dmalloc(c, &q.GX, q.glen * K)); MW_TRY(mw_dmalloc(c, &q.GY, q.glen * K));
-    MW_TRY(mw_dmalloc(c, &q.W, q.wlen * K)); MW_TRY(mw_dmalloc(c, &q.Sd, q.sdlen * K));
-    MW_TRY(mw_dmalloc(c, &q.S, Slen * K)); MW_TRY(mw_dmalloc(c, &q.LB, xlen * (i64)N * K)); MW_TRY(mw_dmalloc(c, &q.Q, (i64)N * N * K));
-    MW_TRY(mw_dmalloc(c, &q.Si, Slen * K)); MW_TRY(mw_dmalloc(c, &q.Qi, (i64)N * N * K));
+    q.J = t.J; q.N = t.N; q.NB = t.NB; q.nlr = (int)t.lr_list.size(); q.ndn = (int)t.dn_list.size();
+    q.xylen = t.xylen; q.xlen = t.xlen; q.Slen = t.Slen; q.T = t.T; q.xrdlen = t.xrdlen;
+    q.zlen = std::max<i64>(t.zlen, 1); q.glen = std::max<i64>(t.glen, 1); q.wlen = std::max<i64>(t.wlen, 1); q.sdlen = std::max<i64>(t.sdlen, 1);
+    q.Vp = t.Vp; q.dAp = t.dAp; q.lamp = t.lamp; q.Bp = t.Bp;
+    MW_RET(mw_upload(c, c->blk, &q.blk)); MW_RET(mw_upload(c, c->clu, &q.clu));
+    MW_RET(mw_upload(c, t.lr_list, &q.lr_list)); MW_RET(mw_upload(c, t.dn_list, &q.dn_list));
+    MW_RET(mw_upload(c, t.V, &q.V)); MW_RET(mw_upload(c, t.vrow, &q.vrow));
+    MW_RET(mw_upload(c, t.st_a, &q.st_a)); MW_RET(mw_upload(c, t.st_b, &q.st_b)); MW_RET(mw_upload(c, t.st_lam, &q.st_lam));
+    MW_RET(mw_upload(c, t.tptr, &q.tptr));
+    MW_RET(mw_upload(c, t.st_orig, &q.st_orig)); MW_RET(mw_upload(c, t.st_p, &q.st_p)); MW_RET(mw_upload(c, t.st_war, &q.st_war)); MW_RET(mw_upload(c, t.st_wac, &q.st_wac));
+    MW_RET(mw_upload(c, t.st_trl, &q.st_trl)); MW_RET(mw_upload(c, t.st_trd, &q.st_trd)); MW_RET(mw_upload(c, t.st_flag, &q.st_flag));
+    MW_RET(mw_upload(c, t.ay_a, &q.ay_a)); MW_RET(mw_upload(c, t.ay_b, &q.ay_b)); MW_RET(mw_upload(c, t.ay_blk, &q.ay_blk));
+    MW_RET(mw_upload(c, t.dA, &q.dA)); MW_RET(mw_upload(c, t.dmap, &q.dmap)); MW_RET(mw_upload(c, t.dense_p, &q.dense_p));
+    MW_RET(mw_upload(c, t.drow_ptr, &q.drow_ptr)); MW_RET(mw_upload(c, t.drow_blk, &q.drow_blk)); MW_RET(mw_upload(c, t.drow_en, &q.drow_en));
+    q.dn_big = t.dn_big;
+    q.maxcnt = c->maxcnt;
+    return mw_upload(c, t.B, &q.B);
+}
 
-    MW_TRY(mw_dmalloc(c, &q.Xf, xyoff * K)); MW_TRY(mw_dmalloc(c, &q.Xb, xyoff * K)); MW_TRY(mw_dmalloc(c, &q.Xi, xyoff * K));
-    MW_TRY(mw_dmalloc(c, &q.xrd, rdoff * K)); MW_TRY(mw_dmalloc(c, &q.srd, xlen * K)); MW_TRY(mw_dmalloc(c, &q.qrd, (i64)N * K));
-    MW_TRY(mw_dmalloc(c, &q.t, xlen * K)); MW_TRY(mw_dmalloc(c, &q.u, (i64)J * N * K)); MW_TRY(mw_dmalloc(c, &q.AY, T * K));
+static int mw_stage_buffers(clrs_mw_ctx *c) {
+    MwDev &q = c->d;
+    const int K = c->K, J = q.J, N = q.N;
+    const i64 xlen = q.xlen, Slen = q.Slen, xyoff = q.xylen, rdoff = q.xrdlen, T = q.T;
+    MW_RET(mw_dmalloc(c, &q.Z, q.zlen * K)); MW_RET(mw_dmalloc(c, &q.Tm, q.zlen * K));
+    MW_RET(mw_dmalloc(c, &q.GX, q.glen * K)); MW_RET(mw_dmalloc(c, &q.GY, q.glen * K));
+    MW_RET(mw_dmalloc(c, &q.W, q.wlen * K)); MW_RET(mw_dmalloc(c, &q.Sd, q.sdlen * K));
+    MW_RET(mw_dmalloc(c, &q.S, Slen * K)); MW_RET(mw_dmalloc(c, &q.LB, xlen * (i64)N * K)); MW_RET(mw_dmalloc(c, &q.Q, (i64)N * N * K));
+    MW_RET(mw_dmalloc(c, &q.Si, Slen * K)); MW_RET(mw_dmalloc(c, &q.Qi, (i64)N * N * K));
+
+    MW_RET(mw_dmalloc(c, &q.Xf, xyoff * K)); MW_RET(mw_dmalloc(c, &q.Xb, xyoff * K)); MW_RET(mw_dmalloc(c, &q.Xi, xyoff * K));
+    MW_RET(mw_dmalloc(c, &q.xrd, rdoff * K)); MW_RET(mw_dmalloc(c, &q.srd, xlen * K)); MW_RET(mw_dmalloc(c, &q.qrd, (i64)N * K));
+    MW_RET(mw_dmalloc(c, &q.t, xlen * K)); MW_RET(mw_dmalloc(c, &q.u, (i64)J * N * K)); MW_RET(mw_dmalloc(c, &q.AY, T * K));
     q.AX = nullptr;                      // (the interior-point iteration asks for it: clrs_mw_ipm_create)
     q.aff_mu = q.aff_rhs = q.aff_t = q.aff_u = nullptr; q.aff_wait = nullptr; q.ride2_rhs = nullptr; q.ride2_t = q.ride2_u = nullptr;
-    MW_TRY(mw_dmalloc(c, &c->vz, 2 * (i64)N * K));
-    MW_TRY(mw_dmalloc(c, &q.S0, Slen * K)); MW_TRY(mw_dmalloc(c, &q.ub, (i64)J * N * K));
-    MW_TRY(mw_dmalloc(c, &q.rx2, xlen * K)); MW_TRY(mw_dmalloc(c, &q.dx2, xlen * K));
-    MW_TRY(mw_dmalloc(c, &q.u2, (i64)N * K)); MW_TRY(mw_dmalloc(c, &q.dy2, (i64)N * K));
+    MW_RET(mw_dmalloc(c, &c->vz, 2 * (i64)N * K));
+    MW_RET(mw_dmalloc(c, &q.S0, Slen * K)); MW_RET(mw_dmalloc(c, &q.ub, (i64)J * N * K));
+    MW_RET(mw_dmalloc(c, &q.rx2, xlen * K)); MW_RET(mw_dmalloc(c, &q.dx2, xlen * K));
+    MW_RET(mw_dmalloc(c, &q.u2, (i64)N * K)); MW_RET(mw_dmalloc(c, &q.dy2, (i64)N * K));
     q.uadd = nullptr;
-    c->refine = cfg_refine;
-    c->refine_predictor = cfg_refine_pred;
+    MW_RET(mw_dmalloc(c, &c->d_Xin, xyoff * K)); MW_RET(mw_dmalloc(c, &c->d_Xc, xyoff * K)); MW_RET(mw_dmalloc(c, &c->d_Y, xyoff * K));
+    MW_RET(mw_dmalloc(c, &c->d_rx, xlen * K)); MW_RET(mw_dmalloc(c, &c->d_dx, xlen * K));
+    MW_RET(mw_dmalloc(c, &c->d_ry, (i64)N * K)); MW_RET(mw_dmalloc(c, &c->d_dy, (i64)N * K));
+    int *info = nullptr;
+    MW_RET(mw_hip(hipMalloc((void **)&info, 2 * sizeof(int)), "hipMalloc"));
+    c->allocs.push_back(info);
+    q.info = info;
+    int init[2] = {MW_INFO_NONE, MW_INFO_NONE};
+    MW_RET(mw_hip(hipMemcpy(info, init, sizeof(init), hipMemcpyHostToDevice), "hipMemcpy"));
+    return mw_alloc_fill(c, &q.pcnt, (size_t)(2 * J + 3), 0);
+}
+
+// matrices of the blocked path (k_mw_bp_*): the clusters beyond LDS, and Q
+static int mw_stage_blocked(clrs_mw_ctx *c) {
+    MwDev &q = c->d;
+    const int K = c->K, J = q.J, N = q.N;
+    for (int j = 0; j < J; j++) {
+        const MwClu &cl = c->clu[j];
+        if (cl.lds) { c->any_lds_cluster = true; continue; }
+        c->bp_S.push_back(MwBp{q.S + cl.Soff, q.Si + cl.Soff, q.srd + cl.coff, q.Slen, q.xlen, cl.P, cl.P, j + 1, 0, (int)c->bp_S.size(), 0});
+    }
+    if (N > 0) c->bp_Q.push_back(MwBp{q.Q, q.Qi, q.qrd, (i64)N * N, (i64)N, N, N, J + 1, 0, (int)c->bp_S.size(), 0});
+    std::vector<MwBp> all = c->bp_S;
+    all.insert(all.end(), c->bp_Q.begin(), c->bp_Q.end());
+    MW_RET(mw_upload(c, all, &c->d_bp));
+    const int MW_PB = MW_PB_OF(K);
+    c->sm_bp_diag = ((size_t)MW_POTRF_SCR(K, MW_PB) + (size_t)K * MW_PB * MW_PB + (size_t)K * MW_TRI(MW_PB) + (size_t)K * MW_PB) * 8;
+    c->sm_bp_panel = (size_t)K * MW_BP_PR * MW_PB * 8;
+    c->sm_bp_inv = (size_t)K * MW_PB * MW_BP_IC * 8;
+    MW_DISPATCH(c, { MW_RET(mw_set_lds(k_mw_bp_diag<KK>, std::max(c->sm_bp_diag, c->sm_factor))); MW_RET(mw_set_lds(k_mw_bp_panel<KK>, c->sm_bp_panel)); MW_RET(mw_set_lds(k_mw_bp_inv<KK>, c->sm_bp_inv)); MW_RET(mw_set_lds(k_mw_bp_inv_row<KK>, c->sm_bp_inv)); });
+    return 0;
+}
+
+// pipelined factorisations (clrs_mw_pipe.hip.h): matrices of at most 32 rows, while stages + W workgroups of every matrix can be resident side by side
+static int mw_stage_pipelines(clrs_mw_ctx *c, const MwOpts &o) {
+    MwDev &q = c->d;
+    const int K = c->K, J = q.J, N = q.N, cfg_pipe = o.pipe;
+    bool small = c->maxP <= MWP_N;
+    for (auto &cl : c->clu) small = small && cl.lds;
+    c->pipe_S = cfg_pipe != 0 && (K <= 6 || cfg_pipe >= 2) && small && (i64)J * ((MWP_N / MWP_W) + MWP_WW) <= 256;      // (8, 10 limbs: measured slower than one workgroup, 2.42 against 2.34 ms per iteration: opt-in)
+    // (Q: with the columns asked for four steps ahead the pipeline was slower than the one-workgroup kernel on the named problem, 83 against 80 us; with
+    // MWP_AHEAD = 0 it is faster -- whole iterations 0.4197 -> 0.4165 ms on cohnelkies(8,15), 0.4113 -> 0.4057 on delsarte(3,10,1/2): on from two stages,
+    // and with pipeline = 2 for every Q of at most MWP_N rows)
+    c->pipe_Q = (cfg_pipe >= 2 || (cfg_pipe == 1 && K <= 6 && N > MWP_W)) && N > 0 && N <= MWP_N;
+    bool lds_all = !c->clu.empty();
+    for (auto &cl : c->clu) lds_all = lds_all && cl.lds;
+    // (measured at 5 limbs, factor stage in 4: PolyOpt 2d = 40, P = 41 -- six stages, five hops -- 0.478 -> 0.487 ms per iteration; the tested three-point instance,
+    // P = 50, 0.648 -> 0.638: by default from 48 rows on, with pipeline = 2 for every cluster of 33 .. 64 rows)
+    c->pipe_S64 = cfg_pipe != 0 && K <= 6 && lds_all && c->maxP > MWP_N && c->maxP <= MWP_N64 && (i64)J * 16 <= 256 && g_cfg_mw_pipeline64 != 0 &&
+                  (cfg_pipe >= 2 || c->maxP >= 48);
+    // the diagonal blocks of the blocked factorisation (k_mw_bp_diag_pipe): the same pipeline per 32-column block of every matrix beyond LDS
+    const size_t nbp = c->bp_S.size() + c->bp_Q.size();
+    const bool any_bp = !c->bp_S.empty() || (N > 0 && !c->lds_q);
+    // (at every limb count: 8 and 10 limbs gain 2-4 % per iteration as well -- scripts/blocked_pipe_limbs.py -- unlike the clusters that fit in LDS)
+    c->pipe_bp = cfg_pipe != 0 && any_bp && (i64)std::max<size_t>(c->bp_S.size(), 1) * ((MWP_N / MWP_W) + MWP_WW) <= 256;
+    q.pipe_pc = nullptr;
+    q.pipe_stamps = nullptr;
+    q.pipe_bp = 0;
+    {   // the Cholesky of the X blocks through the pipelines: every block carries its inverse factor in LDS form (inv == 1) and has at most 64 rows
+        // (measured at 5 limbs, whole iterations: blocks of 32 and 48 rows -- Nsphere_packing N = 2 1.146 -> 1.122 ms, N = 3 2.059 -> 2.027; blocks of at most 21 rows:
+        // nothing either way; 64 blocks of 32 rows -- 2 x 64 x 8 working workgroups for 256 compute units -- 1.69 -> 1.87: by default from 24 rows of the largest
+        // block on and while every working workgroup of the launch has a compute unit of its own)
+        bool all_inv = c->d.NB > 0 && c->lds_x;
+        int maxn_x = 0;
+        i64 working = 0;
+        for (auto &kb : c->blk) {
+            all_inv = all_inv && kb.inv == 1;
+            maxn_x = std::max(maxn_x, kb.n);
+            working += 2 * ((kb.n + MWP_W - 1) / MWP_W + (kb.n > MWP_N ? MWP_N64 / MWP_W : MWP_WW));
+        }
+        // no reader of the scaled triangles Xf / Xb in such a context (k_mw_zt and k_mw_dense_t take the products with Xi, k_mwi_Z is not launched, k_mwi_step
+        // takes an inverse-factor path: clrs_mw_ipm_create_ex clears this where it would not) unless a dense block of more than one row substitutes for want of
+        // LDS; callers' own factors (k_mw_xrd) come with triangles of their own
+        q.no_xfb = (all_inv && (!q.dn_big || c->dense_two) && g_cfg_mw_skip_xfb != 0) ? 1 : 0;
+        c->pipe_X = cfg_pipe != 0 && K <= 6 && all_inv && maxn_x <= MWP_N64 && g_cfg_mw_pipeline_x != 0 &&
+                    (cfg_pipe >= 2 || (maxn_x >= g_cfg_mw_pipeline_x_min && working <= 256));
+        if (c->pipe_X) {
+            double *pcx = nullptr, *ti = nullptr;
+            MW_RET(mw_dmalloc(c, &pcx, (i64)2 * c->d.NB * MWP_PC_WORDS_N(K, MWP_N64)));
+            c->pipe_pcx = (unsigned long long *)pcx;
+            MW_RET(mw_dmalloc(c, &c->xpipe_L, c->d.xylen * K));
+            MW_RET(mw_dmalloc(c, &c->xpipe_rd, c->d.xrdlen * K));
+            MW_RET(mw_dmalloc(c, &ti, c->d.NB + 1));
+            c->xpipe_info = (int *)ti;
+            MW_DISPATCH(c, { if constexpr (KK <= 6) { MW_RET(mw_set_lds(k_mw_potrf_x_pipe<KK>, MWP_LDS_ALONE64)); } });
+        }
+    }
+    if (c->pipe_S64) {                                    // (its own hand-off region: 64-row columns; no other pipeline runs in such a context's factor stage but Q's / the blocked path's below)
+        MW_RET(mw_alloc_fill(c, &c->pipe_pc64, (size_t)J * MWP_PC_WORDS_N(K, MWP_N64), 0xff));
+        MW_DISPATCH(c, { if constexpr (KK <= 6) { MW_RET(mw_set_lds(k_mw_factor_pipe64<KK>, MWP_LDS_ALONE64)); } });
+    }
+    if (c->pipe_S || c->pipe_Q || c->pipe_bp) {
+        const size_t own = (size_t)(c->pipe_S ? J : 0) + 1;
+        MW_RET(mw_alloc_fill(c, &q.pipe_pc, (own + (c->pipe_bp ? nbp : 0)) * MWP_PC_WORDS(K), 0xff));      // no launch epoch has this tag
+        c->pipe_pcQ = c->pipe_S ? J : 0;
+        q.pipe_q = c->pipe_pcQ;
+        q.pipe_bp = (int)own;
+        MW_DISPATCH(c, {
+            MW_RET(mw_set_lds(k_mw_factor_pipe<KK>, MWP_LDS_ALONE));
+            MW_RET(mw_set_lds(k_mw_potrf_q_pipe<KK>, std::max<size_t>(MWP_LDS_ALONE, c->sm_fwd)));
+            MW_RET(mw_set_lds(k_mw_bp_diag_pipe<KK>, std::max<size_t>(MWP_LDS_ALONE, c->sm_factor)));
+        });
+    }
+    return 0;
+}
+
+// factor stage and solve products in fewer limbs, residuals and iterate in K (mw_kf_of): the LDS-resident paths with the full-limb refinement step
+static int mw_stage_reduced_limbs(clrs_mw_ctx *c, const MwOpts &o) {
+    MwDev &q = c->d;
+    const int K = c->K, N = q.N;
+    q.rank = 0; q.world = 1; q.gathered = 0;      // (the gather slots of a sharded context, allocated at this point of the sequence)
+    MW_RET(mw_dmalloc(c, &q.Qg, (i64)N * N * K)); MW_RET(mw_dmalloc(c, &q.ug, (i64)N * K));
+    const bool may = mw_kf_of(K) < K && c->refine == 1;      // (every factorisation and solve path carries the reduced form: LDS-resident, pipelined, blocked, row-parallel)
+    c->kf_low = may ? mw_kf_of(K) : K;
+    if (o.factor_limbs != 0 && o.factor_limbs != K && o.factor_limbs != c->kf_low) return mw_fail(CLRS_ERR_INVALID, "factor_limbs: 0 (automatic), the context's limbs, or the reduced count of this limb count where the LDS-resident refined solve runs");
+    if (o.factor_limbs == K) c->kf_low = K;
+    c->kf_entry = o.factor_limbs == 0 ? K : o.factor_limbs;
+    q.kf = c->kf_entry;
+    q.km = o.km;
+    return mw_alloc_fill(c, &q.refstat, 4, 0);
+}
+
+extern "C" int clrs_mw_create_opts(const clrs_sdp_desc *d, int data_limbs, int device, int limbs, const clrs_mw_options *opts, clrs_mw_ctx **out) {
+    if (!d || !out) return mw_fail(CLRS_ERR_INVALID, "null argument");
+    MwOpts o;
+    MW_RET(mw_resolve_opts(opts, limbs, data_limbs, o));
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device >= ndev) return mw_fail(CLRS_ERR_NO_DEVICE, "no usable HIP device");
+    MW_RET(mw_hip(hipSetDevice(device), "hipSetDevice(device)"));
+    if (d->n_clusters <= 0 || d->n_free < 0 || d->n_blocks < 0) return mw_fail(CLRS_ERR_INVALID, "bad sizes");      // (before the stream, as ever; mw_build_tables says the same)
+    std::unique_ptr<clrs_mw_ctx, void (*)(clrs_mw_ctx *)> guard(new clrs_mw_ctx(), clrs_mw_destroy);      // the one cleanup path of every failure below
+    clrs_mw_ctx *c = guard.get();
+    c->device = device;
+    c->K = limbs;
+    c->DK = data_limbs;
+    c->refine = o.refine;
+    c->refine_predictor = o.refine_pred;
     {
         const char *e = std::getenv("CLRS_MW_STREAM_WORDS");
         c->stream_words = e && *e ? std::atoi(e) != 0 : g_cfg_mw_stream_words != 0;
         c->chain_hop = std::min(std::max(g_cfg_mw_chain_hop, 0), 2);
         c->y_riders = g_cfg_mw_y_riders != 0;
     }
-    c->wide_solve = c->maxP > 64 || N > 64;
-    MW_TRY(mw_dmalloc(c, &c->d_Xin, xyoff * K)); MW_TRY(mw_dmalloc(c, &c->d_Xc, xyoff * K)); MW_TRY(mw_dmalloc(c, &c->d_Y, xyoff * K));
-    MW_TRY(mw_dmalloc(c, &c->d_rx, xlen * K)); MW_TRY(mw_dmalloc(c, &c->d_dx, xlen * K));
-    MW_TRY(mw_dmalloc(c, &c->d_ry, (i64)N * K)); MW_TRY(mw_dmalloc(c, &c->d_dy, (i64)N * K));
-    {
-        int *info = nullptr;
-        MWCHECK(hipMalloc((void **)&info, 2 * sizeof(int)));
-        c->allocs.push_back(info);
-        q.info = info;
-        int init[2] = {MW_INFO_NONE, MW_INFO_NONE};
-        MWCHECK(hipMemcpy(info, init, sizeof(init), hipMemcpyHostToDevice));
-        int *pc = nullptr;
-        MWCHECK(hipMalloc((void **)&pc, (size_t)(2 * J + 3) * sizeof(int)));
-        c->allocs.push_back(pc);
-        MWCHECK(hipMemset(pc, 0, (size_t)(2 * J + 3) * sizeof(int)));
-        q.pcnt = pc;
-    }
-    {   // matrices of the blocked path (k_mw_bp_*)
-        for (int j = 0; j < J; j++) {
-            const MwClu &cl = c->clu[j];
-            if (cl.lds) { c->any_lds_cluster = true; continue; }
-            c->bp_S.push_back(MwBp{q.S + cl.Soff, q.Si + cl.Soff, q.srd + cl.coff, q.Slen, q.xlen, cl.P, cl.P, j + 1, 0, (int)c->bp_S.size(), 0});
-        }
-        if (N > 0) c->bp_Q.push_back(MwBp{q.Q, q.Qi, q.qrd, (i64)N * N, (i64)N, N, N, J + 1, 0, (int)c->bp_S.size(), 0});
-        std::vector<MwBp> all = c->bp_S;
-        all.insert(all.end(), c->bp_Q.begin(), c->bp_Q.end());
-        MW_TRY(mw_upload(c, all, &c->d_bp));
-    }
-    {   // pipelined factorisations (clrs_mw_pipe.hip.h): matrices of at most 32 rows, while stages + W workgroups of every matrix can be resident side by side
-        bool small = c->maxP <= MWP_N;
-        for (auto &cl : c->clu) small = small && cl.lds;
-        c->pipe_S = cfg_pipe != 0 && (K <= 6 || cfg_pipe >= 2) && small && (i64)J * ((MWP_N / MWP_W) + MWP_WW) <= 256;      // (8, 10 limbs: measured slower than one workgroup, 2.42 against 2.34 ms per iteration: opt-in)
-        // (Q: with the columns asked for four steps ahead the pipeline was slower than the one-workgroup kernel on the named problem, 83 against 80 us; with
-        // MWP_AHEAD = 0 it is faster -- whole iterations 0.4197 -> 0.4165 ms on cohnelkies(8,15), 0.4113 -> 0.4057 on delsarte(3,10,1/2): on from two stages,
-        // and with pipeline = 2 for every Q of at most MWP_N rows)
-        c->pipe_Q = (cfg_pipe >= 2 || (cfg_pipe == 1 && K <= 6 && N > MWP_W)) && N > 0 && N <= MWP_N;
-        bool lds_all = !c->clu.empty();
-        for (auto &cl : c->clu) lds_all = lds_all && cl.lds;
-        // (measured at 5 limbs, factor stage in 4: PolyOpt 2d = 40, P = 41 -- six stages, five hops -- 0.478 -> 0.487 ms per iteration; the tested three-point instance,
-        // P = 50, 0.648 -> 0.638: by default from 48 rows on, with pipeline = 2 for every cluster of 33 .. 64 rows)
-        c->pipe_S64 = cfg_pipe != 0 && K <= 6 && lds_all && c->maxP > MWP_N && c->maxP <= MWP_N64 && (i64)J * 16 <= 256 && g_cfg_mw_pipeline64 != 0 &&
-                      (cfg_pipe >= 2 || c->maxP >= 48);
-        // the diagonal blocks of the blocked factorisation (k_mw_bp_diag_pipe): the same pipeline per 32-column block of every matrix beyond LDS
-        const size_t nbp = c->bp_S.size() + c->bp_Q.size();
-        const bool any_bp = !c->bp_S.empty() || (N > 0 && !c->lds_q);
-        // (at every limb count: 8 and 10 limbs gain 2-4 % per iteration as well -- scripts/blocked_pipe_limbs.py -- unlike the clusters that fit in LDS)
-        c->pipe_bp = cfg_pipe != 0 && any_bp && (i64)std::max<size_t>(c->bp_S.size(), 1) * ((MWP_N / MWP_W) + MWP_WW) <= 256;
-        q.pipe_pc = nullptr;
-        q.pipe_stamps = nullptr;
-        q.pipe_bp = 0;
-        {   // the Cholesky of the X blocks through the pipelines: every block carries its inverse factor in LDS form (inv == 1) and has at most 64 rows
-            // (measured at 5 limbs, whole iterations: blocks of 32 and 48 rows -- Nsphere_packing N = 2 1.146 -> 1.122 ms, N = 3 2.059 -> 2.027; blocks of at most 21 rows:
-            // nothing either way; 64 blocks of 32 rows -- 2 x 64 x 8 working workgroups for 256 compute units -- 1.69 -> 1.87: by default from 24 rows of the largest
-            // block on and while every working workgroup of the launch has a compute unit of its own)
-            bool all_inv = c->d.NB > 0 && c->lds_x;
-            int maxn_x = 0;
-            i64 working = 0;
-            for (auto &kb : c->blk) {
-                all_inv = all_inv && kb.inv == 1;
-                maxn_x = std::max(maxn_x, kb.n);
-                working += 2 * ((kb.n + MWP_W - 1) / MWP_W + (kb.n > MWP_N ? MWP_N64 / MWP_W : MWP_WW));
-            }
-            // no reader of the scaled triangles Xf / Xb in such a context (k_mw_zt and k_mw_dense_t take the products with Xi, k_mwi_Z is not launched, k_mwi_step
-            // takes an inverse-factor path: clrs_mw_ipm_create_ex clears this where it would not) unless a dense block of more than one row substitutes for want of
-            // LDS; callers' own factors (k_mw_xrd) come with triangles of their own
-            q.no_xfb = (all_inv && (!q.dn_big || c->dense_two) && g_cfg_mw_skip_xfb != 0) ? 1 : 0;
-            c->pipe_X = cfg_pipe != 0 && K <= 6 && all_inv && maxn_x <= MWP_N64 && g_cfg_mw_pipeline_x != 0 &&
-                        (cfg_pipe >= 2 || (maxn_x >= g_cfg_mw_pipeline_x_min && working <= 256));
-            if (c->pipe_X) {
-                double *pcx = nullptr, *ti = nullptr;
-                MW_TRY(mw_dmalloc(c, &pcx, (i64)2 * c->d.NB * MWP_PC_WORDS_N(K, MWP_N64)));
-                c->pipe_pcx = (unsigned long long *)pcx;
-                MW_TRY(mw_dmalloc(c, &c->xpipe_L, c->d.xylen * K));
-                MW_TRY(mw_dmalloc(c, &c->xpipe_rd, c->d.xrdlen * K));
-                MW_TRY(mw_dmalloc(c, &ti, c->d.NB + 1));
-                c->xpipe_info = (int *)ti;
-                MW_DISPATCH(c, { if constexpr (KK <= 6) { MW_TRY(mw_set_lds(k_mw_potrf_x_pipe<KK>, MWP_LDS_ALONE64)); } });
-            }
-        }
-        if (c->pipe_S64) {                                    // (its own hand-off region: 64-row columns; no other pipeline runs in such a context's factor stage but Q's / the blocked path's below)
-            const size_t words64 = (size_t)J * MWP_PC_WORDS_N(K, MWP_N64);
-            unsigned long long *pc64 = nullptr;
-            if (hipMalloc((void **)&pc64, words64 * sizeof(unsigned long long)) != hipSuccess) MW_BAIL(CLRS_ERR_HIP, "hipMalloc failed");
-            c->allocs.push_back(pc64);
-            if (hipMemset(pc64, 0xff, words64 * sizeof(unsigned long long)) != hipSuccess) MW_BAIL(CLRS_ERR_HIP, "hipMemset failed");
-            c->pipe_pc64 = pc64;
-            MW_DISPATCH(c, { if constexpr (KK <= 6) { MW_TRY(mw_set_lds(k_mw_factor_pipe64<KK>, MWP_LDS_ALONE64)); } });
-        }
-        if (c->pipe_S || c->pipe_Q || c->pipe_bp) {
-            const size_t own = (size_t)(c->pipe_S ? J : 0) + 1;
-            const size_t words = (own + (c->pipe_bp ? nbp : 0)) * MWP_PC_WORDS(K);
-            unsigned long long *pc = nullptr;
-            if (hipMalloc((void **)&pc, words * sizeof(unsigned long long)) != hipSuccess) MW_BAIL(CLRS_ERR_HIP, "hipMalloc failed");
-            c->allocs.push_back(pc);
-            if (hipMemset(pc, 0xff, words * sizeof(unsigned long long)) != hipSuccess) MW_BAIL(CLRS_ERR_HIP, "hipMemset failed");      // no launch epoch has this tag
-            q.pipe_pc = pc;
-            c->pipe_pcQ = c->pipe_S ? J : 0;
-            q.pipe_q = c->pipe_pcQ;
-            q.pipe_bp = (int)own;
-            MW_DISPATCH(c, {
-                MW_TRY(mw_set_lds(k_mw_factor_pipe<KK>, MWP_LDS_ALONE));
-                MW_TRY(mw_set_lds(k_mw_potrf_q_pipe<KK>, std::max<size_t>(MWP_LDS_ALONE, c->sm_fwd)));
-                MW_TRY(mw_set_lds(k_mw_bp_diag_pipe<KK>, std::max<size_t>(MWP_LDS_ALONE, c->sm_factor)));
-            });
-        }
-    }
-    const int MW_PB = MW_PB_OF(K);
-    c->sm_bp_diag = ((size_t)MW_POTRF_SCR(K, MW_PB) + (size_t)K * MW_PB * MW_PB + (size_t)K * MW_TRI(MW_PB) + (size_t)K * MW_PB) * 8;
-    c->sm_bp_panel = (size_t)K * MW_BP_PR * MW_PB * 8;
-    c->sm_bp_inv = (size_t)K * MW_PB * MW_BP_IC * 8;
-    MW_DISPATCH(c, { MW_TRY(mw_set_lds(k_mw_bp_diag<KK>, std::max(c->sm_bp_diag, c->sm_factor))); MW_TRY(mw_set_lds(k_mw_bp_panel<KK>, c->sm_bp_panel)); MW_TRY(mw_set_lds(k_mw_bp_inv<KK>, c->sm_bp_inv)); MW_TRY(mw_set_lds(k_mw_bp_inv_row<KK>, c->sm_bp_inv)); });
-    q.rank = 0; q.world = 1; q.gathered = 0;
-    MW_TRY(mw_dmalloc(c, &q.Qg, (i64)N * N * K)); MW_TRY(mw_dmalloc(c, &q.ug, (i64)N * K));
-    {   // factor stage and solve products in fewer limbs, residuals and iterate in K (mw_kf_of): the LDS-resident paths with the full-limb refinement step
-        bool all_lds = true;
-        for (auto &cl : c->clu) all_lds = all_lds && cl.lds;
-        (void)all_lds;
-        const bool may = mw_kf_of(K) < K && c->refine == 1;      // (every factorisation and solve path carries the reduced form: LDS-resident, pipelined, blocked, row-parallel)
-        c->kf_low = may ? mw_kf_of(K) : K;
-        if (cfg_factor_limbs != 0 && cfg_factor_limbs != K && cfg_factor_limbs != c->kf_low) MW_BAIL(CLRS_ERR_INVALID, "factor_limbs: 0 (automatic), the context's limbs, or the reduced count of this limb count where the LDS-resident refined solve runs");
-        if (cfg_factor_limbs == K) c->kf_low = K;
-        c->kf_entry = cfg_factor_limbs == 0 ? K : cfg_factor_limbs;
-        q.kf = c->kf_entry;
-        q.km = cfg_km;
-        unsigned long long *rs = nullptr;
-        if (hipMalloc((void **)&rs, 4 * sizeof(unsigned long long)) != hipSuccess) MW_BAIL(CLRS_ERR_HIP, "hipMalloc failed");
-        c->allocs.push_back(rs);
-        if (hipMemset(rs, 0, 4 * sizeof(unsigned long long)) != hipSuccess) MW_BAIL(CLRS_ERR_HIP, "hipMemset failed");
-        q.refstat = rs;
-    }
-    for (auto &e : c->ev) MWCHECK(hipEventCreate(&e));
-    *out = c;
+    MW_RET(mw_stage_stream(c));
+    MwTables t;
+    std::string err;
+    if (mw_build_tables(d, data_limbs, t, err)) return mw_fail(CLRS_ERR_INVALID, err);
+    mw_adopt_tables(c, t);
+    MW_RET(mw_stage_lds(c, t));
+    std::vector<long long> mws_off;
+    MW_RET(mw_stage_mws(c, t, o, mws_off));
+    MW_RET(mw_stage_mwx(c, t, o, mws_off));
+    MW_RET(mw_stage_mwd(c, t, o));
+    MW_RET(mw_stage_upload(c, t));
+    MW_RET(mw_stage_buffers(c));
+    MW_RET(mw_stage_blocked(c));
+    MW_RET(mw_stage_pipelines(c, o));
+    MW_RET(mw_stage_reduced_limbs(c, o));
+    for (auto &e : c->ev) MW_RET(mw_hip(hipEventCreate(&e), "hipEventCreate(&e)"));
+    *out = guard.release();
     return 0;
-#undef MW_BAIL
-#undef MW_TRY
 }
+#undef MW_RET
 
 extern "C" void clrs_mw_destroy(clrs_mw_ctx *c) {
     if (!c) return;

@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "clrs_mw_arith.h"
+#include "clrs_mw_types.h"      // mwi64, MwBlk, MwClu: shared with the host-only table builder
 
 // Template parameters: K = limbs of every computed number, DK = limbs of the problem data (sampled vectors, lambda, dense
 // A_p, B; the reference holds them at `prec` bits too, src/interface.jl:1078-1112).  DK = 1 is plain fp64 data.
@@ -32,30 +33,6 @@
 #define MW_WAIT_TICKS 3000000000ull  // 30 s of wall_clock64 (100 MHz): a bound against hangs only -- a long wait (a large instance, a GPU shared with other work) is not a failure
 #define MW_INV_WG 4          // workgroups that share the columns of an inverse factor (k_mw_factor, k_mw_potrf_q, k_mw_bp_diag)
 
-typedef long long mwi64;
-
-struct MwBlk {               // one PSD block (j, l)
-    int j, n, kind, delta, U, cnt, P, inv;   // chol(X_b)^-1 is formed beside the factor (Xi): 1 = in LDS, 2 = in place in memory (the block fits in LDS once, not twice), 0 = not
-    mwi64 xyoff;             // offset in the xy layout
-    mwi64 rd_off;            // offset of its reciprocal Cholesky diagonal in xrd (sum of n over earlier blocks)
-    mwi64 v_off;             // low rank: V, n x U column-major fp64 (expanded unique vectors)
-    mwi64 vrow_off;          // low rank: first nonzero row of each unique vector [U]
-    mwi64 z_off;             // Z / T scratch, n x U
-    mwi64 g_off;             // GX / GY scratch, U x U
-    mwi64 tptr_off;          // CSR over the cluster's constraints into the sorted term arrays [P+1]
-    mwi64 a_off;             // dense: stack of A_e, cnt matrices n x n fp64
-    mwi64 sd_off;            // dense: contribution table cnt x cnt
-    mwi64 w_off;             // dense: T_e = X^-1 A_e Y, cnt matrices n x n
-    mwi64 dmap_off;          // dense: constraint -> entry (or -1) [P]
-    mwi64 d0;                // dense: first entry in dense_p
-    mwi64 t0;                // low rank: first term (sorted arrays and original order share the range)
-    int m, pad2;
-};
-struct MwClu {               // one cluster j
-    int P, b0, b1, lds;      // constraints; block range; 1 = S_j and the inverse of its factor fit in LDS side by side (k_mw_factor), 0 = blocked path
-    mwi64 coff, Soff;
-    int one_term, pad;       // 1 = at most four PSD blocks and at most one low-rank term per (constraint, block): S_j by k_mw_saccum_one
-};
 // Limbs of the FACTOR stage and of the products of the solve stage when the context runs them in fewer limbs than its K (MwDev::kf < K; clrs_mw_options.factor_limbs):
 // mixed-precision iterative refinement.  L_j, L_j^-1, L^-1 B, Q, L_Q, L_Q^-1 and both passes of inverse-factor products carry mw_kf_of(K) limbs (their upper
 // planes are stored as zeros, so that every K-limb reader stays valid), the residuals r_x = rhs_x - S dx + B dy, r_y = rhs_y - B^T dx of the refinement step
