@@ -25,6 +25,7 @@
 #include "clrs_mw_ipm.hip.h"
 #include "clrs_mw_rank.hip.h"
 #include "clrs_mw_gemm.hip.h"
+#include "clrs_mw_kernel_vectors.hip.h"
 #include "clrs_mw_inst.h"
 #include "clrs_mw_tables.h"      // host only: mw_build_tables, mw_cut_digits
 #ifdef MW_SPLIT_UNITS        // the kernels of these limb counts are compiled in units of their own (clrs_mw_inst.hip)
@@ -1721,6 +1722,97 @@ extern "C" int clrs_mw_gemm(int device, int limbs, int njobs, const clrs_mw_gemm
                 memcpy(C + o, back.data() + o, (size_t)q.m * sizeof(double));
             }
     }
+    return 0;
+}
+
+// ---- kernel vectors of solution blocks (clrs_mw_kernel_vectors.hip.h): no context, host pointers, the buffers of one call released on every path ----
+extern "C" int clrs_mw_kernel_vectors(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual,
+                                      double dual_max, int32_t *branch, int32_t *perm, int32_t *rank, int32_t *count, double *V, double *resid_max, double *v_max,
+                                      double *pivot_resid) {
+    if (limbs != 4 && limbs != 5 && limbs != 6 && limbs != 8 && limbs != 10) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: limbs must be 4, 5, 6, 8 or 10");
+    if (nblk < 0 || plane < 0) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: negative block count or plane length");
+    if (!(tau > 0.0)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: tau must be positive");
+    if (nblk > 0 && (!n || !X || !Y || !branch || !perm || !rank || !count || !V || !resid_max || !v_max || !pivot_resid)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: null argument");
+    std::vector<MwRankMat> mats(nblk);
+    std::vector<MwKvBlk> blks(nblk);
+    i64 glen = 0, xlen = 0;
+    for (int b = 0; b < nblk; b++) {
+        if (n[b] < 0) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: negative size");
+        mats[b] = MwRankMat{n[b], n[b], 0, 0, glen, xlen, tau};
+        blks[b] = MwKvBlk{n[b], MW_KV_PRIMAL, 0, 0, glen, xlen};
+        glen += (i64)n[b] * n[b];
+        xlen += n[b];
+    }
+    if (glen > plane) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: the blocks leave their plane");
+    if (nblk == 0) return 0;
+    // the branch of every block from limb plane 0, and the matrices to eliminate: X_b (dual) or Y_b (primal), copies -- Y is needed again for the residual
+    const size_t pool = (size_t)plane * limbs, xb = (size_t)xlen * limbs;
+    std::vector<double> G(pool);
+    for (int b = 0; b < nblk; b++) {
+        const i64 nn = (i64)n[b] * n[b], off = blks[b].off;
+        bool dual = use_dual != 0;
+        for (i64 e = 0; dual && e < nn; e++) dual = fabs(X[off + e]) <= dual_max;
+        blks[b].branch = branch[b] = dual ? MW_KV_DUAL : MW_KV_PRIMAL;
+        for (int l = 0; l < limbs; l++) memcpy(G.data() + (i64)l * plane + off, (dual ? X : Y) + (i64)l * plane + off, (size_t)nn * sizeof(double));
+    }
+    MWCHECK(hipSetDevice(device));
+    MwRankBufs bufs;
+    double *d_G = nullptr, *d_Wk = nullptr, *d_W = nullptr, *d_Y = nullptr, *d_V = nullptr, *d_resid = nullptr, *d_rmax = nullptr, *d_vmax = nullptr;
+    int *d_perm = nullptr, *d_rank = nullptr, *d_tiles = nullptr;
+    MwKvBlk *d_blks = nullptr;
+    MwGemmJob *d_jobs = nullptr;
+    MWCHECK(bufs.get(&d_G, pool)); MWCHECK(bufs.get(&d_Wk, pool)); MWCHECK(bufs.get(&d_W, pool)); MWCHECK(bufs.get(&d_Y, pool)); MWCHECK(bufs.get(&d_V, pool));
+    MWCHECK(bufs.get(&d_resid, xb)); MWCHECK(bufs.get(&d_rmax, (size_t)xlen)); MWCHECK(bufs.get(&d_vmax, (size_t)xlen));
+    MWCHECK(bufs.get(&d_perm, (size_t)xlen)); MWCHECK(bufs.get(&d_rank, (size_t)nblk)); MWCHECK(bufs.get(&d_blks, (size_t)nblk));
+    MWCHECK(hipMemcpy(d_G, G.data(), pool * sizeof(double), hipMemcpyHostToDevice));
+    MWCHECK(hipMemcpy(d_Y, Y, pool * sizeof(double), hipMemcpyHostToDevice));
+    MWCHECK(hipMemcpy(d_V, V, pool * sizeof(double), hipMemcpyHostToDevice));        // entries outside n_b x count_b come back as they went
+    MWCHECK(hipMemset(d_W, 0, std::max<size_t>(pool, 1) * sizeof(double)));
+    MWCHECK(hipMemset(d_resid, 0, std::max<size_t>(xb, 1) * sizeof(double)));
+    MWCHECK(hipMemset(d_rmax, 0, std::max<size_t>(xlen, 1) * sizeof(double)));
+    MWCHECK(hipMemset(d_vmax, 0, std::max<size_t>(xlen, 1) * sizeof(double)));
+    // ONE elimination launch over all blocks (it returns synchronised)
+    int rc = mw_rank_launch(limbs, nullptr, mats, d_G, d_Wk, plane, d_W, d_perm, d_rank, d_resid, xlen);
+    if (rc) return rc;
+    MWCHECK(hipMemcpy(rank, d_rank, (size_t)nblk * sizeof(int), hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(perm, d_perm, (size_t)xlen * sizeof(int), hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(pivot_resid, d_resid, xb * sizeof(double), hipMemcpyDeviceToHost));
+    // the product R_b = Y_b V_b of every block that has vectors: jobs and tiles as clrs_mw_gemm builds them; R goes where the eliminated copies were
+    double *d_R = d_G;
+    std::vector<MwGemmJob> jobs;
+    std::vector<int> tiles;
+    for (int b = 0; b < nblk; b++) {
+        const int nb = n[b], r = rank[b];
+        if (r < 0 || r > nb) return mw_fail(CLRS_ERR_HIP, "kernel vectors: the elimination returned a rank outside 0 .. n");
+        blks[b].rank = r;
+        blks[b].count = count[b] = blks[b].branch == MW_KV_DUAL ? r : nb - r;
+        if (count[b] == 0) continue;
+        const int t = (int)jobs.size();
+        jobs.push_back(MwGemmJob{nb, count[b], nb, 0, 0, 1, 0, nb, nb, nb, blks[b].off, blks[b].off, blks[b].off});
+        for (int tj = 0; tj < (count[b] + MW_GEMM_T - 1) / MW_GEMM_T; tj++)
+            for (int ti = 0; ti < (nb + MW_GEMM_T - 1) / MW_GEMM_T; ti++) { tiles.push_back(t); tiles.push_back(ti); tiles.push_back(tj); }
+    }
+    MWCHECK(bufs.get(&d_jobs, jobs.size())); MWCHECK(bufs.get(&d_tiles, tiles.size()));
+    MWCHECK(hipMemcpy(d_blks, blks.data(), (size_t)nblk * sizeof(MwKvBlk), hipMemcpyHostToDevice));
+    if (!jobs.empty()) {
+        MWCHECK(hipMemcpy(d_jobs, jobs.data(), jobs.size() * sizeof(MwGemmJob), hipMemcpyHostToDevice));
+        MWCHECK(hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice));
+        const unsigned grid = (unsigned)(tiles.size() / 3);
+#define MW_KV_CASE(Kc)                                                                                                                                            \
+    case Kc:                                                                                                                                                      \
+        hipLaunchKernelGGL(k_mw_kv_scatter<Kc>, dim3((unsigned)nblk), dim3(MW_NT), 0, nullptr, d_blks, d_perm, d_W, d_V, (mwi64)plane);                            \
+        hipLaunchKernelGGL(k_mw_gemm<Kc>, dim3(grid), dim3(MW_NT), MW_GEMM_LDS(Kc), nullptr, d_jobs, d_tiles, d_Y, (mwi64)plane, d_V, (mwi64)plane, d_R,          \
+                           (mwi64)plane);                                                                                                                         \
+        break;
+        switch (limbs) { MW_KV_CASE(4) MW_KV_CASE(5) MW_KV_CASE(6) MW_KV_CASE(8) MW_KV_CASE(10) }
+#undef MW_KV_CASE
+        hipLaunchKernelGGL(k_mw_kv_colmax, dim3((unsigned)nblk), dim3(MW_NT), 0, nullptr, d_blks, d_R, d_V, d_rmax, d_vmax);
+        MWCHECK(hipGetLastError());
+        MWCHECK(hipStreamSynchronize(nullptr));
+        MWCHECK(hipMemcpy(V, d_V, pool * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    MWCHECK(hipMemcpy(resid_max, d_rmax, (size_t)xlen * sizeof(double), hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(v_max, d_vmax, (size_t)xlen * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -1,0 +1,150 @@
+"""Step 1 of the reference's `exact_solution` (src/rounding.jl:1366): "Finding the kernel" (RoundingSettings, src/rounding.jl:4-10;
+detecteigenvectors, src/rounding.jl:575-642) at the working precision, on the device (clrs_mw_kernel_vectors).
+
+At an optimum X_b Y_b = 0 for every PSD block: the row space of the dual block X_b is the kernel of the primal block Y_b.  The reference takes the
+reduced row-echelon form of a column-pivoted QR of X_b; for a symmetric PSD block that form is [I W] over the pivots of the diagonally pivoted
+elimination the preprocessing already uses (`mw.rank_reveal`).  Where the reference takes an SVD of Y_b instead (kernel_use_dual = false, or X_b too
+large to be trusted), Y_b itself is eliminated and the relations of its dependent columns are the kernel: the same subspace, in echelon form over
+other pivot columns.  Everything after this step (rounding the entries to a field, LLL, the exact solve) is exact arithmetic and stays with the caller.
+"""
+from __future__ import annotations
+
+import dataclasses
+from typing import List, Optional
+
+import numpy as np
+
+from . import _lib
+
+__all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vectors", "kernel_vectors_batch", "vectors_to_mp"]
+
+WRONG_VECTOR_MESSAGE = "wrong vector detected"
+LIMBS = (4, 5, 6, 8, 10)
+
+
+@dataclasses.dataclass
+class RoundingSettings:
+    """The kernel fields of the reference's RoundingSettings (src/rounding.jl:4-10, 60-62) with its defaults."""
+    kernel_errbound: float = 1e-10          # pivots / residuals below this are zero
+    kernel_round_errbound: float = 1e-15    # the dual block is used while max |X_b| <= 1 / sqrt(this)
+    kernel_use_dual: bool = True
+
+
+class KernelVectorError(ValueError):
+    """A kernel vector failed the reference's checks (src/rounding.jl:608, 620, 636)."""
+
+
+@dataclasses.dataclass
+class BlockKernel:
+    """The kernel vectors of one block.  `branch`: "dual" (X_b eliminated) or "primal" (Y_b eliminated); `rank`: of the eliminated matrix; `count`: vectors
+    (dual: rank, primal: n - rank); `perm`: pivots in pivot order, then the rest; `vectors`: planar (limbs, n, count), one vector per column, original
+    index order; `resid_max` / `v_max`: per vector max_i |head (Y_b v)_i| and max_i |head v_i|; `pivot_resid`: planar (limbs, n - rank), the remaining
+    diagonal of the eliminated matrix."""
+    branch: str
+    rank: int
+    count: int
+    perm: np.ndarray
+    vectors: np.ndarray
+    resid_max: np.ndarray
+    v_max: np.ndarray
+    pivot_resid: np.ndarray
+
+
+def kernel_vectors_batch(block_n, X, Y, limbs: int, tau: float, use_dual: bool, dual_max: float, device: int = 0, V=None):
+    """One call of clrs_mw_kernel_vectors: X, Y planar (limbs, sum n_b^2) in the xy layout.  Returns a list of `BlockKernel`.  `V` (planar, the same shape)
+    is the pool the vectors are written into; what the vectors do not cover stays as passed in (V is modified in place)."""
+    n = np.ascontiguousarray(block_n, np.int32).reshape(-1)
+    nb = n.size
+    off = np.concatenate([[0], np.cumsum(n.astype(np.int64) ** 2)])
+    xoff = np.concatenate([[0], np.cumsum(n.astype(np.int64))])
+    limbs, plane, xlen = int(limbs), int(off[-1]), int(xoff[-1])
+    X, Y = (np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64) for a in (X, Y))
+    if X.shape != (limbs, plane) or Y.shape != (limbs, plane):
+        raise ValueError(f"kernel_vectors_batch: X and Y must be planar ({limbs}, {plane}), got {X.shape} and {Y.shape}")
+    if V is None:
+        V = np.zeros((limbs, plane))
+    if V.shape != (limbs, plane) or V.dtype != np.float64 or not V.flags.c_contiguous:
+        raise ValueError(f"kernel_vectors_batch: V must be a contiguous float64 array of shape ({limbs}, {plane})")
+    pad = lambda a: a if a.size else np.zeros((limbs, 1))           # (a valid pointer for an empty pool)
+    branch, rank, count = (np.zeros(max(nb, 1), np.int32) for _ in range(3))
+    perm = np.zeros(max(xlen, 1), np.int32)
+    rmax, vmax, piv = np.zeros(max(xlen, 1)), np.zeros(max(xlen, 1)), np.zeros((limbs, max(xlen, 1)))
+    Xp, Yp, Vp = pad(X), pad(Y), pad(V)
+    p_i = lambda a: a.ctypes.data_as(_lib.p_i32)
+    p_d = lambda a: a.ctypes.data_as(_lib.p_d)
+    _lib.check(_lib.load().clrs_mw_kernel_vectors(int(device), limbs, nb, p_i(n), p_d(Xp), p_d(Yp), plane, float(tau), int(bool(use_dual)), float(dual_max),
+                                                  p_i(branch), p_i(perm), p_i(rank), p_i(count), p_d(Vp), p_d(rmax), p_d(vmax), p_d(piv)))
+    out = []
+    for b in range(nb):
+        nn, r, c = int(n[b]), int(rank[b]), int(count[b])
+        vec = np.ascontiguousarray(np.transpose(V[:, off[b]:off[b] + nn * c].reshape(limbs, c, nn), (0, 2, 1)))
+        out.append(BlockKernel("dual" if branch[b] else "primal", r, c, perm[xoff[b]:xoff[b + 1]].copy(), vec, rmax[xoff[b]:xoff[b] + c].copy(),
+                               vmax[xoff[b]:xoff[b] + c].copy(), piv[:, xoff[b]:xoff[b] + nn - r].copy()))
+    return out
+
+
+def _planes(a, limbs, length, what):
+    """fp64 (length,) or planar (planes, length) -> planar (limbs, length), zero padded or cut, as the warm start of solvesdp_mw does"""
+    a = np.asarray(a, dtype=np.float64)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    if a.ndim != 2 or a.shape[1] != length:
+        raise ValueError(f"kernel_vectors: {what} must hold {length} numbers per limb plane, got {a.shape}")
+    out = np.zeros((limbs, length))
+    out[:min(limbs, a.shape[0])] = a[:limbs]
+    return out
+
+
+def kernel_vectors(sdp_or_block_n, dualsol, primalsol=None, limbs: Optional[int] = None, settings: Optional[RoundingSettings] = None, device: int = 0,
+                   check_dimensions: bool = False, batch=None) -> List[BlockKernel]:
+    """The kernel vectors of every PSD block of a solution: `dualsol.X` are the dual blocks, `primalsol.Y` the primal blocks (a `SolveResult` of
+    `solvesdp_mw`, or anything with those attributes, fp64 or planar limbs; `primalsol=None`: both from `dualsol`).  `sdp_or_block_n`: the problem (a
+    `ClusteredLowRankSDP` or `FlatSDP`) or the block sizes in block order.  `limbs`: 4, 5, 6, 8 or 10 (default: the planes of the solution, 5 for fp64).
+    Raises `KernelVectorError` ("wrong vector detected") when max |Y_b v| of some vector is not below `settings.kernel_errbound`
+    (src/rounding.jl:608, 631-638) and, with `check_dimensions`, when the rank found on X_b plus the rank found on Y_b is not n_b (src/rounding.jl:611-621;
+    a second elimination, of the matrix the first did not take).  `batch`: the device call (default `kernel_vectors_batch`)."""
+    settings = RoundingSettings() if settings is None else settings
+    batch = kernel_vectors_batch if batch is None else batch
+    if hasattr(sdp_or_block_n, "block_n"):
+        block_n = sdp_or_block_n.block_n
+    elif hasattr(sdp_or_block_n, "blocks"):
+        from .sdp import flatten
+        block_n = flatten(sdp_or_block_n).block_n
+    else:
+        block_n = sdp_or_block_n
+    block_n = np.ascontiguousarray(block_n, np.int32).reshape(-1)
+    primalsol = dualsol if primalsol is None else primalsol
+    if limbs is None:
+        planes = max(np.asarray(a).shape[0] if np.asarray(a).ndim == 2 else 1 for a in (dualsol.X, primalsol.Y))
+        limbs = 5 if planes == 1 else planes
+    limbs = int(limbs)
+    if limbs not in LIMBS:
+        raise ValueError(f"kernel_vectors: limbs must be one of {LIMBS}, got {limbs}")
+    if not settings.kernel_errbound > 0 or not settings.kernel_round_errbound > 0:
+        raise ValueError("kernel_vectors: kernel_errbound and kernel_round_errbound must be positive")
+    off = np.concatenate([[0], np.cumsum(block_n.astype(np.int64) ** 2)])
+    X, Y = _planes(dualsol.X, limbs, int(off[-1]), "X"), _planes(primalsol.Y, limbs, int(off[-1]), "Y")
+    tau, dual_max = float(settings.kernel_errbound), 1.0 / float(np.sqrt(settings.kernel_round_errbound))
+    out = batch(block_n, X, Y, limbs, tau, bool(settings.kernel_use_dual), dual_max, device=device)
+    for b, k in enumerate(out):
+        bad = [v for v in range(k.count) if not k.resid_max[v] < tau]
+        if bad:
+            raise KernelVectorError(f"{WRONG_VECTOR_MESSAGE}: block {b}, vector {bad[0]} ({k.branch} branch): max |Y v| = {float(k.resid_max[bad[0]]):.3e} "
+                                    f"is not below kernel_errbound = {tau:.3e} (max |v| = {float(k.v_max[bad[0]]):.3e})")
+    if check_dimensions:
+        other = Y.copy()                                     # the matrix the first elimination did not take: Y_b after the dual branch, X_b after the primal
+        for b, k in enumerate(out):
+            if k.branch == "primal":
+                other[:, off[b]:off[b + 1]] = X[:, off[b]:off[b + 1]]
+        second = batch(block_n, other, other, limbs, tau, False, dual_max, device=device)
+        for b, (k, k2) in enumerate(zip(out, second)):
+            if k.rank + k2.rank != int(block_n[b]):
+                rx, ry = (k.rank, k2.rank) if k.branch == "dual" else (k2.rank, k.rank)
+                raise KernelVectorError(f"{WRONG_VECTOR_MESSAGE}: block {b}: rank {rx} found on X plus rank {ry} found on Y is not n = {int(block_n[b])}")
+    return out
+
+
+def vectors_to_mp(block: BlockKernel):
+    """The vectors of a block as lists of mpmath numbers (the exact sums of the limbs), one list per vector."""
+    from .mw import from_limbs
+    v = np.asarray(block.vectors)
+    return [list(from_limbs(v[:, :, c])) for c in range(v.shape[2])]

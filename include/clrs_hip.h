@@ -362,7 +362,20 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   one multi-word add of beta C), so results are reproducible bit for bit.  beta = 0 never reads C; rows m .. ldc - 1 of C are never written; k = 0 gives
  *   C <- beta C; m = 0 or n = 0 is a no-op.  CLRS_ERR_INVALID (message: clrs_last_error): limbs not on offer, alpha / beta out of range, a negative size or offset,
  *   a leading dimension smaller than the rows it holds, a matrix that leaves its plane, null pools with a non-empty job, or two jobs whose C ranges
- *   [c_off, c_off + (n - 1) ldc + m) overlap (the ranges as intervals: interleaved outputs are refused too). */
+ *   [c_off, c_off + (n - 1) ldc + m) overlap (the ranges as intervals: interleaved outputs are refused too).
+ * clrs_mw_kernel_vectors: kernel vectors of the PSD blocks of a solution (step 1 of the reference's exact_solution, detecteigenvectors, src/rounding.jl:575-642;
+ *   DESIGN.md section 12), host pointers, no context.  X and Y are planar [limbs][plane] in the xy layout: block b is n[b] x n[b] column-major at offset
+ *   sum_{b' < b} n[b']^2 (plane >= sum n^2).  Per block one branch, chosen from limb plane 0: dual (branch[b] = 1) when use_dual != 0 and max |X_b| <= dual_max
+ *   (the caller passes 1 / sqrt(kernel_round_errbound)): X_b is eliminated by the diagonally pivoted elimination of clrs_mw_rank_reveal (every index a candidate,
+ *   stop at pivots <= tau = kernel_errbound), rank r, count[b] = r vectors, vector c has 1 at perm[c], W[c, a] at perm[r + a], 0 at the other pivots; primal
+ *   (branch[b] = 0) otherwise: Y_b is eliminated, rank r, count[b] = n - r vectors, vector a has 1 at perm[r + a], -W[c, a] at perm[c], 0 at the other
+ *   non-pivots.  Outputs: perm (concatenated, n[b] entries each) and rank[b] of the eliminated matrix; V (planar [limbs][plane], block b at its offset): the
+ *   vectors as an n[b] x count[b] column-major matrix in the original index order -- the entries of V outside it are left as they were passed in; resid_max and
+ *   v_max ([sum n], block b at offset sum_{b' < b} n[b'], count[b] entries each, 0 behind them): per vector max_i |head (Y_b V_b)[i, v]| -- the product by the
+ *   kernel of clrs_mw_gemm in its fixed summation order, so clrs_mw_gemm on the returned vectors restates it bit for bit -- and max_i |head V_b[i, v]|; pivot_resid
+ *   (planar [limbs][sum n]): the remaining diagonal of the n - r non-pivots of the eliminated matrix, as clrs_mw_rank_reveal returns it.  CLRS_ERR_INVALID before
+ *   anything is launched: limbs not on offer, a negative count, size or plane, blocks that leave their plane, a null pointer, tau <= 0 (or NaN), and the size
+ *   limit of clrs_mw_rank_reveal. */
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
 int clrs_mw_rank_reveal(int device, int limbs, int nmat, const int32_t *n, const int32_t *ncand, const double *G, const double *tau, int32_t *perm, int32_t *rank,
@@ -374,6 +387,8 @@ typedef struct clrs_mw_gemm_job {
 } clrs_mw_gemm_job;
 int clrs_mw_gemm(int device, int limbs, int njobs, const clrs_mw_gemm_job *jobs, const double *A, int64_t a_plane, const double *B, int64_t b_plane, double *C,
                  int64_t c_plane);
+int clrs_mw_kernel_vectors(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual, double dual_max,
+                           int32_t *branch, int32_t *perm, int32_t *rank, int32_t *count, double *V, double *resid_max, double *v_max, double *pivot_resid);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 

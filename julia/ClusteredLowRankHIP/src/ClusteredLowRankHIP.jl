@@ -607,6 +607,63 @@ function optimize!(opt; device::Integer=0)
     return status, dualsol, primalsol, t, e
 end
 
+"""
+    kernel_vectors(dualblocks, primalblocks; prec=precision(BigFloat), device=0, kernel_errbound=1e-10, kernel_round_errbound=1e-15, kernel_use_dual=true)
+    kernel_vectors(result; kwargs...)
+
+Step 1 of the reference's `exact_solution` ("Finding the kernel": `detecteigenvectors`, src/rounding.jl:575-642, before the entries are rounded to a
+field) for all blocks in one device call (`clrs_mw_kernel_vectors`, DESIGN.md section 12) at `limbs_for(prec)` words per number.  `dualblocks[b]` /
+`primalblocks[b]`: the square matrices of block `b` (anything `BigFloat(::eltype)` accepts).  Returns, per block, the kernel vectors of the primal
+block as `Vector{Vector{BigFloat}}`, each of length `n_b`, in the reference's row convention (`vecs[i] = Rp[i, pinv]`); the keywords are the kernel
+fields of `RoundingSettings` with its defaults.  Raises, like the reference, when `maximum(abs.(primalblock * v))` of some vector is not below
+`kernel_errbound`.  Where the reference takes an SVD of the primal block (`kernel_use_dual = false`, or a dual block with entries beyond
+`1 / sqrt(kernel_round_errbound)`), the primal block itself is eliminated: the same subspace, in echelon form over other pivot columns.
+`result`: the tuple `solvesdp` returns (`status, dualsol, primalsol, ...`); the blocks are then the `matrixvars` of both solutions and the value is a
+`Dict` from their keys to the vectors.
+"""
+function kernel_vectors(dualblocks::AbstractVector, primalblocks::AbstractVector; prec::Integer=precision(BigFloat), device::Integer=0,
+                        kernel_errbound::Real=1e-10, kernel_round_errbound::Real=1e-15, kernel_use_dual::Bool=true)
+    length(dualblocks) == length(primalblocks) || error("kernel_vectors: one dual block per primal block")
+    K = limbs_for(prec)
+    K >= 4 || error("kernel_vectors: prec = $prec selects $K limbs; the multi-word kernels need at least 4 (prec >= 158)")
+    nb = length(dualblocks)
+    n = Int32[size(M, 1) for M in primalblocks]
+    all(size(dualblocks[b]) == (n[b], n[b]) && size(primalblocks[b]) == (n[b], n[b]) for b in 1:nb) || error("kernel_vectors: blocks must be square and of equal size")
+    off = cumsum(vcat(0, [Int(v)^2 for v in n])); xoff = cumsum(vcat(0, [Int(v) for v in n]))
+    plane, xlen = off[end], xoff[end]
+    Xw = zeros(Float64, max(plane, 1), K); Yw = zeros(Float64, max(plane, 1), K); Vw = zeros(Float64, max(plane, 1), K)
+    for b in 1:nb, cc in 1:n[b], rr in 1:n[b]
+        limbs_of!(Xw, off[b] + rr + (cc - 1) * n[b], BigFloat(dualblocks[b][rr, cc]), K)
+        limbs_of!(Yw, off[b] + rr + (cc - 1) * n[b], BigFloat(primalblocks[b][rr, cc]), K)
+    end
+    branch = zeros(Int32, max(nb, 1)); rank = zeros(Int32, max(nb, 1)); count = zeros(Int32, max(nb, 1)); perm = zeros(Int32, max(xlen, 1))
+    rmax = zeros(Float64, max(xlen, 1)); vmax = zeros(Float64, max(xlen, 1)); piv = zeros(Float64, max(xlen, 1), K)
+    check(ccall((:clrs_mw_kernel_vectors, libclrs[]), Cint,
+                (Cint, Cint, Cint, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Cint, Cdouble, Cint, Cdouble, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                device, K, nb, n, Xw, Yw, plane, Float64(kernel_errbound), kernel_use_dual ? 1 : 0, 1 / sqrt(Float64(kernel_round_errbound)),
+                branch, perm, rank, count, Vw, rmax, vmax, piv))
+    out = Vector{Vector{Vector{BigFloat}}}(undef, nb)
+    setprecision(BigFloat, max(prec, 64 * K + 64)) do
+        for b in 1:nb
+            vecs = Vector{Vector{BigFloat}}()
+            for v in 1:count[b]
+                res = rmax[xoff[b] + v]
+                res < kernel_errbound || error("Warning: wrong vector detected! (error = $res, block $b, maximum(abs.(v)) = $(vmax[xoff[b] + v]))")
+                push!(vecs, [BigFloat(sum(BigFloat(Vw[off[b] + i + (v - 1) * n[b], l]) for l in K:-1:1); precision=prec) for i in 1:n[b]])
+            end
+            out[b] = vecs
+        end
+    end
+    return out
+end
+
+function kernel_vectors(result::Tuple; kwargs...)
+    dualsol, primalsol = result[2], result[3]
+    keys_ = collect(keys(primalsol.matrixvars))
+    vecs = kernel_vectors([dualsol.matrixvars[k] for k in keys_], [primalsol.matrixvars[k] for k in keys_]; kwargs...)
+    return Dict(k => vecs[i] for (i, k) in enumerate(keys_))
+end
+
 # `ClusteredLowRankHIP.Optimizer`: the MOI optimizer type lives in the package extension (ext/ClusteredLowRankHIPMOIExt.jl, loaded with
 # MathOptInterface), which registers it here; JuMP takes any callable that returns an optimizer: `GenericModel{BigFloat}(ClusteredLowRankHIP.Optimizer)`
 const OPTIMIZER_TYPE = Ref{Any}(nothing)
