@@ -6,7 +6,7 @@ Import through the repo-root shim:  `import clrs_amd`.
 from . import sdp  # noqa: F401
 from .sdp import Block, ClusteredLowRankSDP, HiLo, LowRankMat, flatten  # noqa: F401
 from . import rounding  # noqa: F401
-from .rounding import KernelVectorError, RoundingSettings, kernel_vectors, vectors_to_mp  # noqa: F401
+from .rounding import KernelVectorError, RoundingSettings, kernel_vectors, rationalize, vectors_to_fractions, vectors_to_mp  # noqa: F401
 
 __all__ = ["sdp", "Block", "ClusteredLowRankSDP", "HiLo", "LowRankMat", "flatten", "rounding", "KernelVectorError", "RoundingSettings", "kernel_vectors",
-           "vectors_to_mp"]
+           "vectors_to_mp", "rationalize", "vectors_to_fractions"]

@@ -153,6 +153,9 @@ SYMBOLS = {
     "clrs_mw_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(MwGemmJob), p_d, C.c_int64, p_d, C.c_int64, p_d, C.c_int64]),
     "clrs_mw_kernel_vectors": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i32, p_d, p_d, C.c_int, C.c_double, C.c_int, C.c_double, p_i32, p_i32, p_i32, p_i32, p_d, p_d,
                                          p_d, p_d]),
+    "clrs_mw_rationalize": (C.c_int, [C.c_int, C.c_int, C.c_int, p_d, C.c_int, C.c_double, p_d, p_d, p_i32, p_d]),
+    "clrs_mw_kernel_vectors_rational": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i32, p_d, p_d, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, p_i32, p_i32,
+                                                  p_i32, p_i32, p_d, p_d, p_d, p_d, p_d, p_d, p_i32, p_d, p_d]),
     "clrs_mw_schur_solve": (C.c_int, [C.c_void_p, p_d, p_d, p_d, p_d]),
     "clrs_mw_cholesky_blocks_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "clrs_mw_sync_status_cholesky": (C.c_int, [C.c_void_p]),

@@ -26,6 +26,7 @@
 #include "clrs_mw_rank.hip.h"
 #include "clrs_mw_gemm.hip.h"
 #include "clrs_mw_kernel_vectors.hip.h"
+#include "clrs_mw_rational.hip.h"
 #include "clrs_mw_inst.h"
 #include "clrs_mw_tables.h"      // host only: mw_build_tables, mw_cut_digits
 #ifdef MW_SPLIT_UNITS        // the kernels of these limb counts are compiled in units of their own (clrs_mw_inst.hip)
@@ -1726,13 +1727,24 @@ extern "C" int clrs_mw_gemm(int device, int limbs, int njobs, const clrs_mw_gemm
 }
 
 // ---- kernel vectors of solution blocks (clrs_mw_kernel_vectors.hip.h): no context, host pointers, the buffers of one call released on every path ----
-extern "C" int clrs_mw_kernel_vectors(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual,
-                                      double dual_max, int32_t *branch, int32_t *perm, int32_t *rank, int32_t *count, double *V, double *resid_max, double *v_max,
-                                      double *pivot_resid) {
+// the outputs of the rational rounding (clrs_mw_rational.hip.h); all null: the vectors are not rounded
+struct MwKvRational {
+    double errbound;
+    double *num, *den;
+    int32_t *status;
+    double *Vq, *resid_max;
+};
+
+// both entries: clrs_mw_kernel_vectors (rat == nullptr) and clrs_mw_kernel_vectors_rational
+static int mw_kernel_vectors_run(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual,
+                                 double dual_max, int32_t *branch, int32_t *perm, int32_t *rank, int32_t *count, double *V, double *resid_max, double *v_max,
+                                 double *pivot_resid, const MwKvRational *rat) {
     if (limbs != 4 && limbs != 5 && limbs != 6 && limbs != 8 && limbs != 10) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: limbs must be 4, 5, 6, 8 or 10");
     if (nblk < 0 || plane < 0) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: negative block count or plane length");
     if (!(tau > 0.0)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: tau must be positive");
     if (nblk > 0 && (!n || !X || !Y || !branch || !perm || !rank || !count || !V || !resid_max || !v_max || !pivot_resid)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: null argument");
+    if (rat && !(rat->errbound > 0.0)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: round_errbound must be positive");
+    if (rat && nblk > 0 && (!rat->num || !rat->den || !rat->status || !rat->Vq || !rat->resid_max)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: null argument");
     std::vector<MwRankMat> mats(nblk);
     std::vector<MwKvBlk> blks(nblk);
     i64 glen = 0, xlen = 0;
@@ -1771,6 +1783,20 @@ extern "C" int clrs_mw_kernel_vectors(int device, int limbs, int nblk, const int
     MWCHECK(hipMemset(d_resid, 0, std::max<size_t>(xb, 1) * sizeof(double)));
     MWCHECK(hipMemset(d_rmax, 0, std::max<size_t>(xlen, 1) * sizeof(double)));
     MWCHECK(hipMemset(d_vmax, 0, std::max<size_t>(xlen, 1) * sizeof(double)));
+    // the rounded vectors and what goes with them: uploaded like V, so that what the vectors do not cover comes back as it went
+    double *d_num = nullptr, *d_den = nullptr, *d_Vq = nullptr, *d_rmax2 = nullptr, *d_vmax2 = nullptr;
+    int *d_status = nullptr;
+    mwi64 *d_idx = nullptr;
+    if (rat) {
+        MWCHECK(bufs.get(&d_num, (size_t)plane)); MWCHECK(bufs.get(&d_den, (size_t)plane)); MWCHECK(bufs.get(&d_status, (size_t)plane)); MWCHECK(bufs.get(&d_Vq, pool));
+        MWCHECK(bufs.get(&d_rmax2, (size_t)xlen)); MWCHECK(bufs.get(&d_vmax2, (size_t)xlen));
+        MWCHECK(hipMemcpy(d_num, rat->num, (size_t)plane * sizeof(double), hipMemcpyHostToDevice));
+        MWCHECK(hipMemcpy(d_den, rat->den, (size_t)plane * sizeof(double), hipMemcpyHostToDevice));
+        MWCHECK(hipMemcpy(d_status, rat->status, (size_t)plane * sizeof(int), hipMemcpyHostToDevice));
+        MWCHECK(hipMemcpy(d_Vq, rat->Vq, pool * sizeof(double), hipMemcpyHostToDevice));
+        MWCHECK(hipMemset(d_rmax2, 0, std::max<size_t>(xlen, 1) * sizeof(double)));
+        MWCHECK(hipMemset(d_vmax2, 0, std::max<size_t>(xlen, 1) * sizeof(double)));
+    }
     // ONE elimination launch over all blocks (it returns synchronised)
     int rc = mw_rank_launch(limbs, nullptr, mats, d_G, d_Wk, plane, d_W, d_perm, d_rank, d_resid, xlen);
     if (rc) return rc;
@@ -1781,12 +1807,14 @@ extern "C" int clrs_mw_kernel_vectors(int device, int limbs, int nblk, const int
     double *d_R = d_G;
     std::vector<MwGemmJob> jobs;
     std::vector<int> tiles;
+    std::vector<mwi64> idx;                                   // the positions of the vectors' entries in the plane (the numbers to round)
     for (int b = 0; b < nblk; b++) {
         const int nb = n[b], r = rank[b];
         if (r < 0 || r > nb) return mw_fail(CLRS_ERR_HIP, "kernel vectors: the elimination returned a rank outside 0 .. n");
         blks[b].rank = r;
         blks[b].count = count[b] = blks[b].branch == MW_KV_DUAL ? r : nb - r;
         if (count[b] == 0) continue;
+        if (rat) for (i64 e = 0; e < (i64)nb * count[b]; e++) idx.push_back(blks[b].off + e);
         const int t = (int)jobs.size();
         jobs.push_back(MwGemmJob{nb, count[b], nb, 0, 0, 1, 0, nb, nb, nb, blks[b].off, blks[b].off, blks[b].off});
         for (int tj = 0; tj < (count[b] + MW_GEMM_T - 1) / MW_GEMM_T; tj++)
@@ -1808,11 +1836,85 @@ extern "C" int clrs_mw_kernel_vectors(int device, int limbs, int nblk, const int
 #undef MW_KV_CASE
         hipLaunchKernelGGL(k_mw_kv_colmax, dim3((unsigned)nblk), dim3(MW_NT), 0, nullptr, d_blks, d_R, d_V, d_rmax, d_vmax);
         MWCHECK(hipGetLastError());
+        if (rat) {
+            // every entry of every vector rounded (one lane each), then the second check of the reference: Y_b Vq_b by the same job list (R is overwritten:
+            // its maxima are taken) and its column maxima
+            MWCHECK(bufs.get(&d_idx, idx.size()));
+            MWCHECK(hipMemcpy(d_idx, idx.data(), idx.size() * sizeof(mwi64), hipMemcpyHostToDevice));
+            const unsigned rgrid = (unsigned)((idx.size() + MW_NT - 1) / MW_NT);
+#define MW_KV_CASE(Kc)                                                                                                                                            \
+    case Kc:                                                                                                                                                      \
+        hipLaunchKernelGGL(k_mw_rationalize<Kc>, dim3(rgrid), dim3(MW_NT), 0, nullptr, d_V, (mwi64)plane, d_idx, (int)idx.size(), rat->errbound, d_num, d_den,    \
+                           d_status, d_Vq);                                                                                                                       \
+        hipLaunchKernelGGL(k_mw_gemm<Kc>, dim3(grid), dim3(MW_NT), MW_GEMM_LDS(Kc), nullptr, d_jobs, d_tiles, d_Y, (mwi64)plane, d_Vq, (mwi64)plane, d_R,         \
+                           (mwi64)plane);                                                                                                                         \
+        break;
+            switch (limbs) { MW_KV_CASE(4) MW_KV_CASE(5) MW_KV_CASE(6) MW_KV_CASE(8) MW_KV_CASE(10) }
+#undef MW_KV_CASE
+            hipLaunchKernelGGL(k_mw_kv_colmax, dim3((unsigned)nblk), dim3(MW_NT), 0, nullptr, d_blks, d_R, d_Vq, d_rmax2, d_vmax2);
+            MWCHECK(hipGetLastError());
+        }
         MWCHECK(hipStreamSynchronize(nullptr));
         MWCHECK(hipMemcpy(V, d_V, pool * sizeof(double), hipMemcpyDeviceToHost));
+        if (rat) {
+            MWCHECK(hipMemcpy(rat->num, d_num, (size_t)plane * sizeof(double), hipMemcpyDeviceToHost));
+            MWCHECK(hipMemcpy(rat->den, d_den, (size_t)plane * sizeof(double), hipMemcpyDeviceToHost));
+            MWCHECK(hipMemcpy(rat->status, d_status, (size_t)plane * sizeof(int), hipMemcpyDeviceToHost));
+            MWCHECK(hipMemcpy(rat->Vq, d_Vq, pool * sizeof(double), hipMemcpyDeviceToHost));
+        }
     }
+    if (rat) MWCHECK(hipMemcpy(rat->resid_max, d_rmax2, (size_t)xlen * sizeof(double), hipMemcpyDeviceToHost));
     MWCHECK(hipMemcpy(resid_max, d_rmax, (size_t)xlen * sizeof(double), hipMemcpyDeviceToHost));
     MWCHECK(hipMemcpy(v_max, d_vmax, (size_t)xlen * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int clrs_mw_kernel_vectors(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual,
+                                      double dual_max, int32_t *branch, int32_t *perm, int32_t *rank, int32_t *count, double *V, double *resid_max, double *v_max,
+                                      double *pivot_resid) {
+    return mw_kernel_vectors_run(device, limbs, nblk, n, X, Y, plane, tau, use_dual, dual_max, branch, perm, rank, count, V, resid_max, v_max, pivot_resid, nullptr);
+}
+
+extern "C" int clrs_mw_kernel_vectors_rational(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau,
+                                               int use_dual, double dual_max, double round_errbound, int32_t *branch, int32_t *perm, int32_t *rank,
+                                               int32_t *count, double *V, double *resid_max, double *v_max, double *pivot_resid, double *num, double *den,
+                                               int32_t *status, double *Vq, double *round_resid_max) {
+    const MwKvRational rat{round_errbound, num, den, status, Vq, round_resid_max};
+    return mw_kernel_vectors_run(device, limbs, nblk, n, X, Y, plane, tau, use_dual, dual_max, branch, perm, rank, count, V, resid_max, v_max, pivot_resid, &rat);
+}
+
+// ---- rounding to rationals (clrs_mw_rational.hip.h): no context, host pointers.  The device pool is compact (plane = count), so nothing behind the first
+// `count` entries of any of the caller's planes is read or written ----
+extern "C" int clrs_mw_rationalize(int device, int limbs, int count, const double *v, int plane, double errbound, double *num, double *den, int32_t *status,
+                                   double *vq) {
+    if (limbs != 4 && limbs != 5 && limbs != 6 && limbs != 8 && limbs != 10) return mw_fail(CLRS_ERR_INVALID, "rationalize: limbs must be 4, 5, 6, 8 or 10");
+    if (count < 0) return mw_fail(CLRS_ERR_INVALID, "rationalize: negative count");
+    if (plane < count) return mw_fail(CLRS_ERR_INVALID, "rationalize: the numbers leave their plane");
+    if (!(errbound > 0.0)) return mw_fail(CLRS_ERR_INVALID, "rationalize: errbound must be positive");
+    if (count > 0 && (!v || !num || !den || !status || !vq)) return mw_fail(CLRS_ERR_INVALID, "rationalize: null argument");
+    if (count == 0) return 0;
+    MWCHECK(hipSetDevice(device));
+    MwRankBufs bufs;
+    const size_t cnt = (size_t)count;
+    double *d_v = nullptr, *d_vq = nullptr, *d_num = nullptr, *d_den = nullptr;
+    int *d_status = nullptr;
+    MWCHECK(bufs.get(&d_v, cnt * limbs)); MWCHECK(bufs.get(&d_vq, cnt * limbs)); MWCHECK(bufs.get(&d_num, cnt)); MWCHECK(bufs.get(&d_den, cnt));
+    MWCHECK(bufs.get(&d_status, cnt));
+    for (int l = 0; l < limbs; l++) MWCHECK(hipMemcpy(d_v + (size_t)l * cnt, v + (size_t)l * plane, cnt * sizeof(double), hipMemcpyHostToDevice));
+    const unsigned grid = (unsigned)((cnt + MW_NT - 1) / MW_NT);
+#define MW_RAT_CASE(Kc)                                                                                                                                           \
+    case Kc:                                                                                                                                                      \
+        hipLaunchKernelGGL(k_mw_rationalize<Kc>, dim3(grid), dim3(MW_NT), 0, nullptr, d_v, (mwi64)count, (const mwi64 *)nullptr, count, errbound, d_num, d_den,   \
+                           d_status, d_vq);                                                                                                                       \
+        break;
+    switch (limbs) { MW_RAT_CASE(4) MW_RAT_CASE(5) MW_RAT_CASE(6) MW_RAT_CASE(8) MW_RAT_CASE(10) }
+#undef MW_RAT_CASE
+    MWCHECK(hipGetLastError());
+    MWCHECK(hipStreamSynchronize(nullptr));
+    MWCHECK(hipMemcpy(num, d_num, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(den, d_den, cnt * sizeof(double), hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(status, d_status, cnt * sizeof(int), hipMemcpyDeviceToHost));
+    for (int l = 0; l < limbs; l++) MWCHECK(hipMemcpy(vq + (size_t)l * plane, d_vq + (size_t)l * cnt, cnt * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -45,3 +45,35 @@ def delsarte(n, d, costheta, prec=DEFAULT_PREC) -> ClusteredLowRankSDP:
         c = -np.ones(P)
         return ClusteredLowRankSDP(maximize=False, constant=0.0, blocks=[blocks], B=[B], c=[c], C=[Cs],
                                    b=np.ones(1), names={"free": ["M"], "blocks": [[b.name for b in blocks]]})
+
+
+def delsarte_exact(n, d, costheta, prec=DEFAULT_PREC) -> ClusteredLowRankSDP:
+    """The Delsarte bound in the form whose optimal solution has a rational kernel (reference examples/DelsarteExact.jl:7-35), for the rounding step:
+
+        minimise 1 + sum_{k=0}^{2d} a_k   s.t.  sum_k a_k P_k^n(x) + <A, b b^T> + (1+x)(cos t - x) <B, b' b'^T> = -1   on samples,   a_k >= 0
+
+    with the plain Chebyshev basis b = (T_0 .. T_d), b' = (T_0 .. T_{d-1}) -- NO change of basis, so the kernel vectors of A and B are those of the
+    polynomial problem, not of an approximately orthogonalised one -- and the 2d + 1 Chebyshev points of [-1, 1] rounded to four decimals (rational
+    samples).  One cluster, P = 2d + 1, no free variables; blocks a_0 .. a_2d (dense 1 x 1), A ((d+1) x (d+1)) and B (d x d), rank one."""
+    with mp.workprec(prec):
+        ct = mp.mpf(costheta) if not isinstance(costheta, str) else mp.mpf(eval(costheta))
+        xs = [mp.mpf(int(mp.nint(x * 10 ** 4))) / 10 ** 4 for x in sample_points_chebyshev(2 * d)]
+        ns = len(xs)
+        V = chebyshev_values(d, xs)
+        G = gegenbauer_values(2 * d, n, xs)
+        blocks, Cs = [], []
+        for k in range(2 * d + 1):
+            ent = {p: HiLo.of(np.array([[G[p, k]]], dtype=object)) for p in range(ns)}
+            blocks.append(Block(m=1, delta=1, entries={(0, 0): ent}, name=("a", k)))
+            Cs.append(np.ones((1, 1)))
+        eA = {p: LowRankMat(np.array([1.0]), HiLo.of(V[p:p + 1, :d + 1]), HiLo.of(V[p:p + 1, :d + 1])) for p in range(ns)}
+        blocks.append(Block(m=1, delta=d + 1, entries={(0, 0): eA}, name="A"))
+        Cs.append(np.zeros((d + 1, d + 1)))
+        eB = {}
+        for p in range(ns):
+            lam = np.array([(1 + xs[p]) * (ct - xs[p])], dtype=object)
+            eB[p] = LowRankMat(HiLo.of(lam), HiLo.of(V[p:p + 1, :d]), HiLo.of(V[p:p + 1, :d]))
+        blocks.append(Block(m=1, delta=d, entries={(0, 0): eB}, name="B"))
+        Cs.append(np.zeros((d, d)))
+        return ClusteredLowRankSDP(maximize=False, constant=1.0, blocks=[blocks], B=[np.zeros((ns, 0))], c=[-np.ones(ns)], C=[Cs],
+                                   b=np.zeros(0), names={"free": [], "blocks": [[b.name for b in blocks]]})

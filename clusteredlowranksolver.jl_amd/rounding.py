@@ -5,20 +5,28 @@ At an optimum X_b Y_b = 0 for every PSD block: the row space of the dual block X
 reduced row-echelon form of a column-pivoted QR of X_b; for a symmetric PSD block that form is [I W] over the pivots of the diagonally pivoted
 elimination the preprocessing already uses (`mw.rank_reveal`).  Where the reference takes an SVD of Y_b instead (kernel_use_dual = false, or X_b too
 large to be trusted), Y_b itself is eliminated and the relations of its dependent columns are the kernel: the same subspace, in echelon form over
-other pivot columns.  Everything after this step (rounding the entries to a field, LLL, the exact solve) is exact arithmetic and stays with the caller.
+other pivot columns.
+
+With `rationalize=True` the entries of the vectors are also rounded to the field QQ on the device (src/rounding.jl:623-628: roundx -> clindep per entry;
+here the first continued-fraction convergent p / q with |q v - p| < kernel_round_errbound, clrs_mw_rationalize) and the rounded
+vectors are tested against the primal block again (src/rounding.jl:630-639).  Everything after that (number fields of degree > 1, LLL, the basis
+transformations, the exact solve) is exact arithmetic and stays with the caller.
 """
 from __future__ import annotations
 
 import dataclasses
+from fractions import Fraction
 from typing import List, Optional
 
 import numpy as np
 
 from . import _lib
 
-__all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vectors", "kernel_vectors_batch", "vectors_to_mp"]
+__all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vectors", "kernel_vectors_batch", "kernel_vectors_rational_batch", "rationalize",
+           "vectors_to_mp", "vectors_to_fractions"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
+CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
 LIMBS = (4, 5, 6, 8, 10)
 
 
@@ -39,7 +47,9 @@ class BlockKernel:
     """The kernel vectors of one block.  `branch`: "dual" (X_b eliminated) or "primal" (Y_b eliminated); `rank`: of the eliminated matrix; `count`: vectors
     (dual: rank, primal: n - rank); `perm`: pivots in pivot order, then the rest; `vectors`: planar (limbs, n, count), one vector per column, original
     index order; `resid_max` / `v_max`: per vector max_i |head (Y_b v)_i| and max_i |head v_i|; `pivot_resid`: planar (limbs, n - rank), the remaining
-    diagonal of the eliminated matrix."""
+    diagonal of the eliminated matrix.  After `kernel_vectors(rationalize=True)` also `num`, `den` (n, count): the entries rounded to num / den, exact
+    integers in fp64, den >= 1; `round_status` (n, count): 0 found, 1 no relation below 2^53, 2 not finite; `vectors_rounded`: num / den as planes
+    (limbs, n, count); `round_resid_max`: per vector max_i |head (Y_b vq)_i|."""
     branch: str
     rank: int
     count: int
@@ -48,11 +58,29 @@ class BlockKernel:
     resid_max: np.ndarray
     v_max: np.ndarray
     pivot_resid: np.ndarray
+    num: Optional[np.ndarray] = None
+    den: Optional[np.ndarray] = None
+    round_status: Optional[np.ndarray] = None
+    vectors_rounded: Optional[np.ndarray] = None
+    round_resid_max: Optional[np.ndarray] = None
+
+    @property
+    def max_num(self) -> int:
+        """the largest |numerator| of the rounded vectors (what basis_transformations prints, src/rounding.jl:799-801)"""
+        return int(np.max(np.abs(self.num))) if self.num is not None and self.num.size else 0
+
+    @property
+    def max_den(self) -> int:
+        """the largest denominator of the rounded vectors"""
+        return int(np.max(self.den)) if self.den is not None and self.den.size else 0
 
 
-def kernel_vectors_batch(block_n, X, Y, limbs: int, tau: float, use_dual: bool, dual_max: float, device: int = 0, V=None):
+def kernel_vectors_batch(block_n, X, Y, limbs: int, tau: float, use_dual: bool, dual_max: float, device: int = 0, V=None, round_errbound: Optional[float] = None,
+                         rounded=None):
     """One call of clrs_mw_kernel_vectors: X, Y planar (limbs, sum n_b^2) in the xy layout.  Returns a list of `BlockKernel`.  `V` (planar, the same shape)
-    is the pool the vectors are written into; what the vectors do not cover stays as passed in (V is modified in place)."""
+    is the pool the vectors are written into; what the vectors do not cover stays as passed in (V is modified in place).
+    `round_errbound`: call clrs_mw_kernel_vectors_rational instead, which also rounds the entries (the further fields of `BlockKernel`); `rounded`: the pools
+    (num (plane,), den (plane,), status (plane,) int32, Vq (limbs, plane)) it writes into, like `V`."""
     n = np.ascontiguousarray(block_n, np.int32).reshape(-1)
     nb = n.size
     off = np.concatenate([[0], np.cumsum(n.astype(np.int64) ** 2)])
@@ -72,15 +100,60 @@ def kernel_vectors_batch(block_n, X, Y, limbs: int, tau: float, use_dual: bool, 
     Xp, Yp, Vp = pad(X), pad(Y), pad(V)
     p_i = lambda a: a.ctypes.data_as(_lib.p_i32)
     p_d = lambda a: a.ctypes.data_as(_lib.p_d)
-    _lib.check(_lib.load().clrs_mw_kernel_vectors(int(device), limbs, nb, p_i(n), p_d(Xp), p_d(Yp), plane, float(tau), int(bool(use_dual)), float(dual_max),
-                                                  p_i(branch), p_i(perm), p_i(rank), p_i(count), p_d(Vp), p_d(rmax), p_d(vmax), p_d(piv)))
+    if round_errbound is None:
+        _lib.check(_lib.load().clrs_mw_kernel_vectors(int(device), limbs, nb, p_i(n), p_d(Xp), p_d(Yp), plane, float(tau), int(bool(use_dual)), float(dual_max),
+                                                      p_i(branch), p_i(perm), p_i(rank), p_i(count), p_d(Vp), p_d(rmax), p_d(vmax), p_d(piv)))
+    else:
+        num, den, status, Vq = (np.zeros(plane), np.zeros(plane), np.zeros(plane, np.int32), np.zeros((limbs, plane))) if rounded is None else rounded
+        for a, shape, dtype in ((num, (plane,), np.float64), (den, (plane,), np.float64), (status, (plane,), np.int32), (Vq, (limbs, plane), np.float64)):
+            if a.shape != shape or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError(f"kernel_vectors_batch: the pools of the rounded vectors must be contiguous, num, den, status ({plane},) and Vq ({limbs}, {plane})")
+        rmax2 = np.zeros(max(xlen, 1))
+        pad1 = lambda a: a if a.size else np.zeros(1, a.dtype)
+        _lib.check(_lib.load().clrs_mw_kernel_vectors_rational(int(device), limbs, nb, p_i(n), p_d(Xp), p_d(Yp), plane, float(tau), int(bool(use_dual)),
+                                                               float(dual_max), float(round_errbound), p_i(branch), p_i(perm), p_i(rank), p_i(count), p_d(Vp),
+                                                               p_d(rmax), p_d(vmax), p_d(piv), p_d(pad1(num)), p_d(pad1(den)), p_i(pad1(status)), p_d(pad(Vq)),
+                                                               p_d(rmax2)))
     out = []
+    cols = lambda a, b, nn, c: np.ascontiguousarray(np.transpose(a[..., off[b]:off[b] + nn * c].reshape(a.shape[:-1] + (c, nn)), (0, 2, 1) if a.ndim == 2 else (1, 0)))
     for b in range(nb):
         nn, r, c = int(n[b]), int(rank[b]), int(count[b])
         vec = np.ascontiguousarray(np.transpose(V[:, off[b]:off[b] + nn * c].reshape(limbs, c, nn), (0, 2, 1)))
         out.append(BlockKernel("dual" if branch[b] else "primal", r, c, perm[xoff[b]:xoff[b + 1]].copy(), vec, rmax[xoff[b]:xoff[b] + c].copy(),
                                vmax[xoff[b]:xoff[b] + c].copy(), piv[:, xoff[b]:xoff[b] + nn - r].copy()))
+        if round_errbound is not None:
+            k = out[-1]
+            k.num, k.den, k.round_status, k.vectors_rounded = cols(num, b, nn, c), cols(den, b, nn, c), cols(status, b, nn, c), cols(Vq, b, nn, c)
+            k.round_resid_max = rmax2[xoff[b]:xoff[b] + c].copy()
     return out
+
+
+def kernel_vectors_rational_batch(block_n, X, Y, limbs: int, tau: float, use_dual: bool, dual_max: float, round_errbound: float, device: int = 0, V=None,
+                                  rounded=None):
+    """One call of clrs_mw_kernel_vectors_rational: `kernel_vectors_batch` plus, on the device, the rounding of every entry of every vector to the first
+    convergent p / q with |q v - p| < round_errbound and the residual of the rounded vectors."""
+    return kernel_vectors_batch(block_n, X, Y, limbs, tau, use_dual, dual_max, device=device, V=V, round_errbound=float(round_errbound), rounded=rounded)
+
+
+def rationalize(values, limbs: int, errbound: float = 1e-15, device: int = 0):
+    """Round numbers to rationals on the device (clrs_mw_rationalize): `values` planar (planes <= limbs, count) or fp64 (count,).  Per number the first
+    continued-fraction convergent p / q of |v| with |q |v| - p| < errbound, the sign restored.  Returns (num, den, status, vq): num, den (count,) exact
+    integers in fp64, status (count,) int32 (0 found; 1 no convergent with p, q < 2^53 within 96 steps; 2 not finite; num = den = 0 for 1 and 2), vq planar
+    (limbs, count) = num / den."""
+    limbs = int(limbs)
+    if limbs not in LIMBS:
+        raise ValueError(f"rationalize: limbs must be one of {LIMBS}, got {limbs}")
+    a = np.asarray(values, dtype=np.float64)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    if a.ndim != 2 or a.shape[0] > limbs:
+        raise ValueError(f"rationalize: values must be fp64 (count,) or planar (planes <= {limbs}, count), got {a.shape}")
+    count = a.shape[1]
+    v = np.zeros((limbs, max(count, 1)))
+    v[:a.shape[0], :count] = a
+    num, den, status, vq = np.zeros(max(count, 1)), np.zeros(max(count, 1)), np.zeros(max(count, 1), np.int32), np.zeros((limbs, max(count, 1)))
+    _lib.check(_lib.load().clrs_mw_rationalize(int(device), limbs, count, v.ctypes.data_as(_lib.p_d), v.shape[1], float(errbound), num.ctypes.data_as(_lib.p_d),
+                                               den.ctypes.data_as(_lib.p_d), status.ctypes.data_as(_lib.p_i32), vq.ctypes.data_as(_lib.p_d)))
+    return num[:count], den[:count], status[:count], vq[:, :count]
 
 
 def _planes(a, limbs, length, what):
@@ -95,15 +168,20 @@ def _planes(a, limbs, length, what):
 
 
 def kernel_vectors(sdp_or_block_n, dualsol, primalsol=None, limbs: Optional[int] = None, settings: Optional[RoundingSettings] = None, device: int = 0,
-                   check_dimensions: bool = False, batch=None) -> List[BlockKernel]:
+                   check_dimensions: bool = False, batch=None, rationalize: bool = False, round_batch=None) -> List[BlockKernel]:
     """The kernel vectors of every PSD block of a solution: `dualsol.X` are the dual blocks, `primalsol.Y` the primal blocks (a `SolveResult` of
     `solvesdp_mw`, or anything with those attributes, fp64 or planar limbs; `primalsol=None`: both from `dualsol`).  `sdp_or_block_n`: the problem (a
     `ClusteredLowRankSDP` or `FlatSDP`) or the block sizes in block order.  `limbs`: 4, 5, 6, 8 or 10 (default: the planes of the solution, 5 for fp64).
     Raises `KernelVectorError` ("wrong vector detected") when max |Y_b v| of some vector is not below `settings.kernel_errbound`
     (src/rounding.jl:608, 631-638) and, with `check_dimensions`, when the rank found on X_b plus the rank found on Y_b is not n_b (src/rounding.jl:611-621;
-    a second elimination, of the matrix the first did not take).  `batch`: the device call (default `kernel_vectors_batch`)."""
+    a second elimination, of the matrix the first did not take).  `batch`: the device call (default `kernel_vectors_batch`).
+    `rationalize`: also round every entry to the rationals with `settings.kernel_round_errbound` (the same device call: `round_batch`, default
+    `kernel_vectors_rational_batch`) and fill `num`, `den`, `round_status`, `vectors_rounded`, `round_resid_max` of every block.  Raises `KernelVectorError`
+    "clindep failed to find a relation" (src/rounding.jl:508) where an entry has no relation, and "wrong vector detected" where max |Y_b vq| of a rounded
+    vector is above `kernel_errbound` (src/rounding.jl:630-639)."""
     settings = RoundingSettings() if settings is None else settings
     batch = kernel_vectors_batch if batch is None else batch
+    round_batch = kernel_vectors_rational_batch if round_batch is None else round_batch
     if hasattr(sdp_or_block_n, "block_n"):
         block_n = sdp_or_block_n.block_n
     elif hasattr(sdp_or_block_n, "blocks"):
@@ -124,12 +202,24 @@ def kernel_vectors(sdp_or_block_n, dualsol, primalsol=None, limbs: Optional[int]
     off = np.concatenate([[0], np.cumsum(block_n.astype(np.int64) ** 2)])
     X, Y = _planes(dualsol.X, limbs, int(off[-1]), "X"), _planes(primalsol.Y, limbs, int(off[-1]), "Y")
     tau, dual_max = float(settings.kernel_errbound), 1.0 / float(np.sqrt(settings.kernel_round_errbound))
-    out = batch(block_n, X, Y, limbs, tau, bool(settings.kernel_use_dual), dual_max, device=device)
+    if rationalize:
+        out = round_batch(block_n, X, Y, limbs, tau, bool(settings.kernel_use_dual), dual_max, float(settings.kernel_round_errbound), device=device)
+    else:
+        out = batch(block_n, X, Y, limbs, tau, bool(settings.kernel_use_dual), dual_max, device=device)
     for b, k in enumerate(out):
         bad = [v for v in range(k.count) if not k.resid_max[v] < tau]
         if bad:
             raise KernelVectorError(f"{WRONG_VECTOR_MESSAGE}: block {b}, vector {bad[0]} ({k.branch} branch): max |Y v| = {float(k.resid_max[bad[0]]):.3e} "
                                     f"is not below kernel_errbound = {tau:.3e} (max |v| = {float(k.v_max[bad[0]]):.3e})")
+    for b, k in enumerate(out if rationalize else ()):
+        failed = np.argwhere(np.asarray(k.round_status).T != 0)                  # (vector, entry), the first vector first
+        if failed.size:
+            v, i = (int(t) for t in failed[0])
+            raise KernelVectorError(f"{CLINDEP_MESSAGE}: block {b}, vector {v}, entry {i} (status {int(k.round_status[i, v])})")
+        bad = [v for v in range(k.count) if k.round_resid_max[v] > tau]
+        if bad:
+            raise KernelVectorError(f"{WRONG_VECTOR_MESSAGE}: block {b}, rounded vector {bad[0]} ({k.branch} branch): max |Y vq| = "
+                                    f"{float(k.round_resid_max[bad[0]]):.3e} is above kernel_errbound = {tau:.3e}")
     if check_dimensions:
         other = Y.copy()                                     # the matrix the first elimination did not take: Y_b after the dual branch, X_b after the primal
         for b, k in enumerate(out):
@@ -148,3 +238,12 @@ def vectors_to_mp(block: BlockKernel):
     from .mw import from_limbs
     v = np.asarray(block.vectors)
     return [list(from_limbs(v[:, :, c])) for c in range(v.shape[2])]
+
+
+def vectors_to_fractions(block: BlockKernel):
+    """The rounded vectors of a block (after `kernel_vectors(rationalize=True)`) as lists of `fractions.Fraction`, one list per vector."""
+    if block.num is None:
+        raise ValueError("vectors_to_fractions: the block was not rounded (kernel_vectors(..., rationalize=True))")
+    if np.any(np.asarray(block.round_status) != 0):
+        raise KernelVectorError(f"{CLINDEP_MESSAGE}: the block has entries without a relation")
+    return [[Fraction(int(block.num[i, c]), int(block.den[i, c])) for i in range(block.num.shape[0])] for c in range(block.num.shape[1])]

@@ -375,7 +375,19 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   kernel of clrs_mw_gemm in its fixed summation order, so clrs_mw_gemm on the returned vectors restates it bit for bit -- and max_i |head V_b[i, v]|; pivot_resid
  *   (planar [limbs][sum n]): the remaining diagonal of the n - r non-pivots of the eliminated matrix, as clrs_mw_rank_reveal returns it.  CLRS_ERR_INVALID before
  *   anything is launched: limbs not on offer, a negative count, size or plane, blocks that leave their plane, a null pointer, tau <= 0 (or NaN), and the size
- *   limit of clrs_mw_rank_reveal. */
+ *   limit of clrs_mw_rank_reveal.
+ * clrs_mw_rationalize: the first `count` numbers of a planar pool v [limbs][plane] rounded to rationals by continued fractions (what the
+ *   reference's roundx -> clindep does per entry for the field QQ, src/rounding.jl:470-512).  Per number: the convergents p_k / q_k of |v|, the first with
+ *   |q_k |v| - p_k| < errbound (evaluated in `limbs` limbs from v itself); num = +-p_k (the sign of v), den = q_k >= 1, exact integers in fp64.  status 0: found;
+ *   1: no convergent with p, q < 2^53 meets the bound within 96 steps; 2: the head of v is NaN or Inf (1 and 2: num = den = 0).  vq [limbs][plane]: num / den in
+ *   `limbs` limbs (0 where den = 0).  Entry i < count of num, den, status and of every plane of vq is written and nothing behind them.  CLRS_ERR_INVALID before
+ *   anything is launched: limbs not on offer, count < 0, plane < count, a null pointer with count > 0, errbound <= 0 (or NaN).
+ * clrs_mw_kernel_vectors_rational: clrs_mw_kernel_vectors (the same arguments, steps and outputs, bit for bit) followed on the device by the rounding of every
+ *   entry of every vector with errbound = round_errbound (the reference's kernel_round_errbound) and by the reference's second check (src/rounding.jl:630-639).
+ *   Further outputs, in the layout of V (block b at its offset, n[b] x count[b] column-major; what the vectors do not cover is left as passed in): num, den
+ *   ([plane]), status ([plane]), Vq ([limbs][plane]: the rounded vectors num / den), and round_resid_max ([sum n], the layout of resid_max): per vector
+ *   max_i |head (Y_b Vq_b)[i, v]|, the product again by the kernel of clrs_mw_gemm.  CLRS_ERR_INVALID as for clrs_mw_kernel_vectors, and for
+ *   round_errbound <= 0 (or NaN) or a null output. */
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
 int clrs_mw_rank_reveal(int device, int limbs, int nmat, const int32_t *n, const int32_t *ncand, const double *G, const double *tau, int32_t *perm, int32_t *rank,
@@ -389,6 +401,11 @@ int clrs_mw_gemm(int device, int limbs, int njobs, const clrs_mw_gemm_job *jobs,
                  int64_t c_plane);
 int clrs_mw_kernel_vectors(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual, double dual_max,
                            int32_t *branch, int32_t *perm, int32_t *rank, int32_t *count, double *V, double *resid_max, double *v_max, double *pivot_resid);
+int clrs_mw_rationalize(int device, int limbs, int count, const double *v, int plane, double errbound, double *num, double *den, int32_t *status, double *vq);
+int clrs_mw_kernel_vectors_rational(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual,
+                                    double dual_max, double round_errbound, int32_t *branch, int32_t *perm, int32_t *rank, int32_t *count, double *V,
+                                    double *resid_max, double *v_max, double *pivot_resid, double *num, double *den, int32_t *status, double *Vq,
+                                    double *round_resid_max);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 

@@ -620,9 +620,15 @@ fields of `RoundingSettings` with its defaults.  Raises, like the reference, whe
 `1 / sqrt(kernel_round_errbound)`), the primal block itself is eliminated: the same subspace, in echelon form over other pivot columns.
 `result`: the tuple `solvesdp` returns (`status, dualsol, primalsol, ...`); the blocks are then the `matrixvars` of both solutions and the value is a
 `Dict` from their keys to the vectors.
+
+`rationalize=true`: the entries are also rounded to the field QQ on the device (`clrs_mw_kernel_vectors_rational`, DESIGN.md section 13: what `roundx` ->
+`clindep` does per entry, src/rounding.jl:623-628 -- the first continued-fraction convergent `p // q` with `|q v - p| < kernel_round_errbound`) and the rounded
+vectors are tested against the primal block again (src/rounding.jl:630-639); the value is then `Vector{Vector{Rational{BigInt}}}` per block.  Raises
+"clindep failed to find a relation" where an entry has none with `p, q < 2^53`, and "wrong vector detected" where `maximum(abs.(primalblock * v))` of a
+rounded vector is above `kernel_errbound`.
 """
 function kernel_vectors(dualblocks::AbstractVector, primalblocks::AbstractVector; prec::Integer=precision(BigFloat), device::Integer=0,
-                        kernel_errbound::Real=1e-10, kernel_round_errbound::Real=1e-15, kernel_use_dual::Bool=true)
+                        kernel_errbound::Real=1e-10, kernel_round_errbound::Real=1e-15, kernel_use_dual::Bool=true, rationalize::Bool=false)
     length(dualblocks) == length(primalblocks) || error("kernel_vectors: one dual block per primal block")
     K = limbs_for(prec)
     K >= 4 || error("kernel_vectors: prec = $prec selects $K limbs; the multi-word kernels need at least 4 (prec >= 158)")
@@ -638,6 +644,31 @@ function kernel_vectors(dualblocks::AbstractVector, primalblocks::AbstractVector
     end
     branch = zeros(Int32, max(nb, 1)); rank = zeros(Int32, max(nb, 1)); count = zeros(Int32, max(nb, 1)); perm = zeros(Int32, max(xlen, 1))
     rmax = zeros(Float64, max(xlen, 1)); vmax = zeros(Float64, max(xlen, 1)); piv = zeros(Float64, max(xlen, 1), K)
+    if rationalize
+        num = zeros(Float64, max(plane, 1)); den = zeros(Float64, max(plane, 1)); rstat = zeros(Int32, max(plane, 1))
+        Vq = zeros(Float64, max(plane, 1), K); rmax2 = zeros(Float64, max(xlen, 1))
+        check(ccall((:clrs_mw_kernel_vectors_rational, libclrs[]), Cint,
+                    (Cint, Cint, Cint, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Cint, Cdouble, Cint, Cdouble, Cdouble, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}),
+                    device, K, nb, n, Xw, Yw, plane, Float64(kernel_errbound), kernel_use_dual ? 1 : 0, 1 / sqrt(Float64(kernel_round_errbound)),
+                    Float64(kernel_round_errbound), branch, perm, rank, count, Vw, rmax, vmax, piv, num, den, rstat, Vq, rmax2))
+        outq = Vector{Vector{Vector{Rational{BigInt}}}}(undef, nb)
+        for b in 1:nb
+            vecs = Vector{Vector{Rational{BigInt}}}()
+            for v in 1:count[b]
+                res = rmax[xoff[b] + v]
+                res < kernel_errbound || error("Warning: wrong vector detected! (error = $res, block $b, maximum(abs.(v)) = $(vmax[xoff[b] + v]))")
+                for i in 1:n[b]
+                    st = rstat[off[b] + i + (v - 1) * n[b]]
+                    st == 0 || error("clindep failed to find a relation: block $b, vector $v, entry $i (status $st)")
+                end
+                res2 = rmax2[xoff[b] + v]
+                res2 > kernel_errbound && error("Warning: wrong vector detected! (error = $res2 after rounding, block $b)")
+                push!(vecs, [BigInt(num[off[b] + i + (v - 1) * n[b]]) // BigInt(den[off[b] + i + (v - 1) * n[b]]) for i in 1:n[b]])
+            end
+            outq[b] = vecs
+        end
+        return outq
+    end
     check(ccall((:clrs_mw_kernel_vectors, libclrs[]), Cint,
                 (Cint, Cint, Cint, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Cint, Cdouble, Cint, Cdouble, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
                 device, K, nb, n, Xw, Yw, plane, Float64(kernel_errbound), kernel_use_dual ? 1 : 0, 1 / sqrt(Float64(kernel_round_errbound)),
@@ -662,6 +693,28 @@ function kernel_vectors(result::Tuple; kwargs...)
     keys_ = collect(keys(primalsol.matrixvars))
     vecs = kernel_vectors([dualsol.matrixvars[k] for k in keys_], [primalsol.matrixvars[k] for k in keys_]; kwargs...)
     return Dict(k => vecs[i] for (i, k) in enumerate(keys_))
+end
+
+"""
+    rationalize(v::AbstractVector{BigFloat}; prec=precision(BigFloat), errbound=1e-15, device=0)
+
+Round numbers to rationals on the device (`clrs_mw_rationalize`, DESIGN.md section 13) at `limbs_for(prec)` words per number: per number the first
+continued-fraction convergent `p // q` of `|v|` with `|q |v| - p| < errbound`, the sign restored.  Returns `(rationals, status)`: `status[i]` is 0 where a
+relation was found, 1 where none with `p, q < 2^53` exists within 96 steps, 2 where `v[i]` is not finite; `rationals[i]` is `0 // 1` unless `status[i] == 0`.
+"""
+function rationalize(v::AbstractVector{BigFloat}; prec::Integer=precision(BigFloat), errbound::Real=1e-15, device::Integer=0)
+    K = limbs_for(prec)
+    K >= 4 || error("rationalize: prec = $prec selects $K limbs; the multi-word kernels need at least 4 (prec >= 158)")
+    cnt = length(v)
+    vw = zeros(Float64, max(cnt, 1), K); vq = zeros(Float64, max(cnt, 1), K)
+    for i in 1:cnt
+        isfinite(v[i]) ? limbs_of!(vw, i, v[i], K) : (vw[i, 1] = Float64(v[i]))
+    end
+    num = zeros(Float64, max(cnt, 1)); den = zeros(Float64, max(cnt, 1)); status = zeros(Int32, max(cnt, 1))
+    check(ccall((:clrs_mw_rationalize, libclrs[]), Cint,
+                (Cint, Cint, Cint, Ptr{Float64}, Cint, Cdouble, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Float64}),
+                device, K, cnt, vw, max(cnt, 1), Float64(errbound), num, den, status, vq))
+    return [status[i] == 0 ? BigInt(num[i]) // BigInt(den[i]) : big(0) // big(1) for i in 1:cnt], status[1:cnt]
 end
 
 # `ClusteredLowRankHIP.Optimizer`: the MOI optimizer type lives in the package extension (ext/ClusteredLowRankHIPMOIExt.jl, loaded with
