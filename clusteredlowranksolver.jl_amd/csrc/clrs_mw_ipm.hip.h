@@ -8,6 +8,7 @@
 // termination (src/solver.jl:921-950).  The smallest eigenvalue of L^-1 dM L^-T is taken in fp64 (Householder + Sturm
 // multisection) from the multi-word congruence rounded to fp64 -- the reference, too, hands a Float64 matrix to its Lanczos
 // (KrylovKit, tol 1e-5, src/solver.jl:1659) -- everything else carries K limbs.
+#include "clrs_mw_zi_panels.h"      // host only: the launch rule of k_mwi_Zi, its MWI_ZS / MWI_ZL
 
 enum { MSC_MU = 0, MSC_MUS, MSC_XY, MSC_XdY, MSC_dXY, MSC_dXdY, MSC_CY, MSC_DOBJ, MSC_POBJ, MSC_GAP, MSC_COUNT = 16 };
 enum { MREC_ITER = 0, MREC_MU, MREC_DOBJ, MREC_POBJ, MREC_GAP, MREC_DERR, MREC_PERR, MREC_AD, MREC_AP, MREC_BETA, MREC_MAXP, MREC_MAXp, MREC_MAXd,
@@ -1105,12 +1106,10 @@ __global__ __launch_bounds__(MW_NT) void k_mwi_Z(const MwDev q, const MwIpmDev p
 
 // The same with the explicit inverse Xi = chol(X)^-1 that k_mw_potrf_x leaves beside the factor: X^-1 M = Xi^T (Xi M), three
 // block products.  They are independent column by column, and one compute unit issues them no faster than its four SIMDs
-// allow, so a block is split over MWI_ZS or more workgroups (panels of at most eight columns) by column panels (eight lanes per entry, MW_PT threads); the panels go to
+// allow, so a block is split over MWI_ZS or more workgroups (panels of at most eight columns) by column panels (eight lanes per entry; 512 or 256 threads: clrs_mw_zi_panels.h); the panels go to
 // a scratch matrix and the workgroup of a block that finishes last symmetrises it (a counter per block).
-#define MWI_ZS 4
-#ifndef MWI_ZL
-#define MWI_ZL 8          // (16 lanes per entry with two-column panels -- one term per lane and product -- is slower: 0.4178 against 0.4150 ms per iteration)
-#endif
+// (MWI_ZS, MWI_ZL and the launch rule -- 512 threads, or 256 with panels of half the width: one wave per SIMD -- are in clrs_mw_zi_panels.h; the
+// workgroup's size is read from the launch)
 // KA <= K: limbs of the three products (MwIpmDev::klow); the panels in the scratch matrix and the symmetrised result carry K planes, the upper ones zero
 template <int K, int KA>
 __device__ __forceinline__ void mwi_Zi_body(const MwDev &q, const MwIpmDev &p, int which) {
@@ -1119,7 +1118,7 @@ __device__ __forceinline__ void mwi_Zi_body(const MwDev &q, const MwIpmDev &p, i
     if (nomu) which = 0;
     const MwBlk &k = q.blk[blockIdx.x];
     if (!k.inv) return;
-    const int n = k.n, tid = threadIdx.x, sub = tid % MWI_ZL;
+    const int n = k.n, tid = threadIdx.x, sub = tid % MWI_ZL, nt = blockDim.x;      // nt: MWI_ZT_WIDE or MWI_ZT_NARROW
     const int zs = gridDim.y, pc0 = (n + zs - 1) / zs, c0 = blockIdx.y * pc0, pc = max(0, min(pc0, n - c0));     // this workgroup's columns
     const long np = (long)n * pc0;
     lds_d *M = MW_LDS, *M2 = M + (long)K * np;
@@ -1133,7 +1132,7 @@ __device__ __forceinline__ void mwi_Zi_body(const MwDev &q, const MwIpmDev &p, i
 #define MWZ_STAMP() do { } while (0)
 #endif
     MWZ_STAMP();
-    for (int e0 = 0; e0 < n * pc; e0 += MW_PT / MWI_ZL) {  // M = sg (A Y - R)
+    for (int e0 = 0; e0 < n * pc; e0 += nt / MWI_ZL) {  // M = sg (A Y - R)
         const int e = e0 + tid / MWI_ZL;
         const bool live = e < n * pc;
         const int ee = live ? e : 0, i = ee % n, c = c0 + ee / n;
@@ -1147,7 +1146,7 @@ __device__ __forceinline__ void mwi_Zi_body(const MwDev &q, const MwIpmDev &p, i
     }
     __syncthreads();
     MWZ_STAMP();
-    for (int e0 = 0; e0 < n * pc; e0 += MW_PT / MWI_ZL) {  // M2 = Xi M
+    for (int e0 = 0; e0 < n * pc; e0 += nt / MWI_ZL) {  // M2 = Xi M
         const int e = e0 + tid / MWI_ZL;
         const bool live = e < n * pc;
         const int ee = live ? e : 0, i = ee % n, cl = ee / n;
@@ -1159,7 +1158,7 @@ __device__ __forceinline__ void mwi_Zi_body(const MwDev &q, const MwIpmDev &p, i
     }
     __syncthreads();
     MWZ_STAMP();
-    for (int e0 = 0; e0 < n * pc; e0 += MW_PT / MWI_ZL) {  // Xi^T M2 -> scratch
+    for (int e0 = 0; e0 < n * pc; e0 += nt / MWI_ZL) {  // Xi^T M2 -> scratch
         const int e = e0 + tid / MWI_ZL;
         const bool live = e < n * pc;
         const int ee = live ? e : 0, i = ee % n, cl = ee / n;
@@ -1172,7 +1171,7 @@ __device__ __forceinline__ void mwi_Zi_body(const MwDev &q, const MwIpmDev &p, i
     MWZ_STAMP();
     if (!mwi_last_block(p, &p.zcnt[blockIdx.x], zs)) return;
     MWZ_STAMP();
-    for (int e = tid; e < n * n; e += MW_PT) {
+    for (int e = tid; e < n * n; e += nt) {
         const int i = e % n, c = e / n;
         if (c > i) continue;
         const mw<K> v = cvt<K, KA>(mul_pow2<KA>(add<KA>(ldx_wt<KA>(p.Zs + k.xyoff, q.xylen, i + (long)c * n, p.hop == 2), ldx_wt<KA>(p.Zs + k.xyoff, q.xylen, c + (long)i * n, p.hop == 2)), 0.5));

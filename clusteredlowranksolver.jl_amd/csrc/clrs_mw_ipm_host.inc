@@ -24,6 +24,7 @@ struct MwIpm {
     double *d_rec = nullptr;      // device, two records
     size_t sm_Z = 0, sm_Zi = 0, sm_step = 0;
     int zs = MWI_ZS;              // workgroups per block of k_mwi_Zi
+    int zt = MW_PT;               // ... and their threads (clrs_mw_zi_panels.h)
     int zs_step = MWI_ZS;         // column panels per (block, which) of k_mwi_step's congruences
     size_t sm_bmm = 0;            // LDS of k_mwi_bmm: eight rows and eight columns of K limbs over the largest block side
     bool z_tiled = false;         // blocks with sides beyond 24: the products of X^-1 (...) as tiled launches (k_mwi_bmm)
@@ -128,20 +129,20 @@ extern "C" int clrs_mw_ipm_create_ex(clrs_mw_ctx *c, const clrs_ipm_data *data, 
             if (k.inv) { st->any_xinv = true; maxn_inv = std::max(maxn_inv, (size_t)k.n); }
             else st->any_xsub = true;
         }
-        {   // column panels per block of k_mwi_Zi and of the congruences of k_mwi_step: narrow enough that a product is ONE pass of the workgroup
-            // (64 entries: eight / four lanes each) while the launch stays near one workgroup per compute unit: every workgroup reads the whole
-            // matrices its columns are multiplied with, and with 19 blocks of sides up to 54 or 64 blocks of 32 x 32 one-column panels were slower
-            const int pc = std::max<int>(1, (MW_PT / MWI_ZL) / (int)std::max<size_t>(maxn_inv, 1)), want = ((int)maxn_inv + pc - 1) / pc;
+        {   // column panels per block of k_mwi_Zi (clrs_mw_zi_panels.h: the narrow form of 256 threads where the launch keeps a compute unit per workgroup) and
+            // of the congruences of k_mwi_step: narrow enough that a product is ONE pass of the workgroup (64 entries: eight / four lanes each) while the
+            // launch stays near one workgroup per compute unit: every workgroup reads the whole matrices its columns are multiplied with, and with 19
+            // blocks of sides up to 54 or 64 blocks of 32 x 32 one-column panels were slower
+            const MwZiPanels zp = mw_zi_panels((int)maxn_inv, q.NB, K, c->zi_narrow && maxn_inv <= 24);      // (beyond 24 rows: the tiled path, k_mwi_Zi is not launched)
+            st->zs = zp.zs; st->zt = zp.threads; st->sm_Zi = zp.sm;
             const int old_rule = std::max<int>(MWI_ZS, (int)((maxn_inv + 7) / 8));     // panels of at most eight columns
-            st->zs = std::max<int>(old_rule, std::min<int>(want, 320 / std::max(q.NB, 1)));
-            {   // (the step kernel's panels: four lanes per entry, 64 entries per pass)
+            {   // (the step kernel's panels: four lanes per entry, 64 entries per pass, 256 threads: one wave per SIMD already)
                 const int pcs = std::max<int>(1, 64 / (int)std::max<size_t>(maxn_inv, 1)), wants = ((int)maxn_inv + pcs - 1) / pcs;
                 st->zs_step = std::max<int>(old_rule, std::min<int>(wants, 320 / std::max(q.NB, 1)));
             }
         }
         st->z_tiled = maxn_inv > 24;
         st->sm_bmm = (size_t)2 * K * MWI_BT * maxn_inv * 8;
-        st->sm_Zi = 2 * maxn_inv * ((maxn_inv + st->zs - 1) / st->zs) * K * 8;
         const size_t step_inv_need = 3 * maxn_inv * maxn_inv * K + step_rest;
         bool all_lds_inv = st->any_xinv;
         for (auto &k : c->blk) all_lds_inv = all_lds_inv && k.inv == 1;
@@ -346,7 +347,7 @@ static int mw_ipm_rhs(clrs_mw_ctx *c, hipStream_t stream, int which) {      // Z
         if (st->any_xinv && st->z_tiled) {                // large blocks: each product a launch over 8 x 8 tiles
             const int nt = ((int)st->maxn_inv + MWI_BT - 1) / MWI_BT;
             for (int op = 0; op < 4; op++) hipLaunchKernelGGL(k_mwi_bmm<KK>, dim3(nt * nt, q.NB), dim3(MW_NT), st->sm_bmm, stream, q, p, op, which);
-        } else if (st->any_xinv) hipLaunchKernelGGL(k_mwi_Zi<KK>, dim3(q.NB, st->zs), dim3(MW_PT), st->sm_Zi, stream, q, p, which);
+        } else if (st->any_xinv) hipLaunchKernelGGL(k_mwi_Zi<KK>, dim3(q.NB, st->zs), dim3(st->zt), st->sm_Zi, stream, q, p, which);
         if (st->any_xsub) hipLaunchKernelGGL(k_mwi_Z<KK>, dim3(q.NB), dim3(MW_NT), st->sm_Z, stream, q, p, which, st->lds_ZL ? 1 : 0);
     });
     MWCHECK(hipGetLastError());
