@@ -11,6 +11,10 @@ With `rationalize=True` the entries of the vectors are also rounded to the field
 here the first continued-fraction convergent p / q with |q v - p| < kernel_round_errbound, clrs_mw_rationalize) and the rounded
 vectors are tested against the primal block again (src/rounding.jl:630-639).  Everything after that (number fields of degree > 1, LLL, the basis
 transformations, the exact solve) is exact arithmetic and stays with the caller.
+
+The next fixed-width step of the pipeline is the first work of `project_to_affine_space` (src/rounding.jl:182-211): "Finding the pivots of A using RREF mod p"
+(`find_pivots_modular`, src/rounding.jl:288-333), a reduced row-echelon form of the integer system [A b] over the integers mod a prime of about 10^4.  It runs
+on the device (clrs_modp_rref): `rref_mod_p`, `find_pivots_modular`, `system_pivots`.
 """
 from __future__ import annotations
 
@@ -23,7 +27,7 @@ import numpy as np
 from . import _lib
 
 __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vectors", "kernel_vectors_batch", "kernel_vectors_rational_batch", "rationalize",
-           "vectors_to_mp", "vectors_to_fractions"]
+           "vectors_to_mp", "vectors_to_fractions", "rref_mod_p", "next_prime", "find_pivots_modular", "system_pivots", "PivotList"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -247,3 +251,160 @@ def vectors_to_fractions(block: BlockKernel):
     if np.any(np.asarray(block.round_status) != 0):
         raise KernelVectorError(f"{CLINDEP_MESSAGE}: the block has entries without a relation")
     return [[Fraction(int(block.num[i, c]), int(block.den[i, c])) for i in range(block.num.shape[0])] for c in range(block.num.shape[1])]
+
+
+# ---- pivots of integer systems: RREF mod p (src/rounding.jl:182-211, 288-333; clrs_modp_rref) -------------------------------------------
+MODP_PRIME_LIMIT = 1 << 23          # clrs_modp_rref takes primes 2 <= p < 2^23
+C_NULL_I32 = _lib.p_i32()
+
+
+def _is_prime(n: int) -> bool:
+    if n < 2:
+        return False
+    d = 2
+    while d * d <= n:
+        if n % d == 0:
+            return False
+        d += 1
+    return True
+
+
+def next_prime(x) -> int:
+    """The smallest prime strictly above `x` (Nemo's next_prime, as src/rounding.jl:293 calls it)."""
+    n = max(int(x) + 1, 2)
+    while not _is_prime(n):
+        n += 1
+    return n
+
+
+def _integer_matrix(A, what):
+    """anything np.asarray takes -> a 2-d array of a numpy integer type, or of Python integers (dtype object) where those do not fit; an empty input
+    becomes 0 x 0"""
+    a = np.asarray(A)
+    if a.size == 0:
+        return np.zeros((a.shape[0], a.shape[1]) if a.ndim == 2 else (0, 0), dtype=np.int64)
+    if a.ndim != 2:
+        raise ValueError(f"{what}: the matrix must be two-dimensional, got shape {a.shape}")
+    if a.dtype.kind in "iu":
+        return a
+    if a.dtype != object:
+        raise ValueError(f"{what}: the entries must be integers, got dtype {a.dtype}")
+    for v in a.flat:
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}: the entries must be integers, got {type(v).__name__}")
+    return a
+
+
+def _max_abs(a) -> int:
+    """max |a| as a Python integer"""
+    return max(abs(int(a.max())), abs(int(a.min())))
+
+
+def _residues(a, p):
+    """the matrix `a` reduced mod p on the host, int32 in [0, p)"""
+    if a.size == 0:
+        return np.zeros(a.shape, np.int32)
+    if a.dtype != object and a.dtype != np.uint64:
+        return np.ascontiguousarray(np.mod(a.astype(np.int64, copy=False), np.int64(p)), dtype=np.int32)
+    return np.ascontiguousarray(np.array([int(v) % p for v in a.flat], dtype=np.int64).reshape(a.shape), dtype=np.int32)
+
+
+def rref_mod_p(A, p: int, device: int = 0, want_rref: bool = False):
+    """The reduced row-echelon form of `A` over the integers mod the prime `p` (2 <= p < 2^23) on the device: one call of clrs_modp_rref.  `A`: anything
+    `np.asarray` takes, Python integers of any size included; it is reduced mod `p` on the host.  Returns `(pivots, rank)`, `pivots` the 0-based pivot
+    columns in ascending order (int32, `rank` of them), or with `want_rref` `(pivots, rank, R)`, `R` (nrows, ncols) int32 with residues in [0, p), the
+    pivot rows first and the rows behind them zero."""
+    a = _integer_matrix(A, "rref_mod_p")
+    p = int(p)
+    if p < 2 or p >= MODP_PRIME_LIMIT or not _is_prime(p):
+        raise ValueError(f"rref_mod_p: p must be a prime with 2 <= p < 2^23, got {p}")
+    nrows, ncols = a.shape
+    res = _residues(a, p)
+    pivots = np.full(max(min(nrows, ncols), 1), -1, np.int32)
+    rank = np.zeros(1, np.int32)
+    R = np.zeros((nrows, ncols), np.int32) if want_rref else None
+    null = C_NULL_I32
+    _lib.check(_lib.load().clrs_modp_rref(int(device), nrows, ncols, p, res.ctypes.data_as(_lib.p_i32) if res.size else null, pivots.ctypes.data_as(_lib.p_i32),
+                                          rank.ctypes.data_as(_lib.p_i32), R.ctypes.data_as(_lib.p_i32) if want_rref and R.size else null))
+    r = int(rank[0])
+    return (pivots[:r].copy(), r, R) if want_rref else (pivots[:r].copy(), r)
+
+
+class PivotList(list):
+    """The 0-based pivot columns `find_pivots_modular` returns: a list of ints with two attributes, `primes` (the primes tried, in order) and `p` (the
+    prime whose pivots these are)."""
+    primes: List[int]
+    p: Optional[int]
+
+    def __init__(self, pivots=(), primes=(), p=None):
+        super().__init__(int(c) for c in pivots)
+        self.primes = [int(q) for q in primes]
+        self.p = None if p is None else int(p)
+
+
+def find_pivots_modular(A, maxprimes: int = 3, device: int = 0, batch=None) -> PivotList:
+    """The reference's `find_pivots_modular(A; maxprimes)` (src/rounding.jl:288-311) with its schedule of primes: p = min(max |A|, 10^4), and per round
+    p <- next_prime(p) and the pivot columns of the reduced row-echelon form of A mod p.  The first list with as many pivots as A has rows is returned; after
+    `maxprimes` rounds the first of the longest lists seen.  Returns a `PivotList`: the 0-based pivot columns (the reference's are 1-based), with the
+    primes tried in `.primes`.  An empty matrix gives `[]` with no prime tried (the reference raises on it); `maxprimes < 1` raises
+    `ValueError` (the reference returns `nothing`).  `batch(A, p, device=...)` -> `(pivots, rank)`
+    replaces the device call (default `rref_mod_p`)."""
+    batch = rref_mod_p if batch is None else batch
+    a = _integer_matrix(A, "find_pivots_modular")
+    if int(maxprimes) < 1:
+        raise ValueError(f"find_pivots_modular: maxprimes must be at least 1, got {maxprimes}")
+    if a.size == 0:
+        return PivotList()
+    nrows = a.shape[0]
+    p = min(_max_abs(a), 10 ** 4)
+    history, primes = [], []
+    for _ in range(int(maxprimes)):
+        p = next_prime(p)
+        primes.append(p)
+        pivots, _ = batch(a, p, device=device)[:2]
+        pivots = [int(c) for c in pivots]
+        if len(pivots) == nrows:
+            return PivotList(pivots, primes, p)
+        history.append((pivots, p))
+    best = max(len(h[0]) for h in history)
+    pivots, p = next(h for h in history if len(h[0]) == best)
+    return PivotList(pivots, primes, p)
+
+
+def _rows_cleared_of_denominators(rows):
+    """rows of Fractions -> an object matrix of Python integers, every row multiplied by the least common multiple of its denominators"""
+    from math import gcd
+    out = np.zeros((len(rows), len(rows[0]) if rows else 0), dtype=object)
+    for r, row in enumerate(rows):
+        lcm = 1
+        for v in row:
+            lcm = lcm * v.denominator // gcd(lcm, v.denominator)
+        out[r] = [int(v * lcm) for v in row]
+    return out
+
+
+def system_pivots(A, b, maxprimes: int = 3, device: int = 0, batch=None):
+    """The pivot part of the reference's `project_to_affine_space` (src/rounding.jl:184-211) for the system A x = b, `A` (nrows, ncols) and `b` (nrows,) or
+    (nrows, 1) of `Fraction`s or integers.  Every row of [A b] is cleared of denominators (multiplied by the least common multiple of its denominators, b
+    included: preprocess_rows!(include_b = true); the rows of A alone likewise for the second call), `pivots = find_pivots_modular([A b])`; the system is
+    inconsistent when the last pivot is the column of b (an empty pivot list counts as consistent); when there are fewer pivots than rows,
+    `rows = find_pivots_modular(transpose(A[:, pivots]))`, a set of independent rows, otherwise all rows.  Returns `(pivots, rows, consistent)`, 0-based
+    `PivotList`s (`rows` of an inconsistent system is every row)."""
+    A = np.asarray(A, dtype=object)
+    if A.ndim != 2:
+        raise ValueError(f"system_pivots: A must be two-dimensional, got shape {A.shape}")
+    nrows, ncols = A.shape
+    b = np.asarray(b, dtype=object).reshape(-1)
+    if b.size != nrows:
+        raise ValueError(f"system_pivots: b must have one entry per row of A, got {b.size} for {nrows} rows")
+    rows_of_A = [[Fraction(v) for v in A[r]] for r in range(nrows)]
+    Ab = _rows_cleared_of_denominators([rows_of_A[r] + [Fraction(b[r])] for r in range(nrows)]) if nrows else np.zeros((0, ncols + 1), dtype=object)
+    pivots = find_pivots_modular(Ab, maxprimes=maxprimes, device=device, batch=batch)
+    every_row = PivotList(range(nrows))
+    if len(pivots) and pivots[-1] == ncols:
+        return pivots, every_row, False
+    if len(pivots) == nrows:
+        return pivots, every_row, True
+    Ai = _rows_cleared_of_denominators(rows_of_A)                  # (the reference's A at that point: rows cleared of the denominators of A alone)
+    rows = find_pivots_modular(Ai[:, list(pivots)].T, maxprimes=maxprimes, device=device, batch=batch)
+    return pivots, rows, True

@@ -387,7 +387,14 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   Further outputs, in the layout of V (block b at its offset, n[b] x count[b] column-major; what the vectors do not cover is left as passed in): num, den
  *   ([plane]), status ([plane]), Vq ([limbs][plane]: the rounded vectors num / den), and round_resid_max ([sum n], the layout of resid_max): per vector
  *   max_i |head (Y_b Vq_b)[i, v]|, the product again by the kernel of clrs_mw_gemm.  CLRS_ERR_INVALID as for clrs_mw_kernel_vectors, and for
- *   round_errbound <= 0 (or NaN) or a null output. */
+ *   round_errbound <= 0 (or NaN) or a null output.
+ * clrs_modp_rref: the reduced row-echelon form of a matrix over the field of integers mod a prime p, 2 <= p < 2^23 (what the reference's
+ *   find_pivots_modular asks of Nemo.rref, src/rounding.jl:313-333), host pointers, no context.  A: nrows x ncols row-major, residues in [0, p).  pivots has
+ *   capacity min(nrows, ncols): its first *rank entries receive the 0-based pivot columns, ascending; the entries behind them stay as passed in.  R, where not
+ *   null, receives the reduced row-echelon form (row-major, residues in [0, p), the pivot rows first in pivot order, rows >= *rank zero).  The arithmetic is
+ *   exact, so the result is the unique reduced row-echelon form and reproducible bit for bit.  An empty matrix gives *rank = 0 and touches nothing else.
+ *   CLRS_ERR_INVALID before anything is allocated or launched: a negative size, nrows * ncols >= 2^31, p < 2, p >= 2^23 or p composite, a null A, pivots or
+ *   rank with a non-empty matrix, a residue outside [0, p).  Every device buffer is released on every path. */
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
 int clrs_mw_rank_reveal(int device, int limbs, int nmat, const int32_t *n, const int32_t *ncand, const double *G, const double *tau, int32_t *perm, int32_t *rank,
@@ -406,6 +413,7 @@ int clrs_mw_kernel_vectors_rational(int device, int limbs, int nblk, const int32
                                     double dual_max, double round_errbound, int32_t *branch, int32_t *perm, int32_t *rank, int32_t *count, double *V,
                                     double *resid_max, double *v_max, double *pivot_resid, double *num, double *den, int32_t *status, double *Vq,
                                     double *round_resid_max);
+int clrs_modp_rref(int device, int nrows, int ncols, int p, const int32_t *A, int32_t *pivots, int32_t *rank, int32_t *R);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 

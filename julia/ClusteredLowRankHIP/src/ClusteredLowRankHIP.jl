@@ -717,6 +717,55 @@ function rationalize(v::AbstractVector{BigFloat}; prec::Integer=precision(BigFlo
     return [status[i] == 0 ? BigInt(num[i]) // BigInt(den[i]) : big(0) // big(1) for i in 1:cnt], status[1:cnt]
 end
 
+"""
+    find_pivots_modular(A::AbstractMatrix{<:Integer}, p::Integer; device=0)
+    find_pivots_modular(A::AbstractMatrix{<:Integer}; maxprimes=3, device=0)
+
+The reference's `find_pivots_modular` (src/rounding.jl:288-333), the first work of `project_to_affine_space`: the pivot columns (1-based, ascending) of the
+reduced row-echelon form of `A` over the integers mod the prime `p`, 2 <= p < 2^23, on the device (`clrs_modp_rref`, DESIGN.md section 14).  `A` is reduced
+mod `p` on the host, so its entries may be `BigInt`s.  Without `p` the reference's schedule: `p = min(maximum(abs.(A)), 10^4)`, per round `p = next_prime(p)`;
+the first list with `size(A, 1)` pivots is returned, after `maxprimes` rounds the first of the longest lists.  An empty matrix gives `Int[]`;
+`maxprimes < 1` is an `ArgumentError`.
+"""
+function find_pivots_modular(A::AbstractMatrix{<:Integer}, p::Integer; device::Integer=0)
+    nr, nc = size(A)
+    (nr == 0 || nc == 0) && return Int[]
+    res = Matrix{Int32}(undef, nc, nr)                      # row-major for the library: the transpose, column-major
+    for i in 1:nr, j in 1:nc
+        res[j, i] = Int32(mod(A[i, j], p))
+    end
+    pivots = zeros(Int32, min(nr, nc)); rank = zeros(Int32, 1)
+    check(ccall((:clrs_modp_rref, libclrs[]), Cint,
+                (Cint, Cint, Cint, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                device, nr, nc, p, res, pivots, rank, Ptr{Int32}(C_NULL)))
+    return Int[Int(pivots[t]) + 1 for t in 1:rank[1]]
+end
+
+# the smallest prime strictly above x (trial division: the schedule stays near 10^4)
+function next_prime_above(x::Integer)
+    n = max(x + 1, 2)
+    while any(n % d == 0 for d in 2:isqrt(n))
+        n += 1
+    end
+    return n
+end
+
+function find_pivots_modular(A::AbstractMatrix{<:Integer}; maxprimes::Integer=3, device::Integer=0)
+    maxprimes >= 1 || throw(ArgumentError("find_pivots_modular: maxprimes must be at least 1, got $maxprimes"))
+    isempty(A) && return Int[]
+    prime = Int(min(maximum(abs, A), 10^4))
+    best = nothing                                          # the longest list so far; a later list replaces it only when strictly longer
+    for _ in 1:maxprimes
+        prime = next_prime_above(prime)
+        cols = find_pivots_modular(A, prime; device=device)
+        length(cols) == size(A, 1) && return cols           # one pivot per row: nothing longer exists
+        if best === nothing || length(cols) > length(best)
+            best = cols
+        end
+    end
+    return best
+end
+
 # `ClusteredLowRankHIP.Optimizer`: the MOI optimizer type lives in the package extension (ext/ClusteredLowRankHIPMOIExt.jl, loaded with
 # MathOptInterface), which registers it here; JuMP takes any callable that returns an optimizer: `GenericModel{BigFloat}(ClusteredLowRankHIP.Optimizer)`
 const OPTIMIZER_TYPE = Ref{Any}(nothing)
