@@ -16,6 +16,7 @@
 //   k_modp_gather  R[j, :] = A[pivot row j, :] as int32, rows >= rank zero.
 //
 // The host reads k and the pivot columns after each panel and stops when the columns are exhausted or rank == nrows (the trailing columns are then final).
+// The panel loop is modp_eliminate, on a matrix already on the device; clrs_modp_rref is its caller, and so is clrs_modp_dixon_lift (clrs_modp_lift.hip.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -249,38 +250,21 @@ struct ModpBufs {                      // every device buffer of a call, release
 };
 }  // namespace
 
-extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int32_t *A, int32_t *pivots, int32_t *rank, int32_t *R) {
-    if (nrows < 0 || ncols < 0) return modp_fail(CLRS_ERR_INVALID, "modp_rref: negative size");
-    if ((long long)nrows * (long long)ncols >= (1ll << 31)) return modp_fail(CLRS_ERR_INVALID, "modp_rref: nrows * ncols must be below 2^31");
-    if (p < 2 || p >= (1 << MODP_MAX_PRIME_BITS) || !modp_is_prime(p)) return modp_fail(CLRS_ERR_INVALID, "modp_rref: p must be a prime with 2 <= p < 2^23");
-    const size_t count = (size_t)nrows * (size_t)ncols;
-    if (count == 0) {
-        if (rank) *rank = 0;
-        return 0;
-    }
-    if (!A || !pivots || !rank) return modp_fail(CLRS_ERR_INVALID, "modp_rref: null argument");
-    for (size_t o = 0; o < count; o++)
-        if (A[o] < 0 || A[o] >= p) return modp_fail(CLRS_ERR_INVALID, "modp_rref: a residue outside [0, p)");
-    MODPCHECK(hipSetDevice(device));
-    ModpBufs bufs;
-    int32_t *d_I = nullptr;
-    double *d_A = nullptr, *d_P = nullptr, *d_Mn = nullptr, *d_G = nullptr, *d_U = nullptr;
-    int *d_flag = nullptr, *d_info = nullptr, *d_order = nullptr;
-    MODPCHECK(bufs.get(&d_I, count)); MODPCHECK(bufs.get(&d_A, count));
+// The elimination itself, on a matrix of fp64 residues already on the device (row-major, nrows x ncols), which it leaves there in reduced form: pivots are
+// sought in the columns below `pcols` only (pcols = ncols: the reduced row-echelon form; pcols < ncols: the columns behind are carried along, as the
+// identity beside A is for an inverse, clrs_modp_lift.hip.h).  `found` receives the pivot columns, ascending; *d_flag_out the device array of flag[i]
+// (-1 or the position of row i among the pivot rows).  The workspaces come from `bufs`.  Synchronises once per panel; work may still be in flight on return.
+static int modp_eliminate(double *d_A, int nrows, int ncols, int pcols, int p, ModpBufs &bufs, int **d_flag_out, std::vector<int32_t> &found) {
+    double *d_P = nullptr, *d_Mn = nullptr, *d_G = nullptr, *d_U = nullptr;
+    int *d_flag = nullptr, *d_info = nullptr;
     MODPCHECK(bufs.get(&d_P, (size_t)nrows * MODP_W)); MODPCHECK(bufs.get(&d_Mn, (size_t)nrows * MODP_W));
     MODPCHECK(bufs.get(&d_G, (size_t)MODP_W * MODP_W)); MODPCHECK(bufs.get(&d_U, (size_t)MODP_W * ncols));
-    MODPCHECK(bufs.get(&d_flag, (size_t)nrows)); MODPCHECK(bufs.get(&d_info, (size_t)1 + 2 * MODP_W)); MODPCHECK(bufs.get(&d_order, (size_t)nrows));
-    MODPCHECK(hipMemcpy(d_I, A, count * sizeof(int32_t), hipMemcpyHostToDevice));
+    MODPCHECK(bufs.get(&d_flag, (size_t)nrows)); MODPCHECK(bufs.get(&d_info, (size_t)1 + 2 * MODP_W));
     MODPCHECK(hipMemset(d_flag, 0xff, (size_t)nrows * sizeof(int)));
-    const unsigned flat = (unsigned)std::min<size_t>((count + MODP_NT - 1) / MODP_NT, 65536);
-    hipLaunchKernelGGL(k_modp_widen, dim3(flat), dim3(MODP_NT), 0, nullptr, d_I, d_A, count);
-    MODPCHECK(hipGetLastError());
-    MODPCHECK(bufs.drop(d_I));                                // the int32 copy is needed again only for R: 8 bytes per entry during the elimination, not 12
-    d_I = nullptr;
-    std::vector<int32_t> found;
+    *d_flag_out = d_flag;
     int rk = 0, info[1 + 2 * MODP_W];
-    for (int c0 = 0; c0 < ncols && rk < nrows; c0 += MODP_W) {
-        const int w = std::min(MODP_W, ncols - c0), c1 = c0 + w;
+    for (int c0 = 0; c0 < pcols && rk < nrows; c0 += MODP_W) {
+        const int w = std::min(MODP_W, pcols - c0), c1 = c0 + w;
         hipLaunchKernelGGL(k_modp_panel, dim3(1), dim3(MODP_PANEL_NT), 0, nullptr, d_A, nrows, ncols, c0, w, rk, p, d_P, d_flag, d_Mn, d_G, d_info);
         MODPCHECK(hipGetLastError());
         MODPCHECK(hipMemcpy(info, d_info, sizeof(info), hipMemcpyDeviceToHost));          // (synchronises: the pivot count decides what follows)
@@ -299,8 +283,39 @@ extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int
         }
         rk += k;
     }
+    return 0;
+}
+
+extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int32_t *A, int32_t *pivots, int32_t *rank, int32_t *R) {
+    if (nrows < 0 || ncols < 0) return modp_fail(CLRS_ERR_INVALID, "modp_rref: negative size");
+    if ((long long)nrows * (long long)ncols >= (1ll << 31)) return modp_fail(CLRS_ERR_INVALID, "modp_rref: nrows * ncols must be below 2^31");
+    if (p < 2 || p >= (1 << MODP_MAX_PRIME_BITS) || !modp_is_prime(p)) return modp_fail(CLRS_ERR_INVALID, "modp_rref: p must be a prime with 2 <= p < 2^23");
+    const size_t count = (size_t)nrows * (size_t)ncols;
+    if (count == 0) {
+        if (rank) *rank = 0;
+        return 0;
+    }
+    if (!A || !pivots || !rank) return modp_fail(CLRS_ERR_INVALID, "modp_rref: null argument");
+    for (size_t o = 0; o < count; o++)
+        if (A[o] < 0 || A[o] >= p) return modp_fail(CLRS_ERR_INVALID, "modp_rref: a residue outside [0, p)");
+    MODPCHECK(hipSetDevice(device));
+    ModpBufs bufs;
+    int32_t *d_I = nullptr;
+    double *d_A = nullptr;
+    int *d_flag = nullptr, *d_order = nullptr;
+    MODPCHECK(bufs.get(&d_I, count)); MODPCHECK(bufs.get(&d_A, count));
+    MODPCHECK(hipMemcpy(d_I, A, count * sizeof(int32_t), hipMemcpyHostToDevice));
+    const unsigned flat = (unsigned)std::min<size_t>((count + MODP_NT - 1) / MODP_NT, 65536);
+    hipLaunchKernelGGL(k_modp_widen, dim3(flat), dim3(MODP_NT), 0, nullptr, d_I, d_A, count);
+    MODPCHECK(hipGetLastError());
+    MODPCHECK(bufs.drop(d_I));                                // the int32 copy is needed again only for R: 8 bytes per entry during the elimination, not 12
+    d_I = nullptr;
+    std::vector<int32_t> found;
+    const int code = modp_eliminate(d_A, nrows, ncols, ncols, p, bufs, &d_flag, found);
+    if (code != 0) return code;
+    const int rk = (int)found.size();
     if (R) {
-        MODPCHECK(bufs.get(&d_I, count));
+        MODPCHECK(bufs.get(&d_I, count)); MODPCHECK(bufs.get(&d_order, (size_t)nrows));
         hipLaunchKernelGGL(k_modp_order, dim3((unsigned)(((long long)nrows + MODP_NT - 1) / MODP_NT)), dim3(MODP_NT), 0, nullptr, d_flag, nrows, d_order);
         MODPCHECK(hipGetLastError());
         hipLaunchKernelGGL(k_modp_gather, dim3(flat), dim3(MODP_NT), 0, nullptr, d_A, nrows, ncols, rk, d_order, d_I);
@@ -312,3 +327,5 @@ extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int
     *rank = rk;
     return 0;
 }
+
+#include "clrs_modp_lift.hip.h"      // clrs_modp_dixon_lift: the inverse mod p by the elimination above, then the p-adic lifting loop

@@ -15,6 +15,10 @@ transformations, the exact solve) is exact arithmetic and stays with the caller.
 The next fixed-width step of the pipeline is the first work of `project_to_affine_space` (src/rounding.jl:182-211): "Finding the pivots of A using RREF mod p"
 (`find_pivots_modular`, src/rounding.jl:288-333), a reduced row-echelon form of the integer system [A b] over the integers mod a prime of about 10^4.  It runs
 on the device (clrs_modp_rref): `rref_mod_p`, `find_pivots_modular`, `system_pivots`.
+
+The rest of `project_to_affine_space` (src/rounding.jl:213-286, 336-364) is the exact solve of the integer system, the reference's `Nemo._solve_dixon`: Dixon's
+p-adic lifting, on the device (clrs_modp_dixon_lift): `dixon_lift`, `solve_dixon`, `solve_system_pseudoinverse`,
+`project_to_affine_space`.  The rational reconstruction and the products around the solve are exact host arithmetic in Python integers.
 """
 from __future__ import annotations
 
@@ -27,7 +31,9 @@ import numpy as np
 from . import _lib
 
 __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vectors", "kernel_vectors_batch", "kernel_vectors_rational_batch", "rationalize",
-           "vectors_to_mp", "vectors_to_fractions", "rref_mod_p", "next_prime", "find_pivots_modular", "system_pivots", "PivotList"]
+           "vectors_to_mp", "vectors_to_fractions", "rref_mod_p", "next_prime", "find_pivots_modular", "system_pivots", "PivotList", "to_balanced_digits", "from_balanced_digits",
+           "prev_prime", "dixon_steps", "dixon_lift", "rational_reconstruction", "SingularSystemError", "DixonSolution", "solve_dixon",
+           "solve_system_pseudoinverse", "project_to_affine_space"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -36,10 +42,17 @@ LIMBS = (4, 5, 6, 8, 10)
 
 @dataclasses.dataclass
 class RoundingSettings:
-    """The kernel fields of the reference's RoundingSettings (src/rounding.jl:4-10, 60-62) with its defaults."""
+    """The kernel and pseudoinverse fields of the reference's RoundingSettings (src/rounding.jl:4-10, 23-25, 57-62) with its defaults."""
     kernel_errbound: float = 1e-10          # pivots / residuals below this are zero
     kernel_round_errbound: float = 1e-15    # the dual block is used while max |X_b| <= 1 / sqrt(this)
     kernel_use_dual: bool = True
+    pseudo: bool = True                     # solve through the pseudoinverse of a few more columns than rows (src/rounding.jl:23, 213)
+    pseudo_columnfactor: float = 1.05       # that many columns per row; at least 1 (src/rounding.jl:60-62)
+    extracolumns_linindep: bool = False     # take the extra columns linearly independent of each other instead of at random
+
+    def __post_init__(self):
+        if self.pseudo_columnfactor < 1:
+            self.pseudo_columnfactor = 1
 
 
 class KernelVectorError(ValueError):
@@ -408,3 +421,338 @@ def system_pivots(A, b, maxprimes: int = 3, device: int = 0, batch=None):
     Ai = _rows_cleared_of_denominators(rows_of_A)                  # (the reference's A at that point: rows cleared of the denominators of A alone)
     rows = find_pivots_modular(Ai[:, list(pivots)].T, maxprimes=maxprimes, device=device, batch=batch)
     return pivots, rows, True
+
+
+# ---- the exact solve: Dixon's p-adic lifting (src/rounding.jl:213-286, 336-364; clrs_modp_dixon_lift) -------------------------------------
+DIGIT_BITS = 24                      # integers cross the C boundary in balanced base-2^24 digits, every digit in [-2^23, 2^23)
+DIXON_FIRST_PRIME = 8388593          # the largest prime below 2^23: the fewest steps
+LIFT_MAX_N = 32767
+
+
+def to_balanced_digits(values, count: Optional[int] = None) -> np.ndarray:
+    """Python integers of any size (anything `np.asarray` takes, any shape) -> balanced base-2^24 digits, little-endian: int32 (count, *shape), every
+    digit `d = ((v + 2^23) mod 2^24) - 2^23`, then `v <- (v - d) / 2^24`.  `count=None`: as many digits as the largest value needs (at least one);
+    otherwise `ValueError` when a value does not fit."""
+    a = np.asarray(values)
+    if a.dtype != object and a.dtype.kind not in "iu":
+        if a.size:
+            raise ValueError(f"to_balanced_digits: the values must be integers, got dtype {a.dtype}")
+        a = a.astype(np.int64)
+    half, base = 1 << (DIGIT_BITS - 1), 1 << DIGIT_BITS
+    small = a.dtype != object and (a.size == 0 or _max_abs(a) < 1 << 62)
+    v = a.astype(np.int64) if small else np.array([int(t) for t in a.flat], dtype=object).reshape(a.shape)
+    planes = []
+    while True:
+        d = ((v + half) & (base - 1)) - half if small else np.array([((int(t) + half) % base) - half for t in v.flat], dtype=object).reshape(a.shape)
+        planes.append(np.asarray(d, dtype=np.int64).astype(np.int32))
+        v = (v - d) >> DIGIT_BITS if small else np.array([(int(t) - int(e)) >> DIGIT_BITS for t, e in zip(v.flat, d.flat)], dtype=object).reshape(a.shape)
+        done = not np.any(v != 0)
+        if (count is None and done) or (count is not None and len(planes) == int(count)):
+            break
+    if not done:
+        raise ValueError(f"to_balanced_digits: a value does not fit in {count} balanced digits of {DIGIT_BITS} bits")
+    return np.ascontiguousarray(np.stack(planes))
+
+
+def from_balanced_digits(planes) -> np.ndarray:
+    """Digit planes (count, *shape) -> the integers `sum_l planes[l] 2^(24 l)` as Python integers (an object array of shape `shape`)."""
+    planes = np.asarray(planes)
+    out = np.zeros(planes.shape[1:], dtype=object)
+    for l in range(planes.shape[0] - 1, -1, -1):
+        out = out * (1 << DIGIT_BITS) + planes[l].astype(object)
+    return out
+
+
+def prev_prime(x) -> int:
+    """The largest prime strictly below `x` (`ValueError` for x <= 2)."""
+    n = int(x) - 1
+    while n >= 2 and not _is_prime(n):
+        n -= 1
+    if n < 2:
+        raise ValueError(f"prev_prime: there is no prime below {x}")
+    return n
+
+
+def _isqrt(v: int) -> int:
+    from math import isqrt
+    return isqrt(v)
+
+
+def _object_vector(values) -> np.ndarray:
+    """a list -> a one-dimensional object array, whatever the entries are"""
+    out = np.empty(len(values), dtype=object)
+    out[:] = values
+    return out
+
+
+def _square_system(A, b, what):
+    """(A, b) -> an object matrix (n, n) and an object vector (n,) of Python integers"""
+    A = _integer_matrix(A, what)
+    if A.shape[0] != A.shape[1]:
+        raise ValueError(f"{what}: A must be square, got {A.shape}")
+    n = A.shape[0]
+    bm = np.asarray(b)
+    bv = _integer_matrix(bm.reshape(-1, 1), what).reshape(-1) if bm.size else np.zeros(0, dtype=np.int64)
+    if bv.size != n:
+        raise ValueError(f"{what}: b must have one entry per row of A, got {bv.size} for {n} rows")
+    return (np.array([int(v) for v in A.flat], dtype=object).reshape(n, n) if n else np.zeros((0, 0), dtype=object),
+            _object_vector([int(v) for v in bv.flat]))
+
+
+def dixon_steps(A, b, p: int):
+    """The number of lifting steps and the reconstruction bounds for the integer system A x = b at the prime p: `(K, N, D)` with
+    `D2 = prod_c max(sum_r A[r, c]^2, 1)` (Hadamard), `N2 = D2 max(sum b^2, 1)` (Cramer), `N = isqrt(N2) + 1`, `D = isqrt(D2) + 1` -- every entry of the
+    solution has |numerator| <= N and denominator <= D -- and K the smallest integer with `p^(2K) > 4 N2 D2`."""
+    A, b = _square_system(A, b, "dixon_steps")
+    p = int(p)
+    if p < 2:
+        raise ValueError(f"dixon_steps: p must be at least 2, got {p}")
+    D2 = 1
+    for c in range(A.shape[0]):
+        D2 *= max(sum(int(v) * int(v) for v in A[:, c]), 1)
+    N2 = D2 * max(sum(int(v) * int(v) for v in b), 1)
+    bound = 4 * N2 * D2
+    K = max(int((bound.bit_length() - 1) // (2 * p.bit_length())), 0)            # p^(2K) < 2^(2K bits(p)) <= bound: no larger than the answer
+    q = p ** (2 * K)
+    while q <= bound:
+        q *= p * p
+        K += 1
+    return K, _isqrt(N2) + 1, _isqrt(D2) + 1
+
+
+def _dixon_lift_digits(Ad, bl, p: int, steps: int, device: int = 0):
+    """One call of clrs_modp_dixon_lift on digit planes: `Ad` int32 (nd, n, n), `bl` int32 (nbl, n).  Returns `(X, r_limbs, info)`: X int32 (steps, n),
+    r_limbs int32 (nrl, n), info int32 (4,)."""
+    Ad, bl = np.ascontiguousarray(Ad, dtype=np.int32), np.ascontiguousarray(bl, dtype=np.int32)
+    nd, n, nbl, steps = Ad.shape[0], Ad.shape[1], bl.shape[0], int(steps)
+    if Ad.ndim != 3 or Ad.shape[2] != n or bl.shape != (nbl, n):
+        raise ValueError(f"dixon_lift: the digits of A must be (nd, n, n) and the limbs of b (nbl, n), got {Ad.shape} and {bl.shape}")
+    nrl = max(nbl, nd + 1) + 1
+    X = np.zeros((max(steps, 0), n), np.int32)
+    r = np.zeros((nrl, n), np.int32)
+    info = np.zeros(4, np.int32)
+    ptr = lambda a: a.ctypes.data_as(_lib.p_i32) if a.size else C_NULL_I32
+    _lib.check(_lib.load().clrs_modp_dixon_lift(int(device), n, int(p), nd, ptr(Ad), nbl, ptr(bl), steps, ptr(X), ptr(r), ptr(info)))
+    return X, r, info
+
+
+def dixon_lift(A, b, p: int, steps: int, device: int = 0):
+    """`steps` steps of Dixon's p-adic lifting of the integer system A x = b (A n x n, Python integers of any size) on the device: one call of
+    clrs_modp_dixon_lift.  `C = A^-1 mod p`, `r_0 = b`, `x_k = C (r_k mod p) mod p`, `r_{k+1} = (r_k - A x_k) / p`.  Returns `(X, r, rank)`: X int32
+    (steps, n) with the x_k, residues in [0, p); r (n,) the last residual as Python integers, so that `A sum_k X[k] p^k == b - p^steps r`; rank the rank of
+    A mod p.  When rank < n nothing was lifted and X and r are None."""
+    A, b = _square_system(A, b, "dixon_lift")
+    n, p, steps = A.shape[0], int(p), int(steps)
+    if p < 2 or p >= MODP_PRIME_LIMIT or not _is_prime(p):
+        raise ValueError(f"dixon_lift: p must be a prime with 2 <= p < 2^23, got {p}")
+    if n > LIFT_MAX_N or steps < 0:
+        raise ValueError(f"dixon_lift: n must be at most {LIFT_MAX_N} and steps at least 0, got n = {n}, steps = {steps}")
+    Ad = to_balanced_digits(A) if n else np.zeros((1, 0, 0), np.int32)
+    bl = to_balanced_digits(b) if n else np.zeros((1, 0), np.int32)
+    X, r, info = _dixon_lift_digits(Ad, bl, p, steps, device=device)
+    rank = int(info[0])
+    if rank < n:
+        return None, None, rank
+    return X, from_balanced_digits(r), rank
+
+
+def rational_reconstruction(a: int, m: int, N: int, D: int):
+    """The rational num / den with num = a den (mod m), |num| <= N and 0 < den <= D, by the half-extended Euclidean algorithm on (m, a mod m) stopped at the
+    first remainder <= N; `None` when that remainder's cofactor t does not satisfy 0 < |t| <= D or is not coprime to it.  Unique when m > 2 N D."""
+    from math import gcd
+    m, N, D = int(m), int(N), int(D)
+    r0, r1, t0, t1 = m, int(a) % m, 0, 1
+    while r1 > N:
+        q = r0 // r1
+        r0, r1, t0, t1 = r1, r0 - q * r1, t1, t0 - q * t1
+    if t1 == 0 or abs(t1) > D or gcd(r1, abs(t1)) != 1:
+        return None
+    return Fraction(r1, t1) if t1 > 0 else Fraction(-r1, -t1)
+
+
+class SingularSystemError(ValueError):
+    """The matrix of `solve_dixon` was singular mod every prime tried: it is singular, or `maxprimes` was too small (the reference: "The system is
+    rank-deficient", src/rounding.jl:250)."""
+
+
+class DixonSolution(list):
+    """The solution `solve_dixon` returns: a list of `Fraction`s with three attributes, `p` (the prime lifted at), `primes` (the primes tried, in order)
+    and `steps` (the lifting steps)."""
+    p: Optional[int]
+    primes: List[int]
+    steps: int
+
+    def __init__(self, values=(), p=None, primes=(), steps=0):
+        super().__init__(values)
+        self.p = None if p is None else int(p)
+        self.primes = [int(q) for q in primes]
+        self.steps = int(steps)
+
+
+def _fraction_rows(A, b, what):
+    """(A (nrows, ncols), b (nrows,) or (nrows, 1)) of integers or Fractions -> (rows of Fractions, list of Fractions, ncols)"""
+    A = np.asarray(A, dtype=object)
+    if A.size == 0:
+        A = A.reshape((A.shape[0], A.shape[1]) if A.ndim == 2 else (0, 0))
+    if A.ndim != 2:
+        raise ValueError(f"{what}: A must be two-dimensional, got shape {A.shape}")
+    b = np.asarray(b, dtype=object).reshape(-1)
+    if b.size != A.shape[0]:
+        raise ValueError(f"{what}: b must have one entry per row of A, got {b.size} for {A.shape[0]} rows")
+    return [[Fraction(v) for v in A[r]] for r in range(A.shape[0])], [Fraction(v) for v in b], A.shape[1]
+
+
+def solve_dixon(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True) -> DixonSolution:
+    """The exact solution of the square system A x = b (what the reference asks of `Nemo._solve_dixon`, src/rounding.jl:274, 351, 360): `A` (n, n) and `b`
+    (n,) or (n, 1) of integers or `Fraction`s.  Every row of [A b] is cleared of denominators; the primes are tried downward from 8388593, the largest
+    below 2^23 (the solution does not depend on the prime, and the largest needs the fewest steps), at most `maxprimes` of them, and the first at which A
+    has rank n is lifted `K = dixon_steps(A, b, p)[0]` steps; every entry is then reconstructed from `sum_k x_k p^k mod p^K`.  Returns a
+    `DixonSolution`.  Raises `SingularSystemError` when A is singular mod every prime tried, `ValueError` for `maxprimes < 1`, and, with `check`,
+    `ArithmeticError` unless `A x == b - p^K r_K` holds for the lifted integers and `A solution == b` for the fractions.
+    `lift(A, b, p, steps, device=...)` -> `(X, r, rank)` replaces the device call (default `dixon_lift`)."""
+    lift = dixon_lift if lift is None else lift
+    if int(maxprimes) < 1:
+        raise ValueError(f"solve_dixon: maxprimes must be at least 1, got {maxprimes}")
+    rows, bf, ncols = _fraction_rows(A, b, "solve_dixon")
+    n = len(rows)
+    if ncols != n:
+        raise ValueError(f"solve_dixon: A must be square, got {n} x {ncols}")
+    if n == 0:
+        return DixonSolution()
+    Ab = _rows_cleared_of_denominators([rows[r] + [bf[r]] for r in range(n)])
+    Ai, bi = Ab[:, :n], Ab[:, n]
+    p, primes = DIXON_FIRST_PRIME + 1, []
+    for _ in range(int(maxprimes)):
+        p = prev_prime(p)
+        primes.append(p)
+        K, N, D = dixon_steps(Ai, bi, p)
+        X, r, rank = lift(Ai, bi, p, K, device=device)
+        if rank == n:
+            break
+    else:
+        raise SingularSystemError(f"solve_dixon: the matrix is singular mod every prime tried ({primes})")
+    x = np.zeros(n, dtype=object)
+    for k in range(K - 1, -1, -1):                              # Horner: x = sum_k X[k] p^k
+        x = x * p + np.asarray(X[k]).astype(object)
+    m = p ** K
+    if check and any(int(v) != int(w) for v, w in zip(Ai.dot(x), bi - m * np.asarray(r, dtype=object))):
+        raise ArithmeticError(f"solve_dixon: A x != b - p^K r after {K} steps at p = {p}")
+    sol = [rational_reconstruction(int(v), m, N, D) for v in x]
+    if any(v is None for v in sol):
+        raise ArithmeticError(f"solve_dixon: entry {[v is None for v in sol].index(True)} has no rational reconstruction within the bounds")
+    if check and any(sum(rows[i][j] * sol[j] for j in range(n)) != bf[i] for i in range(n)):
+        raise ArithmeticError("solve_dixon: A solution != b")
+    return DixonSolution(sol, p, primes, K)
+
+
+def _gcd_of(values) -> int:
+    from math import gcd
+    g = 0
+    for v in values:
+        g = gcd(g, int(v))
+    return g if g else 1                                        # (a zero row or column: the matrix is singular, the solve says so)
+
+
+def solve_system_pseudoinverse(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True):
+    """The reference's `solve_system_pseudoinverse(A, b)` (src/rounding.jl:336-364): for `A` (nrows, ncols) with independent rows and more columns than rows
+    the minimum-norm solution `v = A^T (A A^T)^-1 b` of A v = b; otherwise (independent columns) `v = (A^T A)^-1 A^T b`.  A and b are first multiplied by the least
+    common multiple of the denominators of A so that the reference's gcds are gcds of integers; the Gram matrix is scaled on the right by `Dr = diag(1 / gcd(column))` and
+    then on the left by `Dl = diag(1 / gcd(row))` as there, solved by `solve_dixon` (to which `maxprimes`, `device`, `lift`, `check` go), and
+    `v = A^T (Dr y)` or `v = Dr y`.  All products are exact host arithmetic.  Returns a list of `Fraction`s; `SingularSystemError` when the Gram matrix is
+    singular."""
+    from math import gcd
+    rows, bf, ncols = _fraction_rows(A, b, "solve_system_pseudoinverse")
+    nrows = len(rows)
+    if nrows == 0 or ncols == 0:
+        return [Fraction(0)] * ncols
+    lcm = 1                                                     # one multiplier for the whole system: the least-squares solution is that of A, b
+    for row in rows:
+        for v in row:
+            lcm = lcm * v.denominator // gcd(lcm, v.denominator)
+    Ai = np.zeros((nrows, ncols), dtype=object)
+    for r, row in enumerate(rows):
+        Ai[r] = [int(v * lcm) for v in row]
+        bf[r] = bf[r] * lcm
+    bv = _object_vector(bf)
+    wide = ncols > nrows
+    G = Ai.dot(Ai.T) if wide else Ai.T.dot(Ai)
+    rhs = bv if wide else Ai.T.dot(bv)
+    k = G.shape[0]
+    dr = [_gcd_of(G[:, c]) for c in range(k)]
+    for c in range(k):
+        G[:, c] = [int(v) // dr[c] for v in G[:, c]]
+    dl = [_gcd_of(G[r]) for r in range(k)]
+    for r in range(k):
+        G[r] = [int(v) // dl[r] for v in G[r]]
+    y = solve_dixon(G, [Fraction(rhs[r]) / dl[r] for r in range(k)], maxprimes=maxprimes, device=device, lift=lift, check=check)
+    y = [y[c] / dr[c] for c in range(k)]
+    if not wide:
+        return y
+    return [sum((int(Ai[r, c]) * y[r] for r in range(nrows)), Fraction(0)) for c in range(ncols)]
+
+
+def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, rng=None, device: int = 0, batch=None, lift=None):
+    """The reference's `project_to_affine_space(A, b; settings)` (src/rounding.jl:182-286): a solution of A x = b, `A` (nrows, ncols) and `b` (nrows,) or
+    (nrows, 1) of `Fraction`s or integers.  Returns `(x, correct_slacks, finished)`, x a list of ncols `Fraction`s.
+
+    `system_pivots` gives the pivot columns and independent rows; an inconsistent system returns the zero vector, False, False.  With `settings.pseudo`:
+    the columns that are no pivots, shuffled by `rng` (a `numpy.random.Generator`, default `default_rng(0)`; the reference calls `shuffle`), are put behind
+    the pivots -- or, with `extracolumns_linindep`, rounds of `find_pivots_modular` on the shuffled remaining columns until there are
+    `pseudo_columnfactor * nrows` of them -- the list is cut at `round(pseudo_columnfactor * nrows)` columns, and those columns of the independent rows
+    are solved by `solve_system_pseudoinverse`; `correct_slacks = (A x == b)`.  When that solve meets a singular matrix (`SingularSystemError`; the
+    reference prints "The system is rank-deficient") or without `pseudo`: the pivot columns alone, by `solve_dixon` when they form a square system
+    (`correct_slacks = True`), through the normal equations otherwise (`correct_slacks = (A_piv^T A_piv x == A_piv^T b)`).  Indices are 0-based.
+    `batch` / `lift` replace the device calls of `find_pivots_modular` / `solve_dixon`."""
+    settings = RoundingSettings() if settings is None else settings
+    rng = np.random.default_rng(0) if rng is None else rng
+    rows_f, bf, ncols = _fraction_rows(A, b, "project_to_affine_space")
+    nrows = len(rows_f)
+    zero = [Fraction(0)] * ncols
+    if nrows == 0 or ncols == 0:
+        return zero, all(v == 0 for v in bf), True
+    pivots, rows, consistent = system_pivots(rows_f, bf, device=device, batch=batch)
+    if not consistent:
+        return zero, False, False
+    pivots, rows = [int(c) for c in pivots], [int(r) for r in rows]
+    residual_free = lambda x: all(sum((rows_f[r][c] * x[c] for c in range(ncols) if x[c] != 0), Fraction(0)) == bf[r] for r in range(nrows))
+    if settings.pseudo:
+        try:
+            if settings.extracolumns_linindep:
+                Ai = _rows_cleared_of_denominators(rows_f)
+                extracolumns = []
+                while sum(len(e) for e in extracolumns) + len(pivots) < settings.pseudo_columnfactor * nrows:
+                    taken = set(pivots).union(*extracolumns)
+                    nonpivots = [c for c in range(ncols) if c not in taken]
+                    if not nonpivots:
+                        break
+                    nonpivots = [int(c) for c in rng.permutation(nonpivots)]
+                    extra = find_pivots_modular(Ai[rows][:, nonpivots], device=device, batch=batch)
+                    if not len(extra):
+                        break                                   # (only zero columns are left; the reference would not end)
+                    extracolumns.append([nonpivots[t] for t in extra])
+            else:
+                in_pivots = set(pivots)
+                extracolumns = [[int(c) for c in rng.permutation([c for c in range(ncols) if c not in in_pivots])]]
+            subset = list(dict.fromkeys(pivots + [c for e in extracolumns for c in e]))
+            subset = subset[:min(len(subset), int(round(settings.pseudo_columnfactor * nrows)))]
+            newx = solve_system_pseudoinverse([[rows_f[r][c] for c in subset] for r in rows], [bf[r] for r in rows], device=device,
+                                              lift=lift)
+            x = list(zero)
+            for c, v in zip(subset, newx):
+                x[c] = v
+            return x, residual_free(x), True
+        except SingularSystemError:
+            pass                                                # the reference: "The system is rank-deficient"; the pivot system follows
+    Apiv = [[rows_f[r][c] for c in pivots] for r in range(nrows)]
+    nA, nb = Apiv, list(bf)
+    square = nrows == len(pivots)
+    if not square:                                              # the normal equations
+        k = len(pivots)
+        nb = [sum((Apiv[r][i] * bf[r] for r in range(nrows)), Fraction(0)) for i in range(k)]
+        nA = [[sum((Apiv[r][i] * Apiv[r][j] for r in range(nrows)), Fraction(0)) for j in range(k)] for i in range(k)]
+    newx = solve_dixon(nA, nb, device=device, lift=lift) if pivots else []
+    correct = True if square else all(sum((nA[i][j] * newx[j] for j in range(len(pivots))), Fraction(0)) == nb[i] for i in range(len(pivots)))
+    x = list(zero)
+    for j, c in enumerate(pivots):
+        x[c] = newx[j]
+    return x, correct, True

@@ -394,7 +394,17 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   null, receives the reduced row-echelon form (row-major, residues in [0, p), the pivot rows first in pivot order, rows >= *rank zero).  The arithmetic is
  *   exact, so the result is the unique reduced row-echelon form and reproducible bit for bit.  An empty matrix gives *rank = 0 and touches nothing else.
  *   CLRS_ERR_INVALID before anything is allocated or launched: a negative size, nrows * ncols >= 2^31, p < 2, p >= 2^23 or p composite, a null A, pivots or
- *   rank with a non-empty matrix, a residue outside [0, p).  Every device buffer is released on every path. */
+ *   rank with a non-empty matrix, a residue outside [0, p).  Every device buffer is released on every path.
+ * clrs_modp_dixon_lift: the p-adic lifting of Dixon's exact solve of the integer system A x = b, A n x n (what the reference asks of
+ *   Nemo._solve_dixon, src/rounding.jl:274, 351, 360), host pointers, no context.  Integers are balanced base-2^24 digits, little-endian, every digit in
+ *   [-2^23, 2^23): A_digits is [nd][n][n] (row-major planes), b_limbs [nbl][n].  On the device: C = A^-1 mod p (the elimination of clrs_modp_rref on
+ *   [A mod p | I]), r_0 = b, and `steps` times x_k = C (r_k mod p) mod p, r_{k+1} = (r_k - A x_k) / p, the division exact.  X ([steps][n]) receives the x_k,
+ *   residues in [0, p); r_limbs ([nrl][n], nrl = max(nbl, nd + 1) + 1) the last residual, so that A sum_k x_k p^k = b - p^steps r exactly.  info[0]: the rank
+ *   of A mod p; info[1]: the steps done, 0 when the rank is below n (then the call returns 0 with X and r_limbs untouched: the caller takes another prime),
+ *   else `steps`; info[2]: divisions that left a remainder; info[3]: residuals that left their limbs.  Either of the last two non-zero: CLRS_ERR_HIP (they
+ *   cannot be, for digits and limbs as described).  n = 0 returns at once with rank 0.  CLRS_ERR_INVALID before anything is allocated: n < 0 or n > 32767,
+ *   nd < 1, nbl < 1 (or more than 32767 limbs), steps < 0, p no prime in [2, 2^23), a digit outside [-2^23, 2^23), a null pointer with n > 0 (X may be null
+ *   when steps = 0).  Every device buffer is released on every path. */
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
 int clrs_mw_rank_reveal(int device, int limbs, int nmat, const int32_t *n, const int32_t *ncand, const double *G, const double *tau, int32_t *perm, int32_t *rank,
@@ -414,6 +424,8 @@ int clrs_mw_kernel_vectors_rational(int device, int limbs, int nblk, const int32
                                     double *resid_max, double *v_max, double *pivot_resid, double *num, double *den, int32_t *status, double *Vq,
                                     double *round_resid_max);
 int clrs_modp_rref(int device, int nrows, int ncols, int p, const int32_t *A, int32_t *pivots, int32_t *rank, int32_t *R);
+int clrs_modp_dixon_lift(int device, int n, int p, int nd, const int32_t *A_digits, int nbl, const int32_t *b_limbs, int steps, int32_t *X, int32_t *r_limbs,
+                         int32_t *info);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 

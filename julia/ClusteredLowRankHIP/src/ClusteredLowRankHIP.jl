@@ -13,12 +13,14 @@
 # results come back as limbs and are summed into the caller's Arb buffers (`arb_of`); the problem data cross the
 # boundary as 2 limbs (double-double).  `limbs = 1` selects the plain fp64 entry points (clrs_*), which cannot factor
 # the 2d = 30 sphere-packing problems (DESIGN.md section 2).
+# The exact solve of the rounding pipeline (`solve_dixon`, at the end of this file) takes and returns Nemo matrices.
 # This file cannot be executed in the build container (no Julia there); INTEGRATION.md is the contract and
 # tests/test_abi_cpu.py checks the struct below against include/clrs_hip.h.
 module ClusteredLowRankHIP
 
 using Libdl
 using Arblib
+import Nemo
 import ClusteredLowRankSolver
 const CLRS = ClusteredLowRankSolver
 
@@ -764,6 +766,98 @@ function find_pivots_modular(A::AbstractMatrix{<:Integer}; maxprimes::Integer=3,
         end
     end
     return best
+end
+
+# balanced base-2^24 digits, little-endian, every digit in [-2^23, 2^23): digit l of value i at out[i, l] (planar for the library: column-major)
+function balanced_digits(values::AbstractVector{BigInt}, count::Integer)
+    out = zeros(Int32, max(length(values), 1), count)
+    half, base = big(1) << 23, big(1) << 24
+    for (i, v0) in enumerate(values)
+        v = v0
+        for l in 1:count
+            d = mod(v + half, base) - half
+            out[i, l] = Int32(d)
+            v = (v - d) >> 24
+        end
+        v == 0 || error("balanced_digits: a value does not fit in $count digits")
+    end
+    return out
+end
+
+# digits enough for every value of this magnitude: c digits hold every |v| <= (2^23 - 1) (2^(24 c) - 1) / (2^24 - 1), all digits 2^23 - 1
+function digits_needed(maxabs::BigInt)
+    c = 1
+    while maxabs > (big(2)^23 - 1) * ((big(1) << (24 * c)) - 1) ÷ (big(2)^24 - 1)
+        c += 1
+    end
+    return c
+end
+
+# sum_l d[i, l] 2^(24 (l - 1))
+from_balanced_digits(d::AbstractMatrix{Int32}, i::Integer) = foldr((l, acc) -> (acc << 24) + d[i, l], 1:size(d, 2); init=big(0))
+
+# num // den with num = a den (mod m), |num| <= N, 0 < den <= D: the half-extended Euclidean algorithm on (m, a mod m), stopped at the first remainder <= N
+function rational_reconstruction(a::Nemo.ZZRingElem, m::Nemo.ZZRingElem, N::Nemo.ZZRingElem, D::Nemo.ZZRingElem)
+    r0, r1, t0, t1 = m, mod(a, m), Nemo.ZZ(0), Nemo.ZZ(1)
+    while r1 > N
+        q = div(r0, r1)
+        r0, r1, t0, t1 = r1, r0 - q * r1, t1, t0 - q * t1
+    end
+    (t1 == 0 || abs(t1) > D || gcd(r1, abs(t1)) != 1) && return nothing
+    return t1 > 0 ? Nemo.QQ(r1, t1) : Nemo.QQ(-r1, -t1)
+end
+
+"""
+    solve_dixon(A::ZZMatrix, b::ZZMatrix; maxprimes=3, device=0)
+
+The exact solution of the square integer system `A x = b` (`b` one column) as a `QQMatrix`: what the reference asks of `Nemo._solve_dixon`
+(src/rounding.jl:274, 351, 360), with the p-adic lifting on the device (`clrs_modp_dixon_lift`, DESIGN.md section 15).  The digits of `A` and `b` are built
+from `BigInt`s; the primes are tried downward from 8388593 (at most `maxprimes`) until `A` is invertible mod `p`; the number of steps is the smallest `K`
+with `p^(2K) > 4 N2 D2`, `D2 = prod_c max(sum_r A[r, c]^2, 1)`, `N2 = D2 max(sum b^2, 1)`; the entries are reconstructed from `sum_k x_k p^k mod p^K`
+with FLINT integers.  Throws an `ErrorException` ("The system is rank-deficient") when `A` is singular mod every prime tried.
+"""
+function solve_dixon(A::Nemo.ZZMatrix, b::Nemo.ZZMatrix; maxprimes::Integer=3, device::Integer=0)
+    n = Nemo.nrows(A)
+    (Nemo.ncols(A) == n && Nemo.nrows(b) == n && Nemo.ncols(b) == 1) || throw(ArgumentError("solve_dixon: A must be n x n and b n x 1"))
+    maxprimes >= 1 || throw(ArgumentError("solve_dixon: maxprimes must be at least 1, got $maxprimes"))
+    n == 0 && return Nemo.zero_matrix(Nemo.QQ, 0, 1)
+    Ab = BigInt[BigInt(A[i, j]) for i in 1:n for j in 1:n]              # row-major
+    bb = BigInt[BigInt(b[i, 1]) for i in 1:n]
+    nd = digits_needed(maximum(abs, Ab)); nbl = digits_needed(maximum(abs, bb))
+    Ad = balanced_digits(Ab, nd); bl = balanced_digits(bb, nbl)
+    D2 = prod(max(sum(Ab[(i - 1) * n + j]^2 for i in 1:n), big(1)) for j in 1:n)
+    N2 = D2 * max(sum(v^2 for v in bb), big(1))
+    N = Nemo.ZZ(isqrt(N2) + 1); D = Nemo.ZZ(isqrt(D2) + 1)
+    nrl = max(nbl, nd + 1) + 1
+    p = 8388594
+    for _ in 1:maxprimes
+        p -= 1
+        while any(p % d == 0 for d in 2:isqrt(p))
+            p -= 1
+        end
+        K = 0; q = big(1)
+        while q <= 4 * N2 * D2
+            q *= big(p)^2; K += 1
+        end
+        X = zeros(Int32, n, max(K, 1)); r = zeros(Int32, n, nrl); info = zeros(Int32, 4)
+        check(ccall((:clrs_modp_dixon_lift, libclrs[]), Cint,
+                    (Cint, Cint, Cint, Cint, Ptr{Int32}, Cint, Ptr{Int32}, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}),
+                    device, n, p, nd, Ad, nbl, bl, K, X, r, info))
+        info[1] == n || continue                                        # singular mod p: the next prime
+        m = Nemo.ZZ(big(p))^K
+        x = Nemo.zero_matrix(Nemo.QQ, n, 1)
+        for i in 1:n
+            v = Nemo.ZZ(0)
+            for k in K:-1:1                                             # Horner: sum_k X[i, k] p^(k - 1)
+                v = v * p + Int(X[i, k])
+            end
+            f = rational_reconstruction(v, m, N, D)
+            f === nothing && error("solve_dixon: entry $i has no rational reconstruction within the bounds")
+            x[i, 1] = f
+        end
+        return x
+    end
+    error("The system is rank-deficient")
 end
 
 # `ClusteredLowRankHIP.Optimizer`: the MOI optimizer type lives in the package extension (ext/ClusteredLowRankHIPMOIExt.jl, loaded with
