@@ -33,7 +33,7 @@ from . import _lib
 __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vectors", "kernel_vectors_batch", "kernel_vectors_rational_batch", "rationalize",
            "vectors_to_mp", "vectors_to_fractions", "rref_mod_p", "next_prime", "find_pivots_modular", "system_pivots", "PivotList", "to_balanced_digits", "from_balanced_digits",
            "prev_prime", "dixon_steps", "dixon_lift", "rational_reconstruction", "SingularSystemError", "DixonSolution", "solve_dixon",
-           "solve_system_pseudoinverse", "project_to_affine_space"]
+           "solve_system_pseudoinverse", "project_to_affine_space", "to_digits24", "from_digits24", "dixon_reconstruct"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -570,6 +570,79 @@ def rational_reconstruction(a: int, m: int, N: int, D: int):
     return Fraction(r1, t1) if t1 > 0 else Fraction(-r1, -t1)
 
 
+def to_digits24(value: int, count: Optional[int] = None) -> np.ndarray:
+    """The Python integer `value >= 0` -> its little-endian digits in [0, 2^24) as int32: as many as it needs (at least one), or `count` (`ValueError`
+    when it does not fit).  Linear in the digit count: `int.to_bytes`, then three bytes per digit."""
+    value = int(value)
+    if value < 0:
+        raise ValueError("to_digits24: the value must not be negative")
+    need = max((value.bit_length() + DIGIT_BITS - 1) // DIGIT_BITS, 1)
+    count = need if count is None else int(count)
+    if count < need:
+        raise ValueError(f"to_digits24: the value does not fit in {count} digits of {DIGIT_BITS} bits")
+    raw = np.frombuffer(value.to_bytes(3 * count, "little"), dtype=np.uint8).reshape(count, 3)
+    out = np.zeros((count, 4), np.uint8)
+    out[:, :3] = raw
+    return np.ascontiguousarray(out.view("<u4").reshape(count).astype(np.int32))
+
+
+def from_digits24(digits) -> list:
+    """Rows of little-endian digits in [0, 2^24) (int32, shape (count,) or (rows, count)) -> the Python integer of every row (an integer for one row given
+    as (count,), else a list).  Linear in the digit count: the three low bytes of every digit packed, then `int.from_bytes` (`from_balanced_digits` is a
+    Horner loop over the digits, quadratic)."""
+    d = np.ascontiguousarray(digits, dtype="<u4")
+    if d.size and int(d.max()) >= 1 << DIGIT_BITS:
+        raise ValueError("from_digits24: a digit outside [0, 2^24)")
+    rows = d.reshape(-1, d.shape[-1]) if d.ndim > 1 else d.reshape(1, -1)
+    packed = np.ascontiguousarray(rows.view(np.uint8).reshape(rows.shape[0], rows.shape[1], 4)[:, :, :3])
+    out = [int.from_bytes(packed[i].tobytes(), "little") for i in range(rows.shape[0])]
+    return out if d.ndim > 1 else out[0]
+
+
+def _coprime_fraction(num: int, den: int) -> Fraction:
+    """`Fraction(num, den)` for coprime num and den > 0 without the gcd of the constructor: `Fraction._from_coprime_ints` where the running Python has it
+    (3.12 and later), the constructor's `_normalize=False` before that."""
+    make = getattr(Fraction, "_from_coprime_ints", None)
+    return make(num, den) if make is not None else Fraction(num, den, _normalize=False)
+
+
+def dixon_reconstruct(X, p: int, N: int, D: int, device: int = 0, want_x: bool = False):
+    """The rational reconstruction of every entry of a lifted solution on the device, one call of clrs_modp_dixon_reconstruct: `X`
+    int32 (steps, n) as `dixon_lift` returns it, `x_i = sum_k X[k, i] p^k`, and per entry the half-extended Euclidean algorithm on `(p^steps, x_i)`
+    stopped at the first remainder <= N -- what `rational_reconstruction(x_i, p^steps, N, D)` computes, with the same result.  Returns a list of
+    `Fraction | None`; with `want_x` also the list of the integers x_i: `(fractions, x)`.  The digits come back as int32 and become Python integers by
+    `from_digits24` (linear).  Numerator and denominator arrive coprime (the device has tested it), so each `Fraction` is built without a second gcd:
+    by `Fraction._from_coprime_ints` on Python 3.12 and later, by `Fraction(num, den, _normalize=False)` before that.  The counters of the call are kept in
+    `dixon_reconstruct.last_info` (`[limbs of p^steps, most quotient steps of an entry, their total, 0]`)."""
+    X = np.ascontiguousarray(X, dtype=np.int32)
+    if X.ndim != 2:
+        raise ValueError(f"dixon_reconstruct: X must be (steps, n), got shape {X.shape}")
+    steps, n = X.shape
+    p, N, D = int(p), int(N), int(D)
+    if p < 2 or p >= MODP_PRIME_LIMIT or not _is_prime(p):
+        raise ValueError(f"dixon_reconstruct: p must be a prime with 2 <= p < 2^23, got {p}")
+    if steps < 1 or n > LIFT_MAX_N or N < 0 or D < 0:
+        raise ValueError(f"dixon_reconstruct: steps must be at least 1, n at most {LIFT_MAX_N} and the bounds not negative")
+    if n == 0:
+        return ([], []) if want_x else []
+    Nd, Dd = to_digits24(N), to_digits24(D)
+    nl = max(Nd.size, Dd.size)
+    nx = (steps * p.bit_length()) // DIGIT_BITS + 1              # p^steps < 2^(steps bits(p)): never fewer limbs than it has
+    num, den = np.zeros((n, nl), np.int32), np.zeros((n, nl), np.int32)
+    neg, status, info = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(4, np.int32)
+    xl = np.zeros((n, nx), np.int32) if want_x else None
+    ptr = lambda a: C_NULL_I32 if a is None else a.ctypes.data_as(_lib.p_i32)
+    _lib.check(_lib.load().clrs_modp_dixon_reconstruct(int(device), n, p, steps, ptr(X), Nd.size, ptr(Nd), Dd.size, ptr(Dd), nl, ptr(num), ptr(den), ptr(neg),
+                                                       ptr(status), nx, ptr(xl), ptr(info)))
+    dixon_reconstruct.last_info = [int(v) for v in info]
+    nums, dens = from_digits24(num), from_digits24(den)
+    out = [None if status[i] else _coprime_fraction(-nums[i] if neg[i] else nums[i], dens[i]) for i in range(n)]
+    return (out, from_digits24(xl)) if want_x else out
+
+
+dixon_reconstruct.last_info = None
+
+
 class SingularSystemError(ValueError):
     """The matrix of `solve_dixon` was singular mod every prime tried: it is singular, or `maxprimes` was too small (the reference: "The system is
     rank-deficient", src/rounding.jl:250)."""
@@ -602,14 +675,17 @@ def _fraction_rows(A, b, what):
     return [[Fraction(v) for v in A[r]] for r in range(A.shape[0])], [Fraction(v) for v in b], A.shape[1]
 
 
-def solve_dixon(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True) -> DixonSolution:
+def solve_dixon(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True, reconstruct=None) -> DixonSolution:
     """The exact solution of the square system A x = b (what the reference asks of `Nemo._solve_dixon`, src/rounding.jl:274, 351, 360): `A` (n, n) and `b`
     (n,) or (n, 1) of integers or `Fraction`s.  Every row of [A b] is cleared of denominators; the primes are tried downward from 8388593, the largest
     below 2^23 (the solution does not depend on the prime, and the largest needs the fewest steps), at most `maxprimes` of them, and the first at which A
     has rank n is lifted `K = dixon_steps(A, b, p)[0]` steps; every entry is then reconstructed from `sum_k x_k p^k mod p^K`.  Returns a
     `DixonSolution`.  Raises `SingularSystemError` when A is singular mod every prime tried, `ValueError` for `maxprimes < 1`, and, with `check`,
     `ArithmeticError` unless `A x == b - p^K r_K` holds for the lifted integers and `A solution == b` for the fractions.
-    `lift(A, b, p, steps, device=...)` -> `(X, r, rank)` replaces the device call (default `dixon_lift`)."""
+    `lift(A, b, p, steps, device=...)` -> `(X, r, rank)` replaces the device call (default `dixon_lift`).
+    `reconstruct(X, p, N, D, device=..., want_x=...)` -> the list of `Fraction | None` (with `want_x` also the integers `sum_k X[k] p^k`) replaces the
+    Horner loop and the per-entry `rational_reconstruction` on the host; `dixon_reconstruct` does both on the device.  With `check` the identity of the
+    lifted integers is then tested on the integers that `reconstruct` returned."""
     lift = dixon_lift if lift is None else lift
     if int(maxprimes) < 1:
         raise ValueError(f"solve_dixon: maxprimes must be at least 1, got {maxprimes}")
@@ -631,13 +707,20 @@ def solve_dixon(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: boo
             break
     else:
         raise SingularSystemError(f"solve_dixon: the matrix is singular mod every prime tried ({primes})")
-    x = np.zeros(n, dtype=object)
-    for k in range(K - 1, -1, -1):                              # Horner: x = sum_k X[k] p^k
-        x = x * p + np.asarray(X[k]).astype(object)
     m = p ** K
+    if reconstruct is None:
+        x = np.zeros(n, dtype=object)
+        for k in range(K - 1, -1, -1):                          # Horner: x = sum_k X[k] p^k
+            x = x * p + np.asarray(X[k]).astype(object)
+    elif check:
+        sol, x = reconstruct(X, p, N, D, device=device, want_x=True)
+        x = _object_vector([int(v) for v in x])
+    else:
+        sol, x = reconstruct(X, p, N, D, device=device, want_x=False), None
     if check and any(int(v) != int(w) for v, w in zip(Ai.dot(x), bi - m * np.asarray(r, dtype=object))):
         raise ArithmeticError(f"solve_dixon: A x != b - p^K r after {K} steps at p = {p}")
-    sol = [rational_reconstruction(int(v), m, N, D) for v in x]
+    if reconstruct is None:
+        sol = [rational_reconstruction(int(v), m, N, D) for v in x]
     if any(v is None for v in sol):
         raise ArithmeticError(f"solve_dixon: entry {[v is None for v in sol].index(True)} has no rational reconstruction within the bounds")
     if check and any(sum(rows[i][j] * sol[j] for j in range(n)) != bf[i] for i in range(n)):
@@ -653,11 +736,11 @@ def _gcd_of(values) -> int:
     return g if g else 1                                        # (a zero row or column: the matrix is singular, the solve says so)
 
 
-def solve_system_pseudoinverse(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True):
+def solve_system_pseudoinverse(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True, reconstruct=None):
     """The reference's `solve_system_pseudoinverse(A, b)` (src/rounding.jl:336-364): for `A` (nrows, ncols) with independent rows and more columns than rows
     the minimum-norm solution `v = A^T (A A^T)^-1 b` of A v = b; otherwise (independent columns) `v = (A^T A)^-1 A^T b`.  A and b are first multiplied by the least
     common multiple of the denominators of A so that the reference's gcds are gcds of integers; the Gram matrix is scaled on the right by `Dr = diag(1 / gcd(column))` and
-    then on the left by `Dl = diag(1 / gcd(row))` as there, solved by `solve_dixon` (to which `maxprimes`, `device`, `lift`, `check` go), and
+    then on the left by `Dl = diag(1 / gcd(row))` as there, solved by `solve_dixon` (to which `maxprimes`, `device`, `lift`, `check`, `reconstruct` go), and
     `v = A^T (Dr y)` or `v = Dr y`.  All products are exact host arithmetic.  Returns a list of `Fraction`s; `SingularSystemError` when the Gram matrix is
     singular."""
     from math import gcd
@@ -684,14 +767,15 @@ def solve_system_pseudoinverse(A, b, maxprimes: int = 3, device: int = 0, lift=N
     dl = [_gcd_of(G[r]) for r in range(k)]
     for r in range(k):
         G[r] = [int(v) // dl[r] for v in G[r]]
-    y = solve_dixon(G, [Fraction(rhs[r]) / dl[r] for r in range(k)], maxprimes=maxprimes, device=device, lift=lift, check=check)
+    y = solve_dixon(G, [Fraction(rhs[r]) / dl[r] for r in range(k)], maxprimes=maxprimes, device=device, lift=lift, check=check,
+                    reconstruct=reconstruct)
     y = [y[c] / dr[c] for c in range(k)]
     if not wide:
         return y
     return [sum((int(Ai[r, c]) * y[r] for r in range(nrows)), Fraction(0)) for c in range(ncols)]
 
 
-def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, rng=None, device: int = 0, batch=None, lift=None):
+def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, rng=None, device: int = 0, batch=None, lift=None, reconstruct=None):
     """The reference's `project_to_affine_space(A, b; settings)` (src/rounding.jl:182-286): a solution of A x = b, `A` (nrows, ncols) and `b` (nrows,) or
     (nrows, 1) of `Fraction`s or integers.  Returns `(x, correct_slacks, finished)`, x a list of ncols `Fraction`s.
 
@@ -702,7 +786,7 @@ def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, r
     are solved by `solve_system_pseudoinverse`; `correct_slacks = (A x == b)`.  When that solve meets a singular matrix (`SingularSystemError`; the
     reference prints "The system is rank-deficient") or without `pseudo`: the pivot columns alone, by `solve_dixon` when they form a square system
     (`correct_slacks = True`), through the normal equations otherwise (`correct_slacks = (A_piv^T A_piv x == A_piv^T b)`).  Indices are 0-based.
-    `batch` / `lift` replace the device calls of `find_pivots_modular` / `solve_dixon`."""
+    `batch` / `lift` replace the device calls of `find_pivots_modular` / `solve_dixon`; `reconstruct` goes to `solve_dixon` as it is."""
     settings = RoundingSettings() if settings is None else settings
     rng = np.random.default_rng(0) if rng is None else rng
     rows_f, bf, ncols = _fraction_rows(A, b, "project_to_affine_space")
@@ -736,7 +820,7 @@ def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, r
             subset = list(dict.fromkeys(pivots + [c for e in extracolumns for c in e]))
             subset = subset[:min(len(subset), int(round(settings.pseudo_columnfactor * nrows)))]
             newx = solve_system_pseudoinverse([[rows_f[r][c] for c in subset] for r in rows], [bf[r] for r in rows], device=device,
-                                              lift=lift)
+                                              lift=lift, reconstruct=reconstruct)
             x = list(zero)
             for c, v in zip(subset, newx):
                 x[c] = v
@@ -750,7 +834,7 @@ def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, r
         k = len(pivots)
         nb = [sum((Apiv[r][i] * bf[r] for r in range(nrows)), Fraction(0)) for i in range(k)]
         nA = [[sum((Apiv[r][i] * Apiv[r][j] for r in range(nrows)), Fraction(0)) for j in range(k)] for i in range(k)]
-    newx = solve_dixon(nA, nb, device=device, lift=lift) if pivots else []
+    newx = solve_dixon(nA, nb, device=device, lift=lift, reconstruct=reconstruct) if pivots else []
     correct = True if square else all(sum((nA[i][j] * newx[j] for j in range(len(pivots))), Fraction(0)) == nb[i] for i in range(len(pivots)))
     x = list(zero)
     for j, c in enumerate(pivots):

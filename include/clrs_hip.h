@@ -404,7 +404,19 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   else `steps`; info[2]: divisions that left a remainder; info[3]: residuals that left their limbs.  Either of the last two non-zero: CLRS_ERR_HIP (they
  *   cannot be, for digits and limbs as described).  n = 0 returns at once with rank 0.  CLRS_ERR_INVALID before anything is allocated: n < 0 or n > 32767,
  *   nd < 1, nbl < 1 (or more than 32767 limbs), steps < 0, p no prime in [2, 2^23), a digit outside [-2^23, 2^23), a null pointer with n > 0 (X may be null
- *   when steps = 0).  Every device buffer is released on every path. */
+ *   when steps = 0).  Every device buffer is released on every path.
+ * clrs_modp_dixon_reconstruct: the rational reconstruction of the entries of a lifted solution, host pointers, no context.  X
+ *   ([steps][n], residues in [0, p)) is what clrs_modp_dixon_lift returned; N_limbs (nN) and D_limbs (nD) are the bounds as little-endian digits in
+ *   [0, 2^24).  Per entry i, on the device: x_i = sum_k X[k][i] p^k by Horner, then the half-extended Euclidean algorithm on (m = p^steps, x_i) stopped at the
+ *   first remainder r <= N, with cofactor t (r = t x_i mod m).  Accepted (status[i] = 0) when 0 < |t| <= D and p does not divide both r and t (gcd(r, t)
+ *   is a power of p): the entry is sign(t) r / |t|, num ([n][nl]) holds the digits in [0, 2^24) of r, den ([n][nl]) those of |t|, neg[i] = 1 when the
+ *   numerator is negative.  Rejected (status[i] = 1): the rows of num and den are zero.  x_limbs, where not null, is [n][nx], nx >= the limbs of p^steps,
+ *   and receives the digits of x_i.  info[0]: the limbs of p^steps; info[1]: the largest number of quotient steps of an entry (a quotient is taken in pieces
+ *   of at most 24 bits, one step each); info[2]: their total, saturating at 2^31 - 1; info[3]: entries that met an impossibility (a negative remainder, a
+ *   cofactor past its row, steps without end): non-zero gives CLRS_ERR_HIP.  n = 0 returns at once.  CLRS_ERR_INVALID before anything is allocated: n < 0
+ *   or n > 32767, steps < 1 (or p^steps beyond 32767 limbs), p no prime in [2, 2^23), a null pointer (x_limbs may be null), nN, nD or nl outside
+ *   [1, 32767], a digit outside [0, 2^24), nl below the limbs of max(N, D), a residue outside [0, p), nx too small.  Every device buffer is released on every path.
+ * clrs_modp_dixon_reconstruct_times: the milliseconds the calling thread's last clrs_modp_dixon_reconstruct spent in its two kernels (Horner, Euclid). */
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
 int clrs_mw_rank_reveal(int device, int limbs, int nmat, const int32_t *n, const int32_t *ncand, const double *G, const double *tau, int32_t *perm, int32_t *rank,
@@ -426,6 +438,9 @@ int clrs_mw_kernel_vectors_rational(int device, int limbs, int nblk, const int32
 int clrs_modp_rref(int device, int nrows, int ncols, int p, const int32_t *A, int32_t *pivots, int32_t *rank, int32_t *R);
 int clrs_modp_dixon_lift(int device, int n, int p, int nd, const int32_t *A_digits, int nbl, const int32_t *b_limbs, int steps, int32_t *X, int32_t *r_limbs,
                          int32_t *info);
+int clrs_modp_dixon_reconstruct(int device, int n, int p, int steps, const int32_t *X, int nN, const int32_t *N_limbs, int nD, const int32_t *D_limbs, int nl,
+                                int32_t *num, int32_t *den, int32_t *neg, int32_t *status, int nx, int32_t *x_limbs, int32_t *info);
+int clrs_modp_dixon_reconstruct_times(double *horner_ms, double *euclid_ms);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 
