@@ -40,6 +40,7 @@ MW_KERNELS_ALL(extern template, 10)
 typedef long long i64;
 
 extern int g_cfg_mw_zi_narrow;        // clrs_hip.hip, clrs_config_set("mw_zi_narrow", 0 / 1)
+extern int g_cfg_mw_xinv_product;     // clrs_hip.hip, clrs_config_set("mw_xinv_product", 0 / 1)
 extern int g_cfg_mw_chain_hop, g_cfg_mw_skip_xfb, g_cfg_mw_y_riders;   // clrs_hip.hip, clrs_config_set("mw_chain_hop", 0 / 1 / 2), ("mw_skip_xfb", 0 / 1), ("mw_y_riders", 0 / 1)
 extern int g_cfg_mw_stream_words;                        // clrs_hip.hip, clrs_config_set("mw_stream_words", 0 / 1); env CLRS_MW_STREAM_WORDS
 extern int g_cfg_mw_pipeline64;                          // clrs_hip.hip, clrs_config_set("mw_pipeline64", 0 / 1): the 64-row form for clusters of 33 .. 64 rows
@@ -192,6 +193,7 @@ struct clrs_mw_ctx {
     bool y_riders = true;                // the iteration may form the Y pairings on the Cholesky launch (clrs_config_set("mw_y_riders", ..) when the context was created)
     const double *ride_y = nullptr;      // set by the iteration around its Cholesky of the X blocks: the Y of the assembly that follows, whose pairings ride on that launch
     bool zi_narrow = true;               // k_mwi_Zi with 256 threads and panels of half the width where clrs_mw_zi_panels.h allows it (clrs_config_set("mw_zi_narrow", ..) when the context was created)
+    bool xinv_product = true;            // k_mwi_Zi applies X^-1 as one product with Xv = Xi^T Xi, formed once per iteration (MwIpmDev::Xv; clrs_config_set("mw_xinv_product", ..) when the context was created)
     int chain_hop = 1;                   // form of the in-launch hand-offs of k_mwi_Zi / k_mwi_step (MwIpmDev::hop; clrs_config_set("mw_chain_hop", ..) when the context was created)
     bool refine_skip_next = false;       // the interior-point iteration's PREDICTOR solve: one pass (set by clrs_mw_ipm_host.inc for the next clrs_mw_schur_solve_dev only)
     int refine_predictor = 0;            // clrs_mw_options.refine_predictor: 1 = the predictor's solve is refined like every other
@@ -700,6 +702,7 @@ extern "C" int clrs_mw_create_opts(const clrs_sdp_desc *d, int data_limbs, int d
         c->chain_hop = std::min(std::max(g_cfg_mw_chain_hop, 0), 2);
         c->y_riders = g_cfg_mw_y_riders != 0;
         c->zi_narrow = g_cfg_mw_zi_narrow != 0;
+        c->xinv_product = g_cfg_mw_xinv_product != 0;
     }
     MW_RET(mw_stage_stream(c));
     MwTables t;

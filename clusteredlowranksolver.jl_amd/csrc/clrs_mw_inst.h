@@ -32,6 +32,7 @@
     X __global__ void k_mwi_R<K>(const MwDev, const MwIpmDev, int);                                                    \
     X __global__ void k_mwi_Z<K>(const MwDev, const MwIpmDev, int, int);                                               \
     X __global__ void k_mwi_Zi<K>(const MwDev, const MwIpmDev, int);                                                   \
+    X __global__ void k_mwi_Xv<K>(const MwDev, const MwIpmDev);                                                        \
     X __global__ void k_mwi_bmm<K>(const MwDev, const MwIpmDev, int, int);                                             \
     X __global__ void k_mwx_slice<K>(const MwDev, const MwxDev);                                                       \
     X __global__ void k_mwx_gram<K>(const MwDev, const MwxDev);                                                        \

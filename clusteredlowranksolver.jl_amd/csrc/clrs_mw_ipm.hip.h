@@ -21,6 +21,8 @@ struct MwIpmDev {
     int wBn;                           // leading dimension of wB: the largest side of a low-rank block (0: not used)
     double *Zs;                        // unsymmetrised X^-1 (...) of k_mwi_Zi (xy layout)
     double *Zt;                        // second scratch of the tiled form of the same products (k_mwi_bmm; xy layout)
+    double *Xv;                        // X^-1 = Xi^T Xi of the blocks with an inverse factor (xy layout, both triangles), formed once per iteration on the side stream
+                                       // (k_mwi_Xv) for every k_mwi_Zi launch of that iteration; null: k_mwi_Zi applies Xi^T (Xi M) (clrs_config_set("mw_xinv_product", 0), the tiled path)
     double *wB;                        // [T * wBn] K limbs: coefficient times right vector of every term, for blocks with many terms (k_mwi_wB)
     int *zcnt;                         // [NB] workgroups of a block that have delivered their panel
     unsigned long long *stamps;        // diagnostic (clrs_mw_debug_exact_stamps): wall_clock64 at the phase boundaries of k_mwi_Zi, wave 0 of the first workgroup, or null
@@ -1110,6 +1112,7 @@ __global__ __launch_bounds__(MW_NT) void k_mwi_Z(const MwDev q, const MwIpmDev p
 // a scratch matrix and the workgroup of a block that finishes last symmetrises it (a counter per block).
 // (MWI_ZS, MWI_ZL and the launch rule -- 512 threads, or 256 with panels of half the width: one wave per SIMD -- are in clrs_mw_zi_panels.h; the
 // workgroup's size is read from the launch)
+// With MwIpmDev::Xv (the product Xi^T Xi, formed once per iteration by k_mwi_Xv) the last two products are one, Xv M: two dependent phases and one barrier.
 // KA <= K: limbs of the three products (MwIpmDev::klow); the panels in the scratch matrix and the symmetrised result carry K planes, the upper ones zero
 template <int K, int KA>
 __device__ __forceinline__ void mwi_Zi_body(const MwDev &q, const MwIpmDev &p, int which) {
@@ -1146,27 +1149,42 @@ __device__ __forceinline__ void mwi_Zi_body(const MwDev &q, const MwIpmDev &p, i
     }
     __syncthreads();
     MWZ_STAMP();
-    for (int e0 = 0; e0 < n * pc; e0 += nt / MWI_ZL) {  // M2 = Xi M
-        const int e = e0 + tid / MWI_ZL;
-        const bool live = e < n * pc;
-        const int ee = live ? e : 0, i = ee % n, cl = ee / n;
-        acc<KA> s;
-        acc_zero<KA>(s);
-        for (int r = sub; r <= i; r += MWI_ZL) acc_fma<KA, KA, KA>(s, ldx<KA>(Xi, q.xylen, i + (long)r * n), ldx<KA>(M, np, r + (long)cl * n));
-        const mw<KA> v = lanes_sum<KA, MWI_ZL>(acc_result<KA>(s));
-        if (live && sub == 0) stx<KA>(M2, np, ee, v);
-    }
-    __syncthreads();
-    MWZ_STAMP();
-    for (int e0 = 0; e0 < n * pc; e0 += nt / MWI_ZL) {  // Xi^T M2 -> scratch
-        const int e = e0 + tid / MWI_ZL;
-        const bool live = e < n * pc;
-        const int ee = live ? e : 0, i = ee % n, cl = ee / n;
-        acc<KA> s;
-        acc_zero<KA>(s);
-        for (int r = i + sub; r < n; r += MWI_ZL) acc_fma<KA, KA, KA>(s, ldx<KA>(Xi, q.xylen, r + (long)i * n), ldx<KA>(M2, np, r + (long)cl * n));
-        const mw<KA> v = lanes_sum<KA, MWI_ZL>(acc_result<KA>(s));
-        if (live && sub == 0) stx_wt<K>(p.Zs + k.xyoff, q.xylen, i + (long)(c0 + cl) * n, cvt<K, KA>(v), p.hop != 0);
+    if (p.Xv) {                                          // X^-1 M as ONE product with Xv = Xi^T Xi (k_mwi_Xv): a full row of n terms, no second barrier, M2 not used
+        const double *Xv = p.Xv + k.xyoff;
+        for (int e0 = 0; e0 < n * pc; e0 += nt / MWI_ZL) {
+            const int e = e0 + tid / MWI_ZL;
+            const bool live = e < n * pc;
+            const int ee = live ? e : 0, i = ee % n, cl = ee / n;
+            acc<KA> s;
+            acc_zero<KA>(s);
+            for (int r = sub; r < n; r += MWI_ZL) acc_fma<KA, KA, KA>(s, ldx<KA>(Xv, q.xylen, i + (long)r * n), ldx<KA>(M, np, r + (long)cl * n));
+            const mw<KA> v = lanes_sum<KA, MWI_ZL>(acc_result<KA>(s));
+            if (live && sub == 0) stx_wt<K>(p.Zs + k.xyoff, q.xylen, i + (long)(c0 + cl) * n, cvt<K, KA>(v), p.hop != 0);
+        }
+        MWZ_STAMP();
+    } else {
+        for (int e0 = 0; e0 < n * pc; e0 += nt / MWI_ZL) {  // M2 = Xi M
+            const int e = e0 + tid / MWI_ZL;
+            const bool live = e < n * pc;
+            const int ee = live ? e : 0, i = ee % n, cl = ee / n;
+            acc<KA> s;
+            acc_zero<KA>(s);
+            for (int r = sub; r <= i; r += MWI_ZL) acc_fma<KA, KA, KA>(s, ldx<KA>(Xi, q.xylen, i + (long)r * n), ldx<KA>(M, np, r + (long)cl * n));
+            const mw<KA> v = lanes_sum<KA, MWI_ZL>(acc_result<KA>(s));
+            if (live && sub == 0) stx<KA>(M2, np, ee, v);
+        }
+        __syncthreads();
+        MWZ_STAMP();
+        for (int e0 = 0; e0 < n * pc; e0 += nt / MWI_ZL) {  // Xi^T M2 -> scratch
+            const int e = e0 + tid / MWI_ZL;
+            const bool live = e < n * pc;
+            const int ee = live ? e : 0, i = ee % n, cl = ee / n;
+            acc<KA> s;
+            acc_zero<KA>(s);
+            for (int r = i + sub; r < n; r += MWI_ZL) acc_fma<KA, KA, KA>(s, ldx<KA>(Xi, q.xylen, r + (long)i * n), ldx<KA>(M2, np, r + (long)cl * n));
+            const mw<KA> v = lanes_sum<KA, MWI_ZL>(acc_result<KA>(s));
+            if (live && sub == 0) stx_wt<K>(p.Zs + k.xyoff, q.xylen, i + (long)(c0 + cl) * n, cvt<K, KA>(v), p.hop != 0);
+        }
     }
     MWZ_STAMP();
     if (!mwi_last_block(p, &p.zcnt[blockIdx.x], zs)) return;
@@ -1186,6 +1204,32 @@ __global__ __launch_bounds__(MW_PT) void k_mwi_Zi(const MwDev q, const MwIpmDev 
     mw_mark(q);
     if constexpr (mw_kf_of(K) < K) { if (p.klow < K) { mwi_Zi_body<K, mw_kf_of(K)>(q, p, which); return; } }
     mwi_Zi_body<K, K>(q, p, which);
+}
+
+// Xv = Xi^T Xi = X^-1 of the blocks with an inverse factor: the same for the four k_mwi_Zi launches of an iteration, three of them on the main stream's
+// chain, so it is formed ONCE, on the side stream behind "the assembly is complete" (Xi is this iteration's) and in front of the side stream's own k_mwi_Zi.
+// Eight lanes per entry of the lower triangle (Xi is lower triangular: rows max(i, c) = i .. n - 1), the mirror written by the same lanes; K limbs, whatever
+// the limbs of the launch that reads it.  grid (tiles of MW_NT / MWI_ZL entries, NB)
+template <int K>
+__global__ __launch_bounds__(MW_NT) void k_mwi_Xv(const MwDev q, const MwIpmDev p) {
+    using namespace mwk;
+    const MwBlk &k = q.blk[blockIdx.y];
+    if (!k.inv) return;
+    const int n = k.n;
+    if (blockIdx.x * (MW_NT / MWI_ZL) >= n * n) return;
+    const int e = blockIdx.x * (MW_NT / MWI_ZL) + threadIdx.x / MWI_ZL, sub = threadIdx.x % MWI_ZL;
+    const bool live = e < n * n;
+    const int ee = live ? e : 0, i = ee % n, c = ee / n;
+    const double *Xi = q.Xi + k.xyoff;
+    acc<K> s;
+    acc_zero<K>(s);
+    if (i >= c)
+        for (int r = i + sub; r < n; r += MWI_ZL) acc_fma<K, K, K>(s, ldx<K>(Xi, q.xylen, r + (long)i * n), ldx<K>(Xi, q.xylen, r + (long)c * n));
+    const mw<K> v = lanes_sum<K, MWI_ZL>(acc_result<K>(s));
+    if (live && sub == 0 && i >= c) {
+        stx<K>(p.Xv + k.xyoff, q.xylen, i + (long)c * n, v);
+        stx<K>(p.Xv + k.xyoff, q.xylen, c + (long)i * n, v);
+    }
 }
 
 // The same three products for LARGE blocks (sides beyond ~24), as launches of their own over 8 x 8 output tiles, four lanes per entry: a column panel

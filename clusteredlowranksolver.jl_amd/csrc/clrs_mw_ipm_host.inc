@@ -142,6 +142,8 @@ extern "C" int clrs_mw_ipm_create_ex(clrs_mw_ctx *c, const clrs_ipm_data *data, 
             }
         }
         st->z_tiled = maxn_inv > 24;
+        p.Xv = nullptr;                                     // X^-1 = Xi^T Xi for the k_mwi_Zi launches (formed by k_mwi_Xv: mw_ipm_enqueue_body); the tiled path and k_mwi_Z do without
+        if (st->any_xinv && !st->z_tiled && c->xinv_product && (rc = mw_dmalloc(c, &p.Xv, q.xylen * K))) return rc;
         st->sm_bmm = (size_t)2 * K * MWI_BT * maxn_inv * 8;
         const size_t step_inv_need = 3 * maxn_inv * maxn_inv * K + step_rest;
         bool all_lds_inv = st->any_xinv;
@@ -493,6 +495,14 @@ static int mw_ipm_enqueue_body(clrs_mw_ctx *c) {
     MWCHECK(hipGetLastError());
     if (words) hipLaunchKernelGGL(k_mwi_wait<0>, dim3(1), dim3(64), 0, S, (const int *)(p.sync + 1), seq, q.info, q.J + 1);      // the inverse factors of chol(X), and A_Y: the pairings w^T Y v of the assembly
     else MWCHECK(hipStreamWaitEvent(S, st->ev[MwIpm::E_ASM], 0));
+    if (p.Xv) {
+        // Xv = Xi^T Xi, once for the four k_mwi_Zi launches of this iteration.  Written here only: behind the Cholesky of X of THIS iteration (the wait above) and so
+        // behind the previous iteration's update, i.e. behind every launch of M that read the previous Xv; M reads it first behind the Cholesky of Q, whose
+        // riders have waited for this stream's mark (E_PREP in event mode), which is submitted behind this launch.
+        const int xv_tiles = ((int)(st->maxn_inv * st->maxn_inv) * MWI_ZL + MW_NT - 1) / MW_NT;
+        MW_DISPATCH(c, hipLaunchKernelGGL(k_mwi_Xv<KK>, dim3(xv_tiles, q.NB), dim3(MW_NT), 0, S, q, p));
+        MWCHECK(hipGetLastError());
+    }
     if ((rc = mw_ipm_rhs(c, S, 0))) return rc;
     if ((rc = mw_ipm_trace_rhs(c, S))) return rc;
     MW_DISPATCH(c, {
