@@ -19,6 +19,11 @@ on the device (clrs_modp_rref): `rref_mod_p`, `find_pivots
 The rest of `project_to_affine_space` (src/rounding.jl:213-286, 336-364) is the exact solve of the integer system, the reference's `Nemo._solve_dixon`: Dixon's
 p-adic lifting, on the device (clrs_modp_dixon_lift): `dixon_lift`, `solve_dixon`, `solve_system_pseudoinverse`,
 `project_to_affine_space`.  The rational reconstruction and the products around the solve are exact host arithmetic in Python integers.
+
+The last numeric step of the chain is `is_valid_solution` (src/rounding.jl:367-415): zero slacks, and every block of the exact solution positive definite
+(`checkpd_cholesky`, src/rounding.jl:447-472, Arb's ball-arithmetic Cholesky).  Here the answer is exact: the leading principal minors of the block, cleared of
+denominators, mod many primes on the device (clrs_modp_minors), lifted to integers on the host: `leading_minors_mod`, `minor_bounds`,
+`crt_tree`, `checkpd`, `is_valid_solution`.  Blocks of at most 128 rows.
 """
 from __future__ import annotations
 
@@ -33,7 +38,8 @@ from . import _lib
 __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vectors", "kernel_vectors_batch", "kernel_vectors_rational_batch", "rationalize",
            "vectors_to_mp", "vectors_to_fractions", "rref_mod_p", "next_prime", "find_pivots_modular", "system_pivots", "PivotList", "to_balanced_digits", "from_balanced_digits",
            "prev_prime", "dixon_steps", "dixon_lift", "rational_reconstruction", "SingularSystemError", "DixonSolution", "solve_dixon",
-           "solve_system_pseudoinverse", "project_to_affine_space", "to_digits24", "from_digits24", "dixon_reconstruct"]
+           "solve_system_pseudoinverse", "project_to_affine_space", "to_digits24", "from_digits24", "dixon_reconstruct", "leading_minors_mod", "minor_bounds", "crt_tree",
+           "PDCertificate", "checkpd", "is_valid_solution"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -840,3 +846,250 @@ def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, r
     for j, c in enumerate(pivots):
         x[c] = newx[j]
     return x, correct, True
+
+
+# ---- the exact positive-definiteness check: leading minors mod many primes (src/rounding.jl:367-415, 447-472; clrs_modp_minors) ------------
+MINORS_MAX_N = 128                   # clrs_modp_minors keeps the matrix of a prime in the LDS of one workgroup
+MINORS_MAX_PRIMES = 65535            # primes of one call of clrs_modp_minors
+
+
+def _primes_descending():
+    """every prime below 2^23, descending (what repeated `prev_prime` from 2^23 gives), sieved once"""
+    if _primes_descending.cache is None:
+        sieve = np.ones(MODP_PRIME_LIMIT, dtype=bool)
+        sieve[:2] = False
+        for d in range(2, _isqrt(MODP_PRIME_LIMIT) + 1):
+            if sieve[d]:
+                sieve[d * d::d] = False
+        _primes_descending.cache = np.flatnonzero(sieve)[::-1].astype(np.int64)
+    return _primes_descending.cache
+
+
+_primes_descending.cache = None
+
+
+def _symmetric_integer_matrix(M, what):
+    """-> an object matrix (n, n) of Python integers; `ValueError` unless square and symmetric"""
+    a = _integer_matrix(M, what)
+    if a.shape[0] != a.shape[1]:
+        raise ValueError(f"{what}: the matrix must be square, got {a.shape}")
+    n = a.shape[0]
+    out = np.array([int(v) for v in a.flat], dtype=object).reshape(n, n) if n else np.zeros((0, 0), dtype=object)
+    if any(out[i, j] != out[j, i] for i in range(n) for j in range(i)):
+        raise ValueError(f"{what}: the matrix must be symmetric")
+    return out
+
+
+def leading_minors_mod(M, primes, device: int = 0):
+    """The leading principal minors of the symmetric integer matrix `M` (n <= 128, Python integers of any size) mod every prime of `primes` (distinct, in
+    [2, 2^23), at most 65535) on the device: one call of clrs_modp_minors.  Returns `(minors, breakdown)`: minors int32 (len(primes), n), row q holding
+    minor_1 .. minor_n mod primes[q]; breakdown int32 (len(primes),), 0 or the order k of the first minor that is 0 mod primes[q] -- row q then holds 0 at
+    position k and -1 behind it (the elimination takes no exchanges, so nothing behind a zero pivot is defined).  The counters of the call are kept in
+    `leading_minors_mod.last_info` (`[LDS bytes per workgroup, workgroups, primes that broke down, 0]`)."""
+    a = _symmetric_integer_matrix(M, "leading_minors_mod")
+    n = a.shape[0]
+    pr = np.ascontiguousarray([int(p) for p in primes], dtype=np.int64)
+    if n < 1 or n > MINORS_MAX_N:
+        raise ValueError(f"leading_minors_mod: n must lie in [1, {MINORS_MAX_N}], got {n}")
+    if pr.size < 1 or pr.size > MINORS_MAX_PRIMES or pr.min() < 2 or pr.max() >= MODP_PRIME_LIMIT:
+        raise ValueError(f"leading_minors_mod: between 1 and {MINORS_MAX_PRIMES} primes in [2, 2^23) are needed")
+    pr = pr.astype(np.int32)
+    digits = to_balanced_digits(a)
+    minors, breakdown, info = np.full((pr.size, n), -2, np.int32), np.full(pr.size, -2, np.int32), np.zeros(4, np.int32)
+    ptr = lambda v: v.ctypes.data_as(_lib.p_i32)
+    _lib.check(_lib.load().clrs_modp_minors(int(device), n, digits.shape[0], ptr(digits), pr.size, ptr(pr), ptr(minors), ptr(breakdown), ptr(info)))
+    leading_minors_mod.last_info = [int(v) for v in info]
+    return minors, breakdown
+
+
+leading_minors_mod.last_info = None
+
+
+def minor_bounds(M) -> list:
+    """Python integers `H_k >= |minor_k|`, k = 1 .. n, for the symmetric integer matrix `M`: Hadamard's bound on the leading k x k part, the product of
+    the Euclidean norms of its rows, every square root an integer square root rounded up."""
+    a = _symmetric_integer_matrix(M, "minor_bounds")
+    n = a.shape[0]
+    sums, out = [0] * n, []
+    for k in range(1, n + 1):
+        for i in range(k - 1):
+            sums[i] += a[i, k - 1] * a[i, k - 1]
+        sums[k - 1] = sum(a[k - 1, j] * a[k - 1, j] for j in range(k))
+        h = 1
+        for i in range(k):
+            r = _isqrt(sums[i])
+            h *= r if r * r == sums[i] else r + 1
+        out.append(h)
+    return out
+
+
+def crt_tree(residues, primes):
+    """Balanced Chinese remaindering of many residue vectors over ONE product tree: `primes` m distinct primes, `residues` (m, count) (or (m,)): row q
+    holds the residues mod primes[q].  Returns `(values, modulus)`: `modulus` the product P of the primes, `values` a list of `count` Python integers
+    (one integer for (m,)), the representatives in (-P / 2, P / 2].
+
+    The tree of products is built once.  The cofactors (P / p_q)^-1 mod p_q come from one remainder tree of P modulo the squares of the nodes
+    ((P mod p^2) / p = (P / p) mod p); a vector is then combined upwards, `v_left P_right + v_right P_left` per node.  Every level costs a few
+    multiplications of the total size, so the whole is quasi-linear in the bits of P (a Horner-style incremental CRT is quadratic)."""
+    pr = [int(p) for p in primes]
+    m = len(pr)
+    res = np.asarray(residues)
+    single = res.ndim == 1
+    res = res.reshape(m, -1) if m else res.reshape(0, 0)
+    if m < 1 or len(set(pr)) != m or min(pr) < 2:
+        raise ValueError("crt_tree: at least one modulus, all distinct and at least 2")
+    count = res.shape[1]
+    levels = [pr]
+    while len(levels[-1]) > 1:
+        prev = levels[-1]
+        levels.append([prev[i] * prev[i + 1] if i + 1 < len(prev) else prev[i] for i in range(0, len(prev), 2)])
+    P = levels[-1][0]
+    rem = [P]
+    for lev in reversed(levels[:-1]):
+        rem = [rem[i // 2] % (v * v) for i, v in enumerate(lev)]
+    inv = [pow((rem[i] // pr[i]) % pr[i], -1, pr[i]) for i in range(m)]
+    if max(pr) < MODP_PRIME_LIMIT:                                  # the leaves in int64: a residue times a cofactor is below 2^46
+        leaves = np.mod(np.mod(res.astype(np.int64), np.array(pr, np.int64)[:, None]) * np.array(inv, np.int64)[:, None], np.array(pr, np.int64)[:, None]).astype(object)
+    else:
+        leaves = np.array([[(int(res[i, c]) % pr[i]) * inv[i] % pr[i] for c in range(count)] for i in range(m)], dtype=object).reshape(m, count)
+    half = P // 2
+    values = []
+    for c in range(count):
+        vals = [int(v) for v in leaves[:, c]]
+        for lev in levels[:-1]:
+            vals = [vals[i] * lev[i + 1] + vals[i + 1] * lev[i] if i + 1 < len(vals) else vals[i] for i in range(0, len(vals), 2)]
+        x = vals[0] % P
+        values.append(x - P if x > half else x)
+    return (values[0] if single else values), P
+
+
+@dataclasses.dataclass
+class PDCertificate:
+    """What `checkpd` proves about a symmetric rational matrix A.  `pd`: A is positive definite.  `scale`: the positive least common multiple D of the
+    denominators; the minors are those of the integer matrix D A.  `minors`: the exact leading principal minors of D A as Python integers, from order 1 up
+    to the order at which the walk stopped (all n of them when `pd`).  `failed_order`: None, or the order k of the first minor that is <= 0 (`minors[-1]`).
+    When a diagonal entry <= 0 decided the question on the host, no minor was computed: `minors` is empty and `failed_order` is the 1-based index of that
+    entry.  `primes`: every prime the device was given, in order; `discarded`: `(prime, order)` for the primes that broke down (a zero pivot at that
+    order: the prime divides that minor) and were left out of every minor behind it."""
+    pd: bool
+    minors: list
+    failed_order: Optional[int]
+    scale: int
+    primes: list
+    discarded: list
+
+    def __bool__(self):
+        return self.pd
+
+
+def _product(values) -> int:
+    values = list(values)
+    while len(values) > 1:
+        values = [values[i] * values[i + 1] if i + 1 < len(values) else values[i] for i in range(0, len(values), 2)]
+    return values[0] if values else 1
+
+
+def checkpd(A, device: int = 0, minors=None) -> PDCertificate:
+    """Is the symmetric matrix `A` (n <= 128, `Fraction`s or integers) positive definite?  An exact answer with its proof, where the reference asks Arb for a
+    ball-arithmetic Cholesky (checkpd_cholesky, src/rounding.jl:447-472).  `ValueError` unless A is square and symmetric.
+
+    M = D A with D the positive least common multiple of the denominators; A is positive definite iff every leading principal minor of M is positive.  An
+    empty matrix is positive definite; a diagonal entry <= 0 answers from the host.  Otherwise the minors are computed mod primes taken downward from
+    8388593 (`minors(M, primes, device=...)` -> `(residues, breakdown)`, default `leading_minors_mod`; at most 65535 primes per call) and lifted by
+    `crt_tree`: for minor k the primes with `breakdown == 0` or `breakdown >= k` are usable, and their product must exceed `2 minor_bounds(M)[k - 1]`.
+    The orders are walked upwards; where breakdowns leave too few primes for the next order, more primes are drawn in a further call; the walk stops at the
+    first minor <= 0.  A prime at which minor k is not 0 cannot break down at order k or below, so for a non-zero minor only the finitely many primes that
+    divide it or an earlier minor are lost; when minor k is 0 every prime breaks down at k at the latest, all are usable for k, and the zero is proven by
+    the same bound."""
+    from math import gcd
+    minors_fn = leading_minors_mod if minors is None else minors
+    a = np.asarray(A, dtype=object)
+    if a.size == 0 and a.ndim <= 2 and (a.ndim < 2 or a.shape[0] == a.shape[1]):
+        return PDCertificate(True, [], None, 1, [], [])
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise ValueError(f"checkpd: the matrix must be square, got shape {a.shape}")
+    n = a.shape[0]
+    rows = [[Fraction(v) for v in a[i]] for i in range(n)]
+    if any(rows[i][j] != rows[j][i] for i in range(n) for j in range(i)):
+        raise ValueError("checkpd: the matrix must be symmetric")
+    scale = 1
+    for row in rows:
+        for v in row:
+            scale = scale * v.denominator // gcd(scale, v.denominator)
+    for i in range(n):
+        if rows[i][i] <= 0:
+            return PDCertificate(False, [], i + 1, scale, [], [])
+    if n > MINORS_MAX_N:
+        raise ValueError(f"checkpd: blocks of more than {MINORS_MAX_N} rows are not supported, got {n}")
+    M = np.zeros((n, n), dtype=object)
+    for i in range(n):
+        M[i] = [int(v * scale) for v in rows[i]]
+    H = minor_bounds(M)
+    schedule = _primes_descending()
+    primes, breaks, columns = [], [], []                            # per prime: its breakdown and its row of residues
+    exact, done, drawn = [], 0, 0                                   # the minors lifted so far (orders 1 .. done)
+    while done < n:
+        # draw: enough primes that, were none to break down, the product exceeds twice the largest bound still ahead
+        need, have = 2 * max(max(H[done:]), 1), _product(p for p, k in zip(primes, breaks) if k == 0)
+        batch = []
+        while (have <= need or not batch) and len(batch) < MINORS_MAX_PRIMES:
+            if drawn >= schedule.size:
+                raise ArithmeticError("checkpd: the primes below 2^23 are exhausted")
+            batch.append(int(schedule[drawn]))
+            have *= batch[-1]
+            drawn += 1
+        res, brk = minors_fn(M, batch, device=device)
+        primes += batch
+        breaks += [int(k) for k in brk]
+        columns += [np.asarray(r) for r in np.asarray(res)]
+        # lift every order whose usable primes suffice, in groups that share their set of usable primes (one tree per group)
+        groups, products, order = {}, {}, done + 1
+        while order <= n:
+            usable = tuple(q for q, k in enumerate(breaks) if k == 0 or k >= order)
+            if usable not in products:
+                products[usable] = _product(primes[q] for q in usable)
+            if not usable or products[usable] <= 2 * H[order - 1]:
+                break
+            groups.setdefault(usable, []).append(order)
+            order += 1
+        stop = False
+        for usable, orders in groups.items():                      # (insertion order: ascending orders)
+            values, _ = crt_tree(np.array([[int(columns[q][k - 1]) for k in orders] for q in usable], dtype=np.int64), [primes[q] for q in usable])
+            for k, v in zip(orders, values):
+                exact.append(v)
+                done = k
+                if v <= 0:
+                    stop = True
+                    break
+            if stop:
+                break
+        if stop:
+            break
+    discarded = [(p, k) for p, k in zip(primes, breaks) if k != 0]
+    failed = done if exact and exact[-1] <= 0 else None
+    return PDCertificate(failed is None, exact, failed, scale, primes, discarded)
+
+
+def is_valid_solution(blocks, A=None, b=None, x=None, check_slacks: bool = True, device: int = 0, minors=None):
+    """The numeric part of the reference's `is_valid_solution` (src/rounding.jl:367-415): are the slacks zero, and is every block of the exact solution
+    positive definite?  `blocks`: the symmetric blocks (`Fraction`s or integers), each through `checkpd` (`device`, `minors` go there).  With
+    `check_slacks` the slacks `A x - b` (`A` (nrows, ncols), `b` (nrows,), `x` (ncols,)) are formed in `Fraction` arithmetic on the host.  Returns
+    `(success, failures)`: `failures` lists `("constraint", i, slack)` for every constraint i with a non-zero slack and `("block", j, failed_order)` for
+    every block j that is not positive definite."""
+    failures = []
+    if check_slacks:
+        if A is None or b is None or x is None:
+            raise ValueError("is_valid_solution: A, b and x are needed to check the slacks")
+        rows, bf, ncols = _fraction_rows(A, b, "is_valid_solution")
+        xf = [Fraction(v) for v in np.asarray(x, dtype=object).reshape(-1)]
+        if len(xf) != ncols:
+            raise ValueError(f"is_valid_solution: x must have one entry per column of A, got {len(xf)} for {ncols} columns")
+        for i, row in enumerate(rows):
+            slack = sum((row[c] * xf[c] for c in range(ncols) if xf[c] != 0), Fraction(0)) - bf[i]
+            if slack != 0:
+                failures.append(("constraint", i, slack))
+    for j, blk in enumerate(blocks):
+        cert = checkpd(blk, device=device, minors=minors)
+        if not cert.pd:
+            failures.append(("block", j, cert.failed_order))
+    return not failures, failures

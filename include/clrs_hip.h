@@ -416,7 +416,21 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   cofactor past its row, steps without end): non-zero gives CLRS_ERR_HIP.  n = 0 returns at once.  CLRS_ERR_INVALID before anything is allocated: n < 0
  *   or n > 32767, steps < 1 (or p^steps beyond 32767 limbs), p no prime in [2, 2^23), a null pointer (x_limbs may be null), nN, nD or nl outside
  *   [1, 32767], a digit outside [0, 2^24), nl below the limbs of max(N, D), a residue outside [0, p), nx too small.  Every device buffer is released on every path.
- * clrs_modp_dixon_reconstruct_times: the milliseconds the calling thread's last clrs_modp_dixon_reconstruct spent in its two kernels (Horner, Euclid). */
+ * clrs_modp_dixon_reconstruct_times: the milliseconds the calling thread's last clrs_modp_dixon_reconstruct spent in its two kernels (Horner, Euclid).
+ * clrs_modp_minors: the n leading principal minors of a symmetric integer matrix mod each of nprimes primes (the device half of an exact
+ *   positive-definiteness check, what the reference's is_valid_solution asks of checkpd_cholesky, src/rounding.jl:367-415, 447-472), host pointers, no context.
+ *   digits is [nd][n][n]: nd row-major planes of balanced base-2^24 digits, little-endian, every digit in [-2^23, 2^23], every plane symmetric.  primes holds
+ *   nprimes distinct primes in [2, 2^23).  minors is [nprimes][n]: row q receives minor_1 .. minor_n mod primes[q], in [0, primes[q]), the running products of
+ *   the pivots of the elimination L D L^T mod that prime, WITHOUT exchanges (leading minors do not survive them).  breakdown[q] is 0, or the 1-based order k of
+ *   the first minor that is 0 mod primes[q]: row q is then valid up to and including position k, where it holds 0, and holds -1 behind it.  info[0]: the LDS
+ *   bytes of a workgroup (one workgroup per prime, the matrix resident in LDS: hence n <= CLRS_MODP_MINORS_MAX_N); info[1]: workgroups launched; info[2]:
+ *   primes that broke down; info[3]: impossibilities (a pivot or a minor that is no residue): non-zero gives CLRS_ERR_HIP and leaves minors and breakdown
+ *   untouched.  CLRS_ERR_INVALID before any device call: n outside [1, 128], nd outside [1, 32767], nprimes outside [1, 65535], a null pointer, a digit outside
+ *   [-2^23, 2^23], planes that are not symmetric, a modulus that is no prime in [2, 2^23), a repeated prime.  Every device buffer is released on every path.
+ *   clrs_config_set("modp_minors_chunk_bytes", b): the primes are taken in chunks whose residues (8 n^2 bytes per prime) stay below b bytes (0, the default: 256 MiB).
+ * clrs_modp_minors_times: the milliseconds of the calling thread's last clrs_modp_minors: in the residue kernel, in the L D L^T kernel, and from the first
+ *   upload to the last download (device events). */
+#define CLRS_MODP_MINORS_MAX_N 128
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
 int clrs_mw_rank_reveal(int device, int limbs, int nmat, const int32_t *n, const int32_t *ncand, const double *G, const double *tau, int32_t *perm, int32_t *rank,
@@ -441,6 +455,8 @@ int clrs_modp_dixon_lift(int device, int n, int p, int nd, const int32_t *A_digi
 int clrs_modp_dixon_reconstruct(int device, int n, int p, int steps, const int32_t *X, int nN, const int32_t *N_limbs, int nD, const int32_t *D_limbs, int nl,
                                 int32_t *num, int32_t *den, int32_t *neg, int32_t *status, int nx, int32_t *x_limbs, int32_t *info);
 int clrs_modp_dixon_reconstruct_times(double *horner_ms, double *euclid_ms);
+int clrs_modp_minors(int device, int n, int nd, const int32_t *digits, int nprimes, const int32_t *primes, int32_t *minors, int32_t *breakdown, int32_t *info);
+int clrs_modp_minors_times(double *residues_ms, double *ldl_ms, double *total_ms);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 
