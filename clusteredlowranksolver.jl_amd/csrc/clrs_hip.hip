@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -893,6 +894,10 @@ static bool vec_eq(const double *a, const double *b, int n) {   // exact equalit
     return true;
 }
 
+#include "clrs_ctx_create.inc"
+
+typedef std::unique_ptr<clrs_ctx, void (*)(clrs_ctx *)> CtxOwner;   // destroys the context it still holds: the one failure path of whoever creates one
+
 extern "C" int clrs_ctx_create(const clrs_sdp_desc *d, int device, clrs_ctx **out) {
     if (!d || !out) return fail(CLRS_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -900,1387 +905,14 @@ extern "C" int clrs_ctx_create(const clrs_sdp_desc *d, int device, clrs_ctx **ou
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(CLRS_ERR_NO_DEVICE, "no HIP device");
     if (device < 0 || device >= ndev) return fail(CLRS_ERR_NO_DEVICE, "device index out of range");
     HIPCHECK(hipSetDevice(device));
-    clrs_ctx *c = new clrs_ctx();
+    CtxOwner c(new clrs_ctx(), clrs_ctx_destroy);      // whatever a failed stage left behind goes with the context
     c->device = device;
-    int rc = 0;
-#define CK(x) do { rc = (x); if (rc) { clrs_ctx_destroy(c); return rc; } } while (0)
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { clrs_ctx_destroy(c); return fail(CLRS_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } } while (0)
-    HIPCK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIPCK(hipFuncSetAttribute((const void *)k_gemm_f64_t<128, 128, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes(128, 128)));
-    HIPCK(hipFuncSetAttribute((const void *)k_gemm_f64_t<128, 128, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes(128, 128)));
-    HIPCK(hipFuncSetAttribute((const void *)k_gemm_f64_t<128, 128, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes(128, 128)));
-    HIPCK(hipFuncSetAttribute((const void *)k_gemm_f64_t<128, 128, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes(128, 128)));
-    for (int i = 0; i < 10; i++) HIPCK(hipEventCreate(&c->ev[i]));
-    c->J = d->n_clusters; c->N = d->n_free; c->NB = d->n_blocks;
-    if (c->J < 0 || c->N < 0 || c->NB < 0) { clrs_ctx_destroy(c); return fail(CLRS_ERR_INVALID, "negative sizes"); }
-    const int J = c->J, N = c->N, NB = c->NB;
-    c->P.assign(d->cluster_P, d->cluster_P + J);
-    c->coff.assign(J + 1, 0); c->Soff.assign(J + 1, 0);
-    for (int j = 0; j < J; j++) {
-        if (c->P[j] <= 0) { clrs_ctx_destroy(c); return fail(CLRS_ERR_INVALID, "cluster with no constraints"); }
-        c->coff[j + 1] = c->coff[j] + c->P[j];
-        c->Soff[j + 1] = c->Soff[j] + (i64)c->P[j] * c->P[j];
-    }
-    c->xlen = c->coff[J]; c->Slen = c->Soff[J];
-    c->T = d->term_ptr[NB]; c->D = d->dense_ptr[NB];
-    const i64 T = c->T;
-
-    // ---- blocks, de-duplication of the sampled vectors (src/solver.jl:985-1059) ----
-    c->blk.resize(NB);
-    std::vector<int> ridx(T), lidx(T);
-    std::vector<i64> partner(T, -1);
-    std::vector<std::vector<std::vector<i64>>> uniqR(NB), uniqL(NB);
-    i64 xyoff = 0;
-    int prevj = 0;
-    for (int b = 0; b < NB; b++) {
-        BlockInfo &k = c->blk[b];
-        k.j = d->block_cluster[b]; k.m = d->block_m[b]; k.delta = d->block_delta[b]; k.kind = d->block_kind[b];
-        k.n = k.m * k.delta;
-        if (k.j < prevj || k.j >= J || k.m <= 0 || k.delta <= 0) { clrs_ctx_destroy(c); return fail(CLRS_ERR_INVALID, "bad block description (clusters must be listed in order)"); }
-        prevj = k.j;
-        k.xyoff = xyoff; xyoff += (i64)k.n * k.n;
-        k.t0 = d->term_ptr[b]; k.t1 = d->term_ptr[b + 1]; k.d0 = d->dense_ptr[b]; k.d1 = d->dense_ptr[b + 1];
-        c->host_U_off.push_back((i64)c->host_UR.size());
-        if (k.kind != 0) {
-            if (k.m != 1) { clrs_ctx_destroy(c); return fail(CLRS_ERR_INVALID, "dense blocks need m == 1"); }
-            k.cnt = (int)(k.d1 - k.d0);
-            for (i64 e = k.d0; e < k.d1; e++)
-                if (d->dense_p[e] < 0 || d->dense_p[e] >= c->P[k.j]) { clrs_ctx_destroy(c); return fail(CLRS_ERR_INVALID, "dense constraint index out of range"); }
-            continue;
-        }
-        const int m = k.m, dl = k.delta;
-        k.UR.assign(m, 0); k.UL.assign(m, 0); k.offR.assign(m + 1, 0); k.offL.assign(m + 1, 0);
-        uniqR[b].resize(m); uniqL[b].resize(m);
-        for (i64 t = k.t0; t < k.t1; t++) {
-            int r = d->term_r[t], s = d->term_s[t], p = d->term_p[t];
-            if (r < 0 || r >= m || s < 0 || s >= m || p < 0 || p >= c->P[k.j] || d->term_vec_ptr[t + 1] - d->term_vec_ptr[t] != dl) {
-                clrs_ctx_destroy(c);
-                return fail(CLRS_ERR_INVALID, "bad term description");
-            }
-            const double *v = d->term_vs + d->term_vec_ptr[t], *w = d->term_ws + d->term_vec_ptr[t];
-            std::vector<i64> &uR = uniqR[b][r], &uL = uniqL[b][r];
-            int f = -1;
-            for (size_t u = 0; u < uR.size(); u++) if (vec_eq(d->term_vs + d->term_vec_ptr[uR[u]], v, dl)) { f = (int)u; break; }
-            if (f < 0) { f = (int)uR.size(); uR.push_back(t); }
-            ridx[t] = f;
-            f = -1;
-            for (size_t u = 0; u < uL.size(); u++) if (vec_eq(d->term_ws + d->term_vec_ptr[uL[u]], w, dl)) { f = (int)u; break; }
-            if (f < 0) { f = (int)uL.size(); uL.push_back(t); }
-            lidx[t] = f;
-        }
-        {   // transposed partner (p, s, r, rank) of every term; required by the convention src/solver.jl:1009
-            std::map<std::array<int, 4>, i64> index;
-            for (i64 t = k.t0; t < k.t1; t++) index[{d->term_p[t], d->term_r[t], d->term_s[t], d->term_rank[t]}] = t;
-            for (i64 t = k.t0; t < k.t1; t++) {
-                auto it = index.find({d->term_p[t], d->term_s[t], d->term_r[t], d->term_rank[t]});
-                if (it == index.end()) { clrs_ctx_destroy(c); return fail(CLRS_ERR_INVALID, "term without transposed partner: A[r,s][p] must equal A[s,r][p]^T"); }
-                partner[t] = it->second;
-            }
-        }
-        k.sym = true;
-        for (int r = 0; r < m; r++) {
-            k.UR[r] = (int)uniqR[b][r].size(); k.UL[r] = (int)uniqL[b][r].size();
-            k.offR[r + 1] = k.offR[r] + k.UR[r]; k.offL[r + 1] = k.offL[r] + k.UL[r];
-            c->host_UR.push_back(k.UR[r]); c->host_UL.push_back(k.UL[r]);
-            if (k.UR[r] != k.UL[r]) k.sym = false;
-            else
-                for (int u = 0; u < k.UR[r] && k.sym; u++)
-                    if (!vec_eq(d->term_vs + d->term_vec_ptr[uniqR[b][r][u]], d->term_ws + d->term_vec_ptr[uniqL[b][r][u]], dl)) k.sym = false;
-        }
-        k.URt = k.offR[m]; k.ULt = k.offL[m];
-    }
-    c->xylen = xyoff;
-
-    // ---- arena layout ----
-    // "solve" arena: per low-rank block ZR (n x URt) [+ ZL (n x ULt) if not symmetric]; per dense block W (n x n*cnt).
-    // the static arena has the identical layout and holds the expanded vectors / the dense A stacks.
-    i64 so = 0, tyo = 0, go = 0, tto = 0, sdo = 0;
-    for (int b = 0; b < NB; b++) {
-        BlockInfo &k = c->blk[b];
-        if (k.kind == 0) {
-            k.zr_off = so; so += (i64)k.n * k.URt;
-            if (k.sym) k.zl_off = k.zr_off; else { k.zl_off = so; so += (i64)k.n * k.ULt; }
-            k.ty_off = tyo; tyo += (i64)k.n * k.URt;
-            k.g_off = go; go += 2 * (i64)k.ULt * k.URt;
-        } else {
-            k.w_off = so; so += (i64)k.n * k.n * k.cnt;
-            k.tt_off = tto; tto += (i64)k.n * k.n * k.cnt;
-            k.sd_off = sdo; sdo += (i64)k.cnt * k.cnt;
-        }
-    }
-    c->solve_arena_len = so;
-    std::vector<double> h_static((size_t)std::max<i64>(so, 1), 0.0);
-    for (int b = 0; b < NB; b++) {
-        BlockInfo &k = c->blk[b];
-        if (k.kind == 0) {
-            const int dl = k.delta, n = k.n;
-            for (int r = 0; r < k.m; r++) {
-                for (int u = 0; u < k.UR[r]; u++) {
-                    const double *v = d->term_vs + d->term_vec_ptr[uniqR[b][r][u]];
-                    double *dst = h_static.data() + k.zr_off + (i64)(k.offR[r] + u) * n + (i64)r * dl;
-                    std::memcpy(dst, v, sizeof(double) * dl);
-                }
-                if (!k.sym)
-                    for (int u = 0; u < k.UL[r]; u++) {
-                        const double *w = d->term_ws + d->term_vec_ptr[uniqL[b][r][u]];
-                        double *dst = h_static.data() + k.zl_off + (i64)(k.offL[r] + u) * n + (i64)r * dl;
-                        std::memcpy(dst, w, sizeof(double) * dl);
-                    }
-            }
-        } else {
-            for (i64 e = k.d0; e < k.d1; e++) {
-                if (d->dense_A_ptr[e + 1] - d->dense_A_ptr[e] != (i64)k.n * k.n) { clrs_ctx_destroy(c); return fail(CLRS_ERR_INVALID, "dense matrix has the wrong size"); }
-                {   // the dense branch forms <A_i, X^-1 A_k Y> from lower tiles and transposed stores (k_dense_T32, pairing_tri): A_p must be
-                    // symmetric, as the reference's constructor makes it (src/interface.jl:1010-1017 symmetrises a non-symmetric entry)
-                    const double *Ae = d->dense_A + d->dense_A_ptr[e];
-                    for (int cc = 0; cc < k.n; cc++)
-                        for (int rr = cc + 1; rr < k.n; rr++)
-                            if (Ae[rr + (i64)cc * k.n] != Ae[cc + (i64)rr * k.n]) { clrs_ctx_destroy(c); return fail(CLRS_ERR_INVALID, "dense constraint matrices must be symmetric"); }
-                }
-                std::memcpy(h_static.data() + k.w_off + (e - k.d0) * (i64)k.n * k.n, d->dense_A + d->dense_A_ptr[e], sizeof(double) * k.n * k.n);
-            }
-        }
-    }
-    CK(upload(c, h_static, &c->d_static));
-    CK(dmalloc(c, &c->d_work, so));
-    CK(dmalloc(c, &c->d_Xc, c->xylen)); CK(dmalloc(c, &c->d_Y, c->xylen)); CK(dmalloc(c, &c->d_X, c->xylen));
-    CK(dmalloc(c, &c->d_TY, tyo)); CK(dmalloc(c, &c->d_G, go)); CK(dmalloc(c, &c->d_TT, tto)); CK(dmalloc(c, &c->d_Sd, sdo));
-    CK(dmalloc(c, &c->d_S, c->Slen));
-    CK(dmalloc(c, &c->d_LB, c->xlen * (i64)N)); CK(dmalloc(c, &c->d_Q, (i64)N * N + N));
-    c->d_u = c->d_Q + (i64)N * N;      // u directly behind Q: a sharded caller sums both partials over the ranks with ONE collective
-    CK(dmalloc(c, &c->d_t, c->xlen)); CK(dmalloc(c, &c->d_dy, N)); CK(dmalloc(c, &c->d_rhsy, N));
-    CK(dmalloc(c, &c->d_dx, c->xlen)); CK(dmalloc(c, &c->d_rhsx, c->xlen));
-    CK(dmalloc(c, &c->d_AY, T));
-    {   // B stacked: rows = all constraints (cluster after cluster), columns = free variables; ld = xlen
-        std::vector<double> hB((size_t)std::max<i64>(c->xlen * (i64)N, 1), 0.0);
-        i64 boff = 0;
-        for (int j = 0; j < J; j++) {
-            for (int col = 0; col < N; col++)
-                for (int r = 0; r < c->P[j]; r++) hB[(size_t)(c->coff[j] + r + (i64)col * c->xlen)] = d->B[boff + r + (i64)col * c->P[j]];
-            boff += (i64)c->P[j] * N;
-        }
-        CK(upload(c, hB, &c->d_B));
-    }
-    {
-        int *di;
-        std::vector<int> hi(2, INFO_NONE);   // [0]: S_j / Q factorisations, [1]: Cholesky of the X blocks
-        CK(upload(c, hi, &di));
-        c->d_info = di;
-    }
-
-    // ---- per-term gather tables ----
-    std::vector<int> h_tL(T), h_tR(T);
-    std::vector<double> h_tlam(d->term_lambda, d->term_lambda + T);
-    std::vector<i64> h_ayidx(T);
-    // the kernel wants the terms of a block sorted by p (CSR over p); build a permutation per block
-    std::vector<i64> perm(T);
-    std::vector<std::vector<int>> h_tptr(NB);
-    for (int b = 0; b < NB; b++) {
-        BlockInfo &k = c->blk[b];
-        if (k.kind != 0) continue;
-        std::vector<i64> idx;
-        for (i64 t = k.t0; t < k.t1; t++) idx.push_back(t);
-        std::stable_sort(idx.begin(), idx.end(), [&](i64 a, i64 bb) { return d->term_p[a] < d->term_p[bb]; });
-        const int Pj = c->P[k.j];
-        h_tptr[b].assign(Pj + 1, 0);
-        for (size_t q = 0; q < idx.size(); q++) {
-            i64 t = idx[q];
-            perm[k.t0 + q] = t;
-            h_tptr[b][d->term_p[t] + 1]++;
-        }
-        for (int p = 0; p < Pj; p++) h_tptr[b][p + 1] += h_tptr[b][p];
-        for (i64 t = k.t0; t < k.t1; t++) {
-            int r = d->term_r[t], s = d->term_s[t];
-            // A_Y[t] = bpY[r,s][pointers_left[r][(s,p,k)], pointers_right[s][(r,p,k)]]  (src/solver.jl:1163)
-            i64 gl = k.offL[r] + lidx[t], gr = k.offR[s] + ridx[partner[t]];
-            if (g_cfg_pairing_tri && k.sym && k.m == 1 && k.ULt == k.URt && gl < gr) std::swap(gl, gr);   // only the lower triangle of the symmetric GY is formed
-            h_ayidx[t] = k.g_off + (i64)k.ULt * k.URt + gl + gr * k.ULt;
-        }
-    }
-    std::vector<int> s_tL(T), s_tR(T);
-    std::vector<double> s_tlam(T);
-    for (int b = 0; b < NB; b++) {
-        BlockInfo &k = c->blk[b];
-        if (k.kind != 0) continue;
-        for (i64 q = k.t0; q < k.t1; q++) {
-            i64 t = perm[q];
-            s_tL[q] = k.offL[d->term_s[t]] + lidx[partner[t]];   // pointers_left[s][(r,p,k)]
-            s_tR[q] = k.offR[d->term_r[t]] + ridx[t];            // pointers_right[r][(s,p,k)]
-            s_tlam[q] = d->term_lambda[t];
-        }
-    }
-    int *d_tL, *d_tR; double *d_tlam;
-    CK(upload(c, s_tL, &d_tL)); CK(upload(c, s_tR, &d_tR)); CK(upload(c, s_tlam, &d_tlam));
-    for (int b = 0; b < NB; b++) {
-        BlockInfo &k = c->blk[b];
-        if (k.kind == 0) {
-            if (k.t1 == k.t0) continue;
-            for (int &v : h_tptr[b]) v += (int)k.t0;   // absolute positions in the sorted term arrays
-            CK(upload(c, h_tptr[b], &k.d_tptr));
-        } else if (k.cnt > 0) {
-            std::vector<int> dp(d->dense_p + k.d0, d->dense_p + k.d1);
-            CK(upload(c, dp, &k.d_tptr));
-        }
-    }
-
-    // ---- which clusters does the fused kernel take?  (everything of the cluster must fit in LDS) ----
-    c->cluster_fused.assign(J, 0);
-    // ---- k_cluster_assemble_w5: clusters whose PSD blocks are all 2 x 2 blocks of 16 x 16 sub-blocks with constraint matrices E_rs (x) v_u v_u^T on the SAME
-    //      U <= 32 vectors in (0,0), (1,1) and as the two terms (0,1) + (1,0): 3 U constraints, every (pair, u) once (Nsphere_packing; clrs_assemble_w5.hip.h) ----
-    std::vector<W3Block> w5b;
-    std::vector<int> w5_cl_blk0, w5_ay;
-    std::vector<double> w5_lam, w5_vop;
-    if (g_cfg_fused_assemble && g_cfg_wave_assemble && g_cfg_wave5_assemble) {
-        int b = 0;
-        for (int j = 0; j < J; j++) {
-            const int b_first = b;
-            int b_end = b;
-            while (b_end < NB && c->blk[b_end].j == j) b_end++;
-            b = b_end;
-            const int Pj = c->P[j];
-            if (Pj < 3 || Pj % 3 != 0 || Pj > 96) continue;
-            const int U = Pj / 3;
-            bool ok = true;
-            int nlr = 0;
-            std::vector<int> pm0;
-            struct Blk5 { std::vector<int> ay; std::vector<double> lam; };
-            std::vector<Blk5> b5;
-            for (int bb = b_first; bb < b_end && ok; bb++) {
-                const BlockInfo &k = c->blk[bb];
-                if (k.kind != 0) { if (k.cnt > 0) ok = false; continue; }
-                const int Tn = (int)(k.t1 - k.t0);
-                if (Tn == 0) continue;
-                if (k.m != 2 || k.delta != 16 || !k.sym || Tn != 4 * U || (int)k.UR.size() != 2 || k.UR[0] != U || k.UR[1] != U) { ok = false; break; }
-                // the same vectors in both sub-blocks
-                const double *V = h_static.data() + k.zr_off;
-                for (int u = 0; u < U && ok; u++)
-                    for (int i2 = 0; i2 < 16; i2++)
-                        if (V[i2 + (i64)(k.offR[0] + u) * k.n] != V[16 + i2 + (i64)(k.offR[1] + u) * k.n]) { ok = false; break; }
-                if (!ok) break;
-                Blk5 e;
-                e.ay.assign(4 * 32, -1);
-                e.lam.assign(3 * U, 0.0);
-                std::vector<int> pm(3 * U, -1), seen_terms(4 * U, 0);
-                for (i64 q = k.t0; q < k.t1 && ok; q++) {
-                    const i64 t = perm[q];
-                    const int r = d->term_r[t], s2 = d->term_s[t];
-                    if (r < 0 || r > 1 || s2 < 0 || s2 > 1) { ok = false; break; }
-                    const int uR = s_tR[q] - k.offR[r], uL = s_tL[q] - k.offL[s2];
-                    if (uR != uL || uR < 0 || uR >= U) { ok = false; break; }
-                    const int pair = r + s2;                              // 0: (0,0); 1: (0,1) and (1,0); 2: (1,1)
-                    const int vi = pair * U + uR, ti2 = (2 * r + s2) * U + uR;
-                    if (seen_terms[ti2]++) { ok = false; break; }
-                    const int pc = d->term_p[t];
-                    const double lm = d->term_lambda[t];
-                    if (pm[vi] < 0) { pm[vi] = pc; e.lam[vi] = lm; }
-                    else if (pm[vi] != pc || e.lam[vi] != lm) { ok = false; break; }      // the two terms of an off-diagonal pair: one constraint, one lambda
-                    e.ay[(2 * r + s2) * 32 + uR] = (int)t;
-                }
-                if (!ok) break;
-                for (int i2 = 0; i2 < 4 * U; i2++) if (seen_terms[i2] != 1) ok = false;
-                std::vector<int> seen(pm);
-                std::sort(seen.begin(), seen.end());
-                for (int i2 = 0; i2 < 3 * U && ok; i2++) if (seen[i2] != i2) ok = false;      // a permutation of the cluster's constraints
-                if (!ok) break;
-                if (pm0.empty()) pm0 = pm;
-                else if (pm != pm0) { ok = false; break; }
-                b5.push_back(e);
-                nlr++;
-            }
-            if (!ok || nlr == 0) continue;
-            bool ident = true;
-            for (int u = 0; u < 3 * U; u++) if (pm0[u] != u) ident = false;
-            if (!ident) continue;                          // (constraints in pair-major vector order only: a table lookup per stored entry costs the kernel its registers)
-            w5_cl_blk0.push_back((int)w5b.size());
-            int ilr = 0;
-            for (int bb = b_first; bb < b_end; bb++) {
-                const BlockInfo &k = c->blk[bb];
-                if (k.kind != 0 || k.t1 == k.t0) continue;
-                W3Block k5;
-                std::memset(&k5, 0, sizeof(k5));
-                k5.xyoff = k.xyoff; k5.n = k.n; k5.U = U; k5.pmap_identity = 1;
-                k5.ndense = ilr == 0 ? 1 : 0;              // (first block of its cluster: it stores S_j, the others add to it)
-                k5.S_off = c->Soff[j];                     // (every block of the cluster writes S_j: it accumulates in memory)
-                k5.lam_off = (int)w5_lam.size();
-                w5_lam.insert(w5_lam.end(), b5[ilr].lam.begin(), b5[ilr].lam.end());
-                k5.ay_base = (int)w5_ay.size();
-                w5_ay.insert(w5_ay.end(), b5[ilr].ay.begin(), b5[ilr].ay.end());
-                ilr++;
-                k5.vop_off = (int)(w5_vop.size() / 512);
-                w5_vop.resize(w5_vop.size() + 512, 0.0);
-                double *dst = w5_vop.data() + (size_t)k5.vop_off * 512;
-                const double *V = h_static.data() + k.zr_off;
-                for (int t = 0; t < 2; t++)
-                    for (int q = 0; q < 4; q++)
-                        for (int ln = 0; ln < 64; ln++) {
-                            const int row = 4 * q + (ln >> 4), col = 16 * t + (ln & 15);
-                            if (col < U) dst[((t * 2 + (q >> 1)) * 64 + ln) * 2 + (q & 1)] = V[row + (i64)(k.offR[0] + col) * k.n];
-                        }
-                w5b.push_back(k5);
-            }
-            W3Block &kl = w5b.back();
-            kl.last = 1; kl.S_off = c->Soff[j];
-            c->cluster_fused[j] = 5;
-            for (int bb = b_first; bb < b_end; bb++) c->blk[bb].fused = true;
-        }
-    }
-    c->n_wave5_clusters = (int)w5_cl_blk0.size();
-    // ---- k_cluster_assemble_w4: clusters whose low-rank blocks are all "simple" (one sub-block, rank-1 symmetric terms, one term per constraint, U = P, the
-    //      same constraint order in every block) with n <= 32 and P <= 64, dense blocks 1 x 1, and at least one block beyond the reach of
-    //      k_cluster_assemble_w3 (n > 16 or P > 32): the register-resident kernel of clrs_assemble_w4.hip.h ----
-    std::vector<W3Block> w4b;
-    std::vector<W3Dense> w4d;
-    std::vector<int> w4_cl_blk0, w4_pmap, w4_ay;
-    std::vector<double> w4_lam, w4_vop;
-    int w4_nu = 0;
-    if (g_cfg_fused_assemble && g_cfg_wave_assemble && g_cfg_wave4_assemble) {
-        int b = 0;
-        for (int j = 0; j < J; j++) {
-            const int b_first = b;
-            int b_end = b;
-            while (b_end < NB && c->blk[b_end].j == j) b_end++;
-            b = b_end;
-            const int Pj = c->P[j];
-            if (Pj < 1 || Pj > 64 || c->cluster_fused[j] != 0) continue;
-            bool ok = true, beyond_w3 = Pj > 32;
-            int nlr = 0;
-            std::vector<int> pm0;
-            std::vector<std::vector<int>> ays;
-            std::vector<std::vector<double>> lams;
-            for (int bb = b_first; bb < b_end && ok; bb++) {
-                const BlockInfo &k = c->blk[bb];
-                if (k.kind == 0) {
-                    const int Tn = (int)(k.t1 - k.t0);
-                    if (Tn == 0) continue;
-                    if (k.m != 1 || k.n > 32 || !k.sym || k.URt != Tn || Tn != Pj) { ok = false; break; }
-                    std::vector<int> pm(Tn, -1), ay(Tn, -1);
-                    std::vector<double> lam(Tn, 0.0);
-                    for (i64 q = k.t0; q < k.t1 && ok; q++) {
-                        const i64 t = perm[q];
-                        const int u = s_tR[q];
-                        if (s_tL[q] != u || u < 0 || u >= Tn || pm[u] >= 0) { ok = false; break; }
-                        pm[u] = d->term_p[t]; lam[u] = d->term_lambda[t]; ay[u] = (int)t;
-                    }
-                    if (!ok) break;
-                    std::vector<int> seen(pm);
-                    std::sort(seen.begin(), seen.end());
-                    for (int i2 = 0; i2 < Tn; i2++) if (seen[i2] != i2) ok = false;      // a permutation of the cluster's constraints
-                    if (!ok) break;
-                    if (pm0.empty()) pm0 = pm;
-                    else if (pm != pm0) { ok = false; break; }
-                    if (k.n > 16) beyond_w3 = true;
-                    ays.push_back(ay); lams.push_back(lam);
-                    nlr++;
-                } else if (k.cnt > 0 && k.n != 1) ok = false;
-            }
-            if (!ok || nlr == 0 || !beyond_w3) continue;
-            std::vector<int> inv(Pj, -1);
-            for (int u = 0; u < Pj; u++) inv[pm0[u]] = u;
-            const int nu = (Pj + 15) / 16 <= 3 ? 3 : 4;
-            w4_nu = std::max(w4_nu, nu);
-            w4_cl_blk0.push_back((int)w4b.size());
-            const int pm_off = (int)w4_pmap.size();
-            w4_pmap.insert(w4_pmap.end(), pm0.begin(), pm0.end());
-            bool ident = true;
-            for (int u = 0; u < Pj; u++) if (pm0[u] != u) ident = false;
-            const int dense0 = (int)w4d.size();
-            size_t last_lr = 0;
-            int ilr = 0;
-            for (int bb = b_first; bb < b_end; bb++) {
-                const BlockInfo &k = c->blk[bb];
-                if (k.kind != 0) {
-                    if (k.cnt == 0) continue;
-                    W3Dense de; de.xyoff = k.xyoff; de.lam_off = (int)w4_lam.size(); de.pad = 0;
-                    std::vector<double> a(Pj, 0.0);
-                    for (i64 e = k.d0; e < k.d1; e++) a[inv[d->dense_p[e]]] = d->dense_A[d->dense_A_ptr[e]];
-                    w4_lam.insert(w4_lam.end(), a.begin(), a.end());
-                    w4d.push_back(de);
-                    continue;
-                }
-                if (k.t1 == k.t0) continue;
-                W3Block k4;
-                std::memset(&k4, 0, sizeof(k4));
-                k4.xyoff = k.xyoff; k4.n = k.n; k4.U = Pj; k4.pmap_off = pm_off; k4.pmap_identity = ident ? 1 : 0;
-                k4.lam_off = (int)w4_lam.size();
-                w4_lam.insert(w4_lam.end(), lams[ilr].begin(), lams[ilr].end());
-                k4.ay_base = (int)w4_ay.size();
-                w4_ay.insert(w4_ay.end(), ays[ilr].begin(), ays[ilr].end());
-                ilr++;
-                k4.vop_off = (int)(w4_vop.size() / 512);
-                w4_vop.resize(w4_vop.size() + (size_t)4 * 512, 0.0);      // (four column tiles for every block: the launch's NU is the largest of its clusters')
-                double *dst = w4_vop.data() + (size_t)k4.vop_off * 512;
-                const double *V = h_static.data() + k.zr_off;
-                for (int t = 0; t < nu; t++)
-                    for (int q = 0; q < 8; q++)
-                        for (int ln = 0; ln < 64; ln++) {
-                            const int row = 4 * q + (ln >> 4), col = 16 * t + (ln & 15);
-                            if (row < k.n && col < Pj) dst[((t * 4 + (q >> 1)) * 64 + ln) * 2 + (q & 1)] = V[row + (i64)col * k.n];
-                        }
-                last_lr = w4b.size();
-                w4b.push_back(k4);
-            }
-            W3Block &kl = w4b[last_lr];
-            kl.last = 1; kl.S_off = c->Soff[j];
-            kl.ndense = (int)w4d.size() - dense0; kl.dense0 = dense0;
-            c->cluster_fused[j] = 4;
-            for (int bb = b_first; bb < b_end; bb++) c->blk[bb].fused = true;
-        }
-    }
-    c->n_wave4_clusters = (int)w4_cl_blk0.size();
-    // ---- wave-per-block assembly (k_cluster_assemble_w1): clusters made of "simple" rank-1 blocks with n <= 16 and small dense blocks ----
-    std::vector<WCluster> wcl;
-    std::vector<WBlock> wbl;
-    std::vector<int> w_pmap, w_ay;
-    std::vector<double> w_lam;
-    std::vector<size_t> w_ioff;       // per WBlock: offset of its pmap / lam / ay entries in the packed arrays
-    std::vector<size_t> w_cl_first;   // per WCluster: its first WBlock
-    std::vector<W2Cluster> w2cl;      // cluster-per-wave kernel
-    std::vector<W2Block> w2bl;
-    std::vector<int> w2_pmap, w2_ay;
-    std::vector<double> w2_lam;
-    std::vector<size_t> w2_cl_pm, w2_boff, w2_bl_cl;
-    int w2_ut = 0;
-    int w_ut = 0, w_nwaves = 8, w_maxblocks = 0;
-    size_t w_cluster_doubles = 0;
-    if (g_cfg_fused_assemble && g_cfg_wave_assemble) {
-        int b = 0;
-        for (int j = 0; j < J; j++) {
-            const int b_first = b;
-            bool ok = c->cluster_fused[j] == 0;      // (not taken by k_cluster_assemble_w4)
-            int work = 0, ut = 1, nblk = 0;
-            std::vector<WBlock> mine;
-            std::vector<size_t> mine_off;
-            const size_t keep_pm = w_pmap.size(), keep_lam = w_lam.size(), keep_ay = w_ay.size();
-            for (; b < NB && c->blk[b].j == j; b++) {
-                BlockInfo &k = c->blk[b];
-                if (!ok) continue;
-                WBlock wb;
-                std::memset(&wb, 0, sizeof(wb));
-                wb.kind = k.kind; wb.n = k.n; wb.xyoff = k.xyoff;
-                if (k.kind == 0) {
-                    const int Tn = (int)(k.t1 - k.t0);
-                    if (Tn == 0) continue;
-                    if (k.m != 1 || k.n > 16 || !k.sym || k.URt != Tn || Tn > 128) { ok = false; continue; }
-                    std::vector<int> pm(Tn, -1), ay(Tn, -1);
-                    std::vector<double> lam(Tn, 0.0);
-                    for (i64 q = k.t0; q < k.t1 && ok; q++) {
-                        const i64 t = perm[q];
-                        const int u = s_tR[q];
-                        if (s_tL[q] != u || u < 0 || u >= Tn || pm[u] >= 0) { ok = false; break; }
-                        pm[u] = d->term_p[t]; lam[u] = d->term_lambda[t]; ay[u] = (int)t;
-                    }
-                    if (ok) {   // one term per constraint
-                        std::vector<int> seen(pm);
-                        std::sort(seen.begin(), seen.end());
-                        for (int i2 = 1; i2 < Tn; i2++) if (seen[i2] == seen[i2 - 1]) ok = false;
-                    }
-                    if (!ok) continue;
-                    wb.U = Tn; wb.v_off = k.zr_off;
-                    mine_off.push_back(w_pmap.size());
-                    w_pmap.insert(w_pmap.end(), pm.begin(), pm.end());
-                    w_ay.insert(w_ay.end(), ay.begin(), ay.end());
-                    w_lam.resize(w_pmap.size(), 0.0);
-                    std::copy(lam.begin(), lam.end(), w_lam.end() - Tn);
-                    ut = std::max(ut, (Tn + 15) / 16);
-                } else {
-                    if (k.cnt == 0) continue;
-                    const int need = 2 * k.n * k.n + 3 * k.cnt * k.n * k.n;
-                    if (k.n > 16 || need > 4096) { ok = false; continue; }
-                    wb.U = k.cnt; wb.v_off = k.w_off;
-                    mine_off.push_back(w_pmap.size());
-                    for (i64 e = k.d0; e < k.d1; e++) { w_pmap.push_back(d->dense_p[e]); w_ay.push_back(0); }
-                    w_lam.resize(w_pmap.size(), 0.0);
-                    work = std::max(work, need);
-                }
-                mine.push_back(wb);
-                nblk++;
-            }
-            const int utr = ut <= 2 ? 2 : ut <= 4 ? 4 : 8;
-            work = std::max(work, 2 * 17 * 16 * utr);
-            const i64 per_wave = (i64)c->P[j] * (c->P[j] | 1) + work;     // slab (odd leading dimension) + work area
-            if (!ok || mine.empty() || per_wave > LDS_BUDGET_DOUBLES) {
-                w_pmap.resize(keep_pm); w_lam.resize(keep_lam); w_ay.resize(keep_ay);
-                continue;
-            }
-            // cluster-per-wave kernel: every low-rank block uses the same constraint order (U = P) and the dense blocks are 1 x 1
-            // ("wave2_assemble" = 1: automatic, 2: always, 0: never.  Automatic: always when the register-resident kernel
-            // k_cluster_assemble_w3 applies (U <= 32) -- it is also the fastest form for a handful of clusters, 8 us against 12.5 us of
-            // the wave-per-block kernel on cohnelkies(8,15) -- and from 64 clusters on for the LDS-staged k_cluster_assemble_w2,
-            // which walks the blocks of a cluster one after the other and needs enough clusters to fill the chip)
-            if ((g_cfg_wave2_assemble == 2 || (g_cfg_wave2_assemble == 1 && (J >= 64 || (g_cfg_wave3_assemble && utr <= 2)))) && utr <= 4) {
-                const int Pj = c->P[j];
-                bool w2 = true;
-                const int *pm0 = nullptr;
-                for (size_t i2 = 0; i2 < mine.size() && w2; i2++) {
-                    const WBlock &wb = mine[i2];
-                    if (wb.kind == 0) {
-                        const int *pm = w_pmap.data() + mine_off[i2];
-                        if (wb.U != Pj) w2 = false;
-                        else if (!pm0) pm0 = pm;
-                        else if (std::memcmp(pm, pm0, sizeof(int) * Pj) != 0) w2 = false;
-                    } else if (wb.n != 1) w2 = false;
-                }
-                if (w2 && pm0) {
-                    std::vector<int> inv(Pj, -1);
-                    for (int u = 0; u < Pj; u++) inv[pm0[u]] = u;
-                    W2Cluster wc2;
-                    std::memset(&wc2, 0, sizeof(wc2));
-                    wc2.S = c->d_S + c->Soff[j]; wc2.P = Pj; wc2.nblk = (int)mine.size(); wc2.blk0 = (i64)w2bl.size();
-                    w2_cl_pm.push_back(w2_pmap.size());
-                    w2_pmap.insert(w2_pmap.end(), pm0, pm0 + Pj);
-                    int bsel = b_first;
-                    for (size_t i2 = 0; i2 < mine.size(); i2++) {
-                        const WBlock &wb = mine[i2];
-                        W2Block q2;
-                        std::memset(&q2, 0, sizeof(q2));
-                        q2.kind = wb.kind; q2.n = wb.n; q2.xyoff = wb.xyoff; q2.v_off = wb.v_off;
-                        w2_boff.push_back(w2_lam.size());
-                        w2_bl_cl.push_back(w2cl.size());
-                        if (wb.kind == 0) {
-                            w2_lam.insert(w2_lam.end(), w_lam.begin() + mine_off[i2], w_lam.begin() + mine_off[i2] + Pj);
-                            w2_ay.insert(w2_ay.end(), w_ay.begin() + mine_off[i2], w_ay.begin() + mine_off[i2] + Pj);
-                        } else {
-                            // locate the BlockInfo of this dense block to read its 1 x 1 matrices
-                            while (!(c->blk[bsel].kind != 0 && c->blk[bsel].xyoff == wb.xyoff)) bsel++;
-                            const BlockInfo &kb = c->blk[bsel];
-                            std::vector<double> a(Pj, 0.0);
-                            for (i64 e = kb.d0; e < kb.d1; e++) a[inv[d->dense_p[e]]] = d->dense_A[d->dense_A_ptr[e]];
-                            w2_lam.insert(w2_lam.end(), a.begin(), a.end());
-                            w2_ay.insert(w2_ay.end(), Pj, 0);
-                        }
-                        w2bl.push_back(q2);
-                    }
-                    w2cl.push_back(wc2);
-                    w2_ut = std::max(w2_ut, utr);
-                    c->cluster_fused[j] = 3;
-                    for (int bb = b_first; bb < b; bb++) c->blk[bb].fused = true;
-                    w_pmap.resize(keep_pm); w_lam.resize(keep_lam); w_ay.resize(keep_ay);
-                    continue;
-                }
-            }
-            WCluster wc;
-            std::memset(&wc, 0, sizeof(wc));
-            wc.S = c->d_S + c->Soff[j]; wc.P = c->P[j]; wc.nblk = (int)mine.size(); wc.work_doubles = work;
-            w_cl_first.push_back(wbl.size());
-            for (size_t i2 = 0; i2 < mine.size(); i2++) { wbl.push_back(mine[i2]); w_ioff.push_back(mine_off[i2]); }
-            wcl.push_back(wc);
-            c->cluster_fused[j] = 2;
-            for (int bb = b_first; bb < b; bb++) c->blk[bb].fused = true;
-            w_ut = std::max(w_ut, utr);
-            w_nwaves = std::min(w_nwaves, (int)(LDS_BUDGET_DOUBLES / per_wave));
-            w_maxblocks = std::max(w_maxblocks, nblk);
-            w_cluster_doubles = std::max(w_cluster_doubles, (size_t)per_wave);
-        }
-        w_nwaves = std::max(1, std::min(w_nwaves, std::max(w_maxblocks, 1)));
-        for (WCluster &wc : wcl) wc.work_doubles = (int)(w_cluster_doubles - (size_t)wc.P * (wc.P | 1));   // one slab + work stride for all clusters
-        // a cluster whose own P^2 + work is smaller still gets the common stride; re-check the budget with it
-        if ((i64)w_nwaves * (i64)w_cluster_doubles > LDS_BUDGET_DOUBLES) w_nwaves = std::max(1, (int)(LDS_BUDGET_DOUBLES / (i64)w_cluster_doubles));
-    }
-    c->n_wave_clusters = (int)wcl.size();
-    c->n_wave2_clusters = (int)w2cl.size();
-    std::vector<FCluster> fcl;
-    std::vector<int> fcl_cluster;
-    std::vector<SSlabSum> fsum;
-    std::vector<FBlock> fbl;
-    int fused_nmax = 0;
-    size_t fused_lds = 0;
-    if (g_cfg_fused_assemble) {
-        int b = 0;
-        for (int j = 0; j < J; j++) {
-            const int b_first = b;
-            int szL = 0, szY = 0, szV = 0, szTY = 0, szZL = 0, szG = 0, szTab = 0, nmax = 0;
-            bool ok = c->cluster_fused[j] == 0;      // not already taken by the wave-per-block kernel
-            std::vector<FBlock> mine;
-            for (; b < NB && c->blk[b].j == j; b++) {
-                BlockInfo &k = c->blk[b];
-                if (!ok) continue;
-                FBlock fb;
-                std::memset(&fb, 0, sizeof(fb));
-                fb.kind = k.kind; fb.n = k.n; fb.xyoff = k.xyoff;
-                const int n = k.n, n16 = (n + 15) & ~15;
-                if (k.kind == 0) {
-                    if (k.t1 == k.t0) continue;
-                    if (n > 64) { ok = false; continue; }
-                    const int UR16 = (k.URt + 15) & ~15, UL16 = (k.ULt + 15) & ~15, Tn = (int)(k.t1 - k.t0);
-                    fb.URt = k.URt; fb.ULt = k.ULt; fb.sym = k.sym ? 1 : 0; fb.T = Tn;
-                    fb.ldn = n16 + 2;                    // >= ceil16(n) rows (zero padded), ldn % 4 == 2: conflict-free ds_read_b64 of the MFMA operands
-                    fb.ldg = k.ULt | 1;
-                    fb.v_off = k.zr_off; fb.w_off = k.zl_off; fb.t0 = k.t0; fb.tptr = k.d_tptr;
-                    szL = std::max(szL, fb.ldn * n16); szY = std::max(szY, fb.ldn * n16);
-                    szV = std::max(szV, fb.ldn * UR16); szTY = std::max(szTY, fb.ldn * UR16);
-                    if (!k.sym) szZL = std::max(szZL, fb.ldn * UL16);
-                    szG = std::max(szG, fb.ldg * k.URt);
-                    szTab = std::max(szTab, ((c->P[j] + 1 + 2 * Tn + 1) & ~1) / 2 + Tn);
-                    nmax = std::max(nmax, n);
-                } else {
-                    if (k.cnt == 0) continue;
-                    if (n > 16) { ok = false; continue; }
-                    fb.T = k.cnt; fb.ldn = n | 1; fb.v_off = k.w_off; fb.tptr = k.d_tptr;
-                    const int st = k.cnt * n * n;
-                    szL = std::max(szL, fb.ldn * n); szY = std::max(szY, fb.ldn * n);
-                    szV = std::max(szV, st); szTY = std::max(szTY, st); szG = std::max(szG, st);
-                    szTab = std::max(szTab, (k.cnt + 1) / 2);
-                }
-                mine.push_back(fb);
-            }
-            if (!ok || mine.empty()) continue;
-            FCluster fc;
-            std::memset(&fc, 0, sizeof(fc));
-            fc.S = c->d_S + c->Soff[j]; fc.P = c->P[j];
-            auto even = [](int v) { return (v + 1) & ~1; };   // keep every region 16-byte aligned
-            int o = 0;
-            fc.oL = o; o += even(szL); fc.oY = o; o += even(szY); fc.oV = o; o += even(szV); fc.oTY = o; o += even(szTY);
-            fc.oZL = o; o += even(szZL); fc.oGX = o; o += even(szG); fc.oGY = o; o += even(szG); fc.oTab = o; o += even(szTab);
-            if (o > LDS_BUDGET_DOUBLES) continue;
-            const int PP = c->P[j] * c->P[j];
-            fc.oS = o;
-            if (o + PP <= LDS_BUDGET_DOUBLES) { fc.s_in_lds = 1; o += even(PP); }
-            fc.lds_doubles = o;
-            fc.b0 = (int)fbl.size();
-            for (const FBlock &fb : mine) fbl.push_back(fb);
-            fc.b1 = (int)fbl.size();
-            fcl.push_back(fc);
-            fcl_cluster.push_back(j);
-            c->cluster_fused[j] = 1;
-            for (int bb = b_first; bb < b; bb++) c->blk[bb].fused = true;
-            fused_nmax = std::max(fused_nmax, nmax);
-            fused_lds = std::max(fused_lds, (size_t)o * sizeof(double));
-        }
-    }
-    c->n_fused_clusters = (int)fcl.size() + (int)wcl.size() + (int)w2cl.size() + c->n_wave4_clusters + c->n_wave5_clusters;
-    // Few clusters with several blocks each: the blocks of a cluster are independent until their contributions meet in S_j.  One
-    // workgroup per block (groups of blocks beyond 32 per cluster) writes its contribution as a P x P slab, k_sum_S_slabs adds
-    // the slabs in block order -- the same additions in the same order as the one-workgroup form, so S_j is bit-identical.
-    if (g_cfg_split_blocks && !fcl.empty() && fcl.size() <= 32) {
-        std::vector<FCluster> split;
-        std::vector<int> split_sum;                // per entry of `split`: its sum descriptor, or -1
-        i64 slab_doubles = 0;
-        for (size_t i = 0; i < fcl.size(); i++) {
-            const FCluster &fc = fcl[i];
-            const int nb = fc.b1 - fc.b0, groups = std::min(nb, 32);
-            if (nb < 2) { split.push_back(fc); split_sum.push_back(-1); continue; }
-            SSlabSum ss;
-            ss.out = fc.S; ss.slabs = nullptr; ss.len = (i64)fc.P * fc.P; ss.nslabs = groups; ss.pad = (int)slab_doubles;      // offset for now (fits: few small clusters)
-            for (int g = 0; g < groups; g++) {
-                FCluster part = fc;
-                part.b0 = fc.b0 + (int)((i64)g * nb / groups);
-                part.b1 = fc.b0 + (int)((i64)(g + 1) * nb / groups);
-                part.S = nullptr;                       // patched below: slab g of this cluster
-                split.push_back(part);
-                split_sum.push_back((int)fsum.size());
-            }
-            slab_doubles += ss.len * groups;
-            fsum.push_back(ss);
-        }
-        if (!fsum.empty()) {
-            double *dslabs;
-            CK(dmalloc(c, &dslabs, slab_doubles));
-            std::vector<int> used(fsum.size(), 0);
-            for (size_t i = 0; i < split.size(); i++)
-                if (split_sum[i] >= 0) {
-                    const int si = split_sum[i];
-                    split[i].S = dslabs + fsum[si].pad + fsum[si].len * used[si]++;
-                }
-            for (SSlabSum &ss : fsum) { ss.slabs = dslabs + ss.pad; ss.pad = 0; }
-            fcl.swap(split);
-        }
-    }
-    for (int b = 0; b < NB; b++)
-        if (c->blk[b].fused && c->blk[b].kind == 0)
-            for (i64 t = c->blk[b].t0; t < c->blk[b].t1; t++) h_ayidx[t] = -1;   // written by the fused kernel
-    CK(upload(c, h_ayidx, &c->d_ayidx));
-    std::vector<int> h_ayL(T), h_ayR(T);
-    for (int b = 0; b < NB; b++) {
-        BlockInfo &k = c->blk[b];
-        if (k.kind != 0) continue;
-        for (i64 t = k.t0; t < k.t1; t++) {
-            h_ayL[t] = k.offL[d->term_r[t]] + lidx[t];
-            h_ayR[t] = k.offR[d->term_s[t]] + ridx[partner[t]];
-        }
-    }
-    int *d_ayL, *d_ayR;
-    CK(upload(c, h_ayL, &d_ayL)); CK(upload(c, h_ayR, &d_ayR));
-    c->d_ayL = d_ayL; c->d_ayR = d_ayR;
-    c->h_term_p.assign(d->term_p, d->term_p + T); c->h_term_lambda.assign(d->term_lambda, d->term_lambda + T);
-    c->h_dense_p.assign(d->dense_p, d->dense_p + c->D);
-
-    // =============================================================================================
-    // plan: assemble
-    // =============================================================================================
-    {
-        Plan &pl = c->p_assemble;
-        bool need_copy = false;
-        for (int b = 0; b < NB; b++) need_copy = need_copy || !c->blk[b].fused;
-        c->all_assemble_fused = !need_copy;
-        // which of the non-fused blocks still need the work arena (a copy of the static arena that the staged solves overwrite)?
-        bool need_work_arena = false;
-        std::vector<DBlock> dblocks;
-        size_t dense_lds = 0;
-        const size_t copy_step_index = pl.steps.size();
-        if (need_copy) add_memcpy(pl, c->d_work, c->d_static, sizeof(double) * (size_t)so);
-        std::vector<TrsmJob> fwd, bwd;
-        std::vector<DenseTBlock> dtb;                       // dense blocks taken by k_dense_T32
-        std::vector<DenseTPair> dtp;
-        std::vector<GemmDesc> g1, g2;
-        bool any_general = false;
-        for (int b = 0; b < NB; b++) {
-            BlockInfo &k = c->blk[b];
-            const double *Lx = c->d_Xc + k.xyoff, *Yb = c->d_Y + k.xyoff;
-            const int n = k.n, dl = k.delta;
-            if (k.fused) continue;
-            any_general = true;
-            if (k.kind == 0) {
-                need_work_arena = true;
-                double *ZR = c->d_work + k.zr_off, *ZL = c->d_work + k.zl_off, *TY = c->d_TY + k.ty_off;
-                double *GX = c->d_G + k.g_off, *GY = GX + (i64)k.ULt * k.URt;
-                const double *VR = c->d_static + k.zr_off, *WL = c->d_static + k.zl_off;
-                for (int r = 0; r < k.m; r++) {
-                    const int r0 = r * dl;
-                    // columns of sub-block row r are zero above row r0: solve with the trailing triangle only
-                    if (k.UR[r] > 0) fwd.push_back(TrsmJob{Lx + r0 + (i64)r0 * n, n, n - r0, ZR + r0 + (i64)k.offR[r] * n, n, k.UR[r]});
-                    if (!k.sym && k.UL[r] > 0) fwd.push_back(TrsmJob{Lx + r0 + (i64)r0 * n, n, n - r0, ZL + r0 + (i64)k.offL[r] * n, n, k.UL[r]});
-                    // T_Y[:, cols r] = Y[:, r-block] V_r            (src/solver.jl:1125)
-                    if (k.UR[r] > 0)
-                        g1.push_back(mk_gemm(0, 0, n, k.UR[r], dl, 1.0, Yb + (i64)r0 * n, n, VR + r0 + (i64)k.offR[r] * n, n, 0.0, TY + (i64)k.offR[r] * n, n));
-                }
-                // W = V in one sub-block: GX = V^T X^-1 V and GY = V^T Y V are symmetric -- lower tiles only, the gather mirrors its reads
-                const int tri = g_cfg_pairing_tri && k.sym && k.m == 1 && k.ULt == k.URt ? 1 : 0;
-                for (int s = 0; s < k.m; s++)  // GY[rows s, :] = W_s^T T_Y[s-block, :]   (src/solver.jl:1131)
-                    if (k.UL[s] > 0 && k.URt > 0)
-                        g2.push_back(mk_gemm(1, 0, k.UL[s], k.URt, dl, 1.0, WL + s * dl + (i64)k.offL[s] * n, n, TY + s * dl, n, 0.0, GY + k.offL[s], k.ULt, 1, 0, 0, 0, tri));
-                // GX = ZL^T ZR = W^T X^-1 V       (replaces src/solver.jl:1117,1137-1143)
-                if (k.ULt > 0 && k.URt > 0) g2.push_back(mk_gemm(1, 0, k.ULt, k.URt, n, 1.0, ZL, n, ZR, n, 0.0, GX, k.ULt, 1, 0, 0, 0, tri));
-            } else if (k.cnt > 0) {
-                {   // dense block that fits in LDS: one fused launch for all such blocks
-                    const size_t n16 = (n + 15) & ~15, msz = (n16 + 2) * n16, need = 2 * msz + n16 + 2 * (size_t)k.cnt * msz + 1024;
-                    if (g_cfg_dense_block && g_cfg_fused_assemble && n <= 64 && need <= (size_t)LDS_BUDGET_DOUBLES) {
-                        DBlock db;
-                        db.n = n; db.cnt = k.cnt; db.xyoff = k.xyoff; db.a_off = k.w_off; db.Sd = c->d_Sd + k.sd_off;
-                        dblocks.push_back(db);
-                        dense_lds = std::max(dense_lds, need * sizeof(double));
-                        continue;
-                    }
-                }
-                if (g_cfg_dense_wave && n <= 32) {      // T_e = X^-1 A_e Y by one wave per matrix (k_dense_T32), then the same Gram GEMM
-                    double *TT = c->d_TT + k.tt_off, *Sd = c->d_Sd + k.sd_off;
-                    const double *Ast = c->d_static + k.w_off;
-                    const int bi = (int)dtb.size();
-                    dtb.push_back(DenseTBlock{Lx, Yb, Ast, nullptr, TT, n, k.cnt});
-                    for (int e0 = 0; e0 < k.cnt; e0 += DT32_WAVES * DT32_ITER) dtp.push_back(DenseTPair{bi, e0});
-                    k.sd_tri = g_cfg_pairing_tri != 0;      // <A_i, X^-1 A_k Y> = tr(A_i X^-1 A_k Y) is symmetric in (i, k): lower tiles, mirrored reads
-                    g2.push_back(mk_gemm(1, 0, k.cnt, k.cnt, n * n, 1.0, Ast, n * n, TT, n * n, 0.0, Sd, k.cnt, 1, 0, 0, 0, k.sd_tri ? 1 : 0));           // <A_i, T_k>   (:1102)
-                    continue;
-                }
-                need_work_arena = true;
-                double *W = c->d_work + k.w_off, *TT = c->d_TT + k.tt_off, *Sd = c->d_Sd + k.sd_off;
-                const double *Ast = c->d_static + k.w_off;
-                fwd.push_back(TrsmJob{Lx, n, n, W, n, n * k.cnt});      // X^-1 A_p for all p  (src/solver.jl:1095)
-                bwd.push_back(TrsmJob{Lx, n, n, W, n, n * k.cnt});
-                g1.push_back(mk_gemm(0, 0, n, n, n, 1.0, W, n, Yb, n, 0.0, TT, n, k.cnt, (i64)n * n, 0, (i64)n * n));  // (X^-1 A_p) Y  (:1097)
-                k.sd_tri = g_cfg_pairing_tri != 0;
-                g2.push_back(mk_gemm(1, 0, k.cnt, k.cnt, n * n, 1.0, Ast, n * n, TT, n * n, 0.0, Sd, k.cnt, 1, 0, 0, 0, k.sd_tri ? 1 : 0));           // <A_i, T_k>   (:1102)
-            }
-        }
-        if (need_copy && !need_work_arena) pl.steps.erase(pl.steps.begin() + copy_step_index);   // nothing left that overwrites it
-        CK(plan_trsm(c, pl, fwd, 0));
-        CK(plan_trsm(c, pl, bwd, 1));
-        CK(add_gemm_stage(c, pl, g1));
-        if (!dtb.empty()) {
-            double *linv = nullptr;
-            CK(dmalloc(c, &linv, (i64)dtb.size() * 1024));
-            for (size_t i = 0; i < dtb.size(); i++) dtb[i].Linv = linv + i * 1024;
-            DenseTBlock *dblk; DenseTPair *dpr;
-            CK(upload(c, dtb, &dblk));
-            CK(upload(c, dtp, &dpr));
-            Step s1;
-            s1.kind = STEP_TRTRI32; s1.grid = (int)dtb.size(); s1.d0 = dblk;
-            pl.steps.push_back(s1);
-            Step s2;
-            s2.kind = STEP_DENSE_T32; s2.grid = (int)dtp.size(); s2.d0 = dblk; s2.d1 = dpr;
-            pl.steps.push_back(s2);
-            HIPCK(hipFuncSetAttribute((const void *)k_dense_T32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dense_T32_lds_bytes()));
-        }
-        CK(add_gemm_stage(c, pl, g2));
-        if (!dblocks.empty()) {
-            DBlock *ddb;
-            CK(upload(c, dblocks, &ddb));
-            c->ftables.Xc = c->d_Xc; c->ftables.Y = c->d_Y; c->ftables.stat = c->d_static;
-            Step s;
-            s.kind = STEP_DENSE_BLOCK; s.grid = (int)dblocks.size(); s.d0 = ddb; s.src = &c->ftables; s.bytes = dense_lds;
-            pl.steps.push_back(s);
-            if (dense_lds > 64 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_dense_block, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dense_lds));
-        }
-        // gather
-        std::vector<SClusterDesc> cl(J);
-        std::vector<SBlockDesc> bl;
-        std::vector<STile> tiles;
-        int b = 0;
-        for (int j = 0; j < J; j++) {
-            cl[j].S = c->d_S + c->Soff[j]; cl[j].P = c->P[j]; cl[j].b0 = (int)bl.size(); cl[j].pad = 0;
-            for (; b < NB && c->blk[b].j == j; b++) {
-                BlockInfo &k = c->blk[b];
-                SBlockDesc sd;
-                std::memset(&sd, 0, sizeof(sd));
-                sd.kind = k.kind;
-                if (k.fused) continue;
-                if (k.kind == 0) {
-                    if (k.t1 == k.t0) continue;
-                    sd.ldg = k.ULt;
-                    sd.tri = g_cfg_pairing_tri && k.sym && k.m == 1 && k.ULt == k.URt ? 1 : 0;
-                    sd.GX = c->d_G + k.g_off; sd.GY = sd.GX + (i64)k.ULt * k.URt;
-                    sd.tptr = k.d_tptr; sd.tL = d_tL; sd.tR = d_tR; sd.tlam = d_tlam;
-                } else {
-                    if (k.cnt == 0) continue;
-                    sd.cnt = k.cnt; sd.Sd = c->d_Sd + k.sd_off; sd.tri = k.sd_tri ? 1 : 0;
-                    std::vector<int> inv(c->P[j], -1);
-                    for (i64 e = k.d0; e < k.d1; e++) inv[d->dense_p[e]] = (int)(e - k.d0);
-                    int *dinv;
-                    CK(upload(c, inv, &dinv));
-                    sd.inv = dinv;
-                }
-                bl.push_back(sd);
-            }
-            cl[j].b1 = (int)bl.size();
-            if (c->cluster_fused[j]) continue;
-            int nt = (c->P[j] + 15) / 16;
-            for (int tj = 0; tj < nt; tj++)
-                for (int ti = 0; ti <= tj; ti++) tiles.push_back(STile{j, ti, tj, 0});
-        }
-        if (!tiles.empty()) {
-            Step s;
-            s.kind = STEP_GATHER_S;
-            s.grid = (int)tiles.size();
-            for (const SClusterDesc &cd : cl) s.aux0 = std::max(s.aux0, cd.b1 - cd.b0);      // most blocks in one cluster
-            SClusterDesc *dcl; SBlockDesc *dbl; STile *dt;
-            CK(upload(c, cl, &dcl)); CK(upload(c, bl, &dbl)); CK(upload(c, tiles, &dt));
-            s.d0 = dcl; s.d1 = dbl; s.d2 = dt;
-            pl.steps.push_back(s);
-        }
-        if (T > 0 && any_general) {
-            Step s;
-            s.kind = STEP_GATHER_SCALAR;
-            s.dst = c->d_AY; s.src = c->d_G; s.d0 = c->d_ayidx; s.n = T;
-            pl.steps.push_back(s);
-        }
-        if (!w5b.empty()) {
-            int *dcb, *day; W3Block *db5; double *dvop, *dlam;
-            CK(upload(c, w5_cl_blk0, &dcb)); CK(upload(c, w5b, &db5)); CK(upload(c, w5_vop, &dvop));
-            CK(upload(c, w5_ay, &day)); CK(upload(c, w5_lam, &dlam));
-            c->w5tables.Xc = c->d_Xc; c->w5tables.Y = c->d_Y; c->w5tables.S = c->d_S; c->w5tables.AY = c->d_AY;
-            c->w5tables.vop = dvop; c->w5tables.lam = dlam; c->w5tables.ay = day;
-            c->ftables.Xc = c->d_Xc; c->ftables.Y = c->d_Y;
-            int cus = 256, dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-            Step s;
-            s.kind = STEP_ASSEMBLE_W5;
-            s.d0 = dcb; s.d1 = db5; s.src = &c->w5tables; s.n = (i64)w5_cl_blk0.size();
-            s.aux0 = (int)std::min<i64>(((i64)w5_cl_blk0.size() + 3) / 4, (i64)cus);
-            s.aux1 = (int)w5b.size();
-            pl.steps.push_back(s);
-        }
-        if (!w4b.empty()) {
-            if (w4d.empty()) { W3Dense de; std::memset(&de, 0, sizeof(de)); w4d.push_back(de); }
-            if (w4_ay.empty()) w4_ay.push_back(0);
-            int *dcb, *dpm, *day; W3Block *db4; W3Dense *dd4; double *dvop, *dlam;
-            CK(upload(c, w4_cl_blk0, &dcb)); CK(upload(c, w4b, &db4)); CK(upload(c, w4d, &dd4)); CK(upload(c, w4_vop, &dvop));
-            CK(upload(c, w4_pmap, &dpm)); CK(upload(c, w4_ay, &day)); CK(upload(c, w4_lam, &dlam));
-            c->w4tables.Xc = c->d_Xc; c->w4tables.Y = c->d_Y; c->w4tables.S = c->d_S; c->w4tables.AY = c->d_AY;
-            c->w4tables.vop = dvop; c->w4tables.lam = dlam; c->w4tables.pmap = dpm; c->w4tables.ay = day; c->w4tables.dense = dd4;
-            c->ftables.Xc = c->d_Xc; c->ftables.Y = c->d_Y;
-            int cus = 256, dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-            Step s;
-            s.kind = STEP_ASSEMBLE_W4;
-            s.d0 = dcb; s.d1 = db4; s.src = &c->w4tables; s.n = (i64)w4_cl_blk0.size(); s.nmax = w4_nu;
-            int maxP = 1;
-            for (const W3Block &kb : w4b) maxP = std::max(maxP, kb.U);
-            s.grid = maxP;                                                                   // rows of the staged S_j
-            s.bytes = W4_LDS_BYTES(w4_nu <= 3 ? 3 : 4, maxP);
-            s.aux0 = (int)std::min<i64>(((i64)w4_cl_blk0.size() + 3) / 4, (i64)cus * W4_WGS_PER_CU(w4_nu <= 3 ? 3 : 4));      // as many workgroups as are resident at once
-            s.aux1 = (int)w4b.size();
-            pl.steps.push_back(s);
-            if (w4_nu <= 3) HIPCK(hipFuncSetAttribute((const void *)k_cluster_assemble_w4<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.bytes));
-            else HIPCK(hipFuncSetAttribute((const void *)k_cluster_assemble_w4<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.bytes));
-        }
-        if (!w2cl.empty()) {
-            int *dpm, *day; double *dlam;
-            CK(upload(c, w2_pmap, &dpm)); CK(upload(c, w2_ay, &day)); CK(upload(c, w2_lam, &dlam));
-            for (size_t i2 = 0; i2 < w2bl.size(); i2++) { w2bl[i2].lam = dlam + w2_boff[i2]; w2bl[i2].ay = day + w2_boff[i2]; }
-            for (size_t i2 = 0; i2 < w2cl.size(); i2++) w2cl[i2].pmap = dpm + w2_cl_pm[i2];
-            W2Cluster *dwc; W2Block *dwb;
-            CK(upload(c, w2cl, &dwc)); CK(upload(c, w2bl, &dwb));
-            c->ftables.Xc = c->d_Xc; c->ftables.Y = c->d_Y; c->ftables.stat = c->d_static; c->ftables.AY = c->d_AY;
-            Step s;
-            s.kind = STEP_ASSEMBLE_W2;
-            bool use_w3 = g_cfg_wave3_assemble && w2_ut <= 2;
-            // k_cluster_assemble_w3 takes the A_Y position of vector u as ay_base + u (terms of a block consecutive in A_Y, in vector order)
-            for (size_t i2 = 0; i2 < w2bl.size() && use_w3; i2++)
-                if (w2bl[i2].kind == 0)
-                    for (int u = 0; u < w2cl[w2_bl_cl[i2]].P; u++)
-                        if (w2_ay[w2_boff[i2] + u] != w2_ay[w2_boff[i2]] + u) { use_w3 = false; break; }
-            s.d0 = dwc; s.d1 = dwb; s.src = &c->ftables; s.n = (i64)w2cl.size(); s.nmax = w2_ut;
-            bool full = w2_ut <= 2;
-            for (size_t i2 = 0; i2 < w2bl.size() && full; i2++) if (w2bl[i2].kind == 0 && w2bl[i2].n != 16) full = false;
-            for (size_t i2 = 0; i2 < w2cl.size() && full; i2++) if (w2cl[i2].P != 16 * w2_ut) full = false;
-            s.grid = full ? 1 : 0;
-            s.bytes = (size_t)4 * 2 * 17 * 16 * w2_ut * sizeof(double);
-            if (use_w3) {
-                // k_cluster_assemble_w3: flat sequence of the low-rank blocks, vectors in MFMA-operand order, the 1 x 1 dense
-                // blocks attached to the last low-rank block of their cluster
-                std::vector<W3Block> b3;
-                std::vector<W3Dense> d3;
-                std::vector<int> cl_blk0;
-                std::vector<double> h_vop;
-                for (size_t ci = 0; ci < w2cl.size(); ci++) {
-                    const W2Cluster &wc = w2cl[ci];
-                    cl_blk0.push_back((int)b3.size());
-                    const int dense0 = (int)d3.size();
-                    size_t last_lr = 0;
-                    for (int i2 = 0; i2 < wc.nblk; i2++) {
-                        const size_t bi2 = (size_t)wc.blk0 + i2;
-                        const W2Block &q2 = w2bl[bi2];
-                        if (q2.kind != 0) { W3Dense de; de.xyoff = q2.xyoff; de.lam_off = (int)w2_boff[bi2]; de.pad = 0; d3.push_back(de); continue; }
-                        W3Block k3;
-                        std::memset(&k3, 0, sizeof(k3));
-                        k3.xyoff = q2.xyoff; k3.n = q2.n; k3.U = wc.P; k3.lam_off = (int)w2_boff[bi2]; k3.pmap_off = (int)w2_cl_pm[ci];
-                        k3.ay_base = w2_ay[w2_boff[bi2]];
-                        k3.vop_off = (int)(h_vop.size() / 512);
-                        h_vop.resize(h_vop.size() + 512, 0.0);
-                        double *dst = h_vop.data() + (size_t)k3.vop_off * 512;
-                        const double *V = h_static.data() + q2.v_off;
-                        for (int t = 0; t < 2; t++)
-                            for (int q = 0; q < 4; q++)
-                                for (int ln = 0; ln < 64; ln++) {
-                                    const int row = 4 * q + (ln >> 4), col = 16 * t + (ln & 15);
-                                    if (row < q2.n && col < wc.P) dst[((t * 2 + (q >> 1)) * 64 + ln) * 2 + (q & 1)] = V[row + (i64)col * q2.n];
-                                }
-                        last_lr = b3.size();
-                        b3.push_back(k3);
-                    }
-                    W3Block &kl = b3[last_lr];
-                    kl.last = 1; kl.S_off = (i64)(wc.S - c->d_S);
-                    kl.pmap_identity = 1;
-                    for (int u = 0; u < wc.P; u++) if (w2_pmap[w2_cl_pm[ci] + u] != u) kl.pmap_identity = 0;
-                    kl.ndense = (int)d3.size() - dense0; kl.dense0 = dense0;
-                    if (kl.ndense > 0) { kl.dxyoff = d3[dense0].xyoff; kl.dlam_off = d3[dense0].lam_off; }
-                }
-                if (d3.empty()) { W3Dense de; std::memset(&de, 0, sizeof(de)); d3.push_back(de); }
-                int *dcb; W3Block *db3; W3Dense *dd3; double *dvop;
-                CK(upload(c, cl_blk0, &dcb)); CK(upload(c, b3, &db3)); CK(upload(c, d3, &dd3)); CK(upload(c, h_vop, &dvop));
-                c->w3tables.Xc = c->d_Xc; c->w3tables.Y = c->d_Y; c->w3tables.S = c->d_S; c->w3tables.AY = c->d_AY;
-                c->w3tables.vop = dvop; c->w3tables.lam = dlam; c->w3tables.pmap = dpm; c->w3tables.dense = dd3;
-                // persistent form: as many workgroups as are resident at once, each wave walks a contiguous range of clusters
-                int per_cu = 2, cus = 256, dev = 0;
-                hipDeviceProp_t prop;
-                if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-                if (full) { if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_cluster_assemble_w3<true>, 256, 0) != hipSuccess) per_cu = 2; }
-                else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_cluster_assemble_w3<false>, 256, 0) != hipSuccess) per_cu = 2;
-                if (const char *e = std::getenv("CLRS_W3_WGS_PER_CU")) per_cu = std::max(1, std::atoi(e));     // diagnostic: waves per SIMD
-                if (std::getenv("CLRS_DEBUG")) std::fprintf(stderr, "[clrs] k_cluster_assemble_w3<%s>: %zu clusters, %zu blocks, %d workgroups per CU x %d CUs\n", full ? "full" : "general", w2cl.size(), b3.size(), per_cu, cus);
-                s.kind = STEP_ASSEMBLE_W3;
-                s.d0 = dcb; s.d1 = db3; s.src = &c->w3tables; s.bytes = 0;
-                s.aux0 = (int)std::min<i64>(((i64)w2cl.size() + 3) / 4, (i64)std::max(per_cu, 1) * cus);
-                s.aux1 = (int)b3.size();
-            }
-            pl.steps.push_back(s);
-            if (s.bytes > 64 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_cluster_assemble_w2<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.bytes));
-        }
-        if (!wcl.empty()) {
-            int *dpm, *day; double *dlam;
-            CK(upload(c, w_pmap, &dpm)); CK(upload(c, w_ay, &day)); CK(upload(c, w_lam, &dlam));
-            for (size_t i2 = 0; i2 < wbl.size(); i2++) { wbl[i2].pmap = dpm + w_ioff[i2]; wbl[i2].ay = day + w_ioff[i2]; wbl[i2].lam = dlam + w_ioff[i2]; }
-            // block table with a fixed number of slots per cluster (the kernel fetches slot `wave` without knowing the cluster yet)
-            std::vector<WBlock> table(wcl.size() * (size_t)w_maxblocks);
-            std::memset(table.data(), 0, table.size() * sizeof(WBlock));
-            for (size_t ci = 0; ci < wcl.size(); ci++)
-                for (int sl = 0; sl < w_maxblocks; sl++)
-                    table[ci * w_maxblocks + sl] = wbl[w_cl_first[ci] + (sl < wcl[ci].nblk ? sl : 0)];
-            WCluster *dwc; WBlock *dwb;
-            CK(upload(c, wcl, &dwc)); CK(upload(c, table, &dwb));
-            c->ftables.Xc = c->d_Xc; c->ftables.Y = c->d_Y; c->ftables.stat = c->d_static; c->ftables.AY = c->d_AY;
-            if (!c->ftables.stamps) {
-                std::vector<unsigned long long> z(64, 0ull);
-                unsigned long long *ds;
-                CK(upload(c, z, &ds));
-                c->ftables.stamps = ds;
-            }
-            Step s;
-            s.kind = STEP_ASSEMBLE_W1;
-            s.grid = (int)wcl.size(); s.d0 = dwc; s.d1 = dwb; s.src = &c->ftables; s.n = w_nwaves; s.nmax = w_ut; s.dst = (void *)(intptr_t)w_maxblocks;
-            s.bytes = (size_t)w_nwaves * w_cluster_doubles * sizeof(double);
-            pl.steps.push_back(s);
-            if (s.bytes > 64 * 1024) {
-                if (w_ut <= 2) HIPCK(hipFuncSetAttribute((const void *)k_cluster_assemble_w1<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.bytes));
-                else if (w_ut <= 4) HIPCK(hipFuncSetAttribute((const void *)k_cluster_assemble_w1<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.bytes));
-                else HIPCK(hipFuncSetAttribute((const void *)k_cluster_assemble_w1<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.bytes));
-            }
-        }
-        if (!fcl.empty()) {
-            FCluster *dfc; FBlock *dfb;
-            CK(upload(c, fcl, &dfc)); CK(upload(c, fbl, &dfb));
-            c->ftables.Xc = c->d_Xc; c->ftables.Y = c->d_Y; c->ftables.stat = c->d_static;
-            c->ftables.tL = d_tL; c->ftables.tR = d_tR; c->ftables.tlam = d_tlam;
-            c->ftables.ayL = d_ayL; c->ftables.ayR = d_ayR; c->ftables.AY = c->d_AY;
-            if (!c->ftables.stamps) {
-                std::vector<unsigned long long> z(64, 0ull);
-                unsigned long long *ds;
-                CK(upload(c, z, &ds));
-                c->ftables.stamps = ds;
-            }
-            Step s;
-            s.kind = STEP_FUSED_ASSEMBLE;
-            s.grid = (int)fcl.size(); s.d0 = dfc; s.d1 = dfb; s.src = &c->ftables; s.bytes = fused_lds; s.nmax = fused_nmax;
-            pl.steps.push_back(s);
-            if (fused_lds > 64 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_cluster_assemble, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fused_lds));
-            if (!fsum.empty()) {
-                SSlabSum *dss;
-                CK(upload(c, fsum, &dss));
-                Step s2;
-                s2.kind = STEP_SUM_S_SLABS; s2.grid = (int)fsum.size(); s2.d0 = dss; s2.n = 0;
-                for (const SSlabSum &ss : fsum) s2.n = std::max<i64>(s2.n, ss.len);
-                pl.steps.push_back(s2);
-            }
-        }
-    }
-    // =============================================================================================
-    // plan: factor (src/solver.jl:1244-1279), split like the reference's timings
-    // =============================================================================================
-    auto lds_square = [](int n) { const int n16 = (n + 15) & ~15; return (n16 + 2) * n16 + n16; };   // matrix + dinv, in doubles
-    {
-        int maxP = 0, maxn = 0;
-        for (int j = 0; j < J; j++) maxP = std::max(maxP, c->P[j]);
-        for (int b = 0; b < NB; b++) maxn = std::max(maxn, c->blk[b].n);
-        c->fused_fs = g_cfg_fused_factor && J > 0 && maxP <= 128;
-        c->fused_q = g_cfg_fused_factor && N > 0 && N <= 128;
-        c->fused_x = g_cfg_fused_factor && NB > 0 && maxn <= 128;
-        CK(dmalloc(c, &c->d_dinvS, c->xlen)); CK(dmalloc(c, &c->d_dinvQ, N));
-    }
-    bool q_from_factor = false;
-    {
-        if (c->fused_fs) {
-            std::vector<CFactor> cf(J);
-            size_t lds = 0;
-            c->q_slabs = c->fused_q && J <= 4096;
-            for (int j = 0; j < J; j++) {
-                const int P = c->P[j], P16 = (P + 15) & ~15, lda = P16 + 2;
-                CFactor &f = cf[j];
-                f.S = c->d_S + c->Soff[j]; f.B = c->d_B + c->coff[j]; f.LB = c->d_LB + c->coff[j]; f.dinv = c->d_dinvS + c->coff[j];
-                f.P = P; f.N = N; f.ldb = (int)c->xlen; f.code = j + 1;
-                const int room = (LDS_BUDGET_DOUBLES - lds_square(P)) / lda;      // columns of B that fit beside L
-                f.nc = std::max(1, std::min(std::max(N, 1), room));
-                if (f.nc < N || room < ((N + 15) & ~15)) c->q_slabs = false;      // the Gram matrix needs all of LinvB_j (+ tile padding) resident
-                lds = std::max(lds, (size_t)(lds_square(P) + lda * (N > 0 ? std::max(f.nc, c->q_slabs ? ((N + 15) & ~15) : 0) : 0)) * sizeof(double));
-            }
-            if (c->q_slabs) {
-                CK(dmalloc(c, &c->d_Qslabs, (i64)J * N * N));
-                for (int j = 0; j < J; j++) cf[j].Qslab = c->d_Qslabs + (i64)j * N * N;
-            } else
-                for (int j = 0; j < J; j++) cf[j].Qslab = nullptr;
-            CFactor *dcf;
-            CK(upload(c, cf, &dcf));
-            Step s;
-            s.kind = STEP_CLUSTER_FACTOR; s.grid = J; s.d0 = dcf; s.dst = c->d_info; s.bytes = lds;
-            c->p_cholS.steps.push_back(s);      // Cholesky of S_j and L_j^-1 B_j in one launch: the LinvB timing slot stays 0
-            if (lds > 64 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_cluster_factor, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        } else if (g_cfg_factor_aug && g_cfg_potrf_levels && J >= 1 && N > 0 && N <= 512 && *std::min_element(c->P.begin(), c->P.end()) > POTRF_NB) {
-            // large clusters, a few free variables: L_j, L_j^-1 B_j and the cluster's share of Q from ONE blocked factorisation of
-            // [S_j .; B_j^T 0] each (k_chol_pack), all clusters in the same launches; several clusters: the shares summed in cluster order
-            if (J > 1) CK(dmalloc(c, &c->d_Qslabs, (i64)J * N * N));
-            Step ms; ms.kind = STEP_MEMSET_INFO;
-            c->p_cholS.steps.push_back(ms);
-            std::vector<PotrfJob> pj;
-            std::vector<Step> unpack;
-            for (int j = 0; j < J; j++) {
-                const int P = c->P[j], P64 = (P + 63) & ~63, na = P64 + N;
-                CholAugDesc ad;
-                std::memset(&ad, 0, sizeof(ad));
-                CK(dmalloc(c, &ad.Aug, (i64)na * na));
-                ad.S = c->d_S + c->Soff[j]; ad.B = c->d_B + c->coff[j]; ad.LB = c->d_LB + c->coff[j];
-                ad.Q = J > 1 ? c->d_Qslabs + (i64)j * N * N : c->d_Q;
-                ad.P = P; ad.P64 = P64; ad.N = N; ad.ldb = (int)c->xlen;
-                c->chol_aug.push_back(ad);
-                Step ps;
-                ps.kind = STEP_CHOL_PACK; ps.n = (i64)c->chol_aug.size() - 1; ps.grid = (int)std::min<i64>(((i64)na * na + 255) / 256, 8192);
-                c->p_cholS.steps.push_back(ps);
-                PotrfJob job{ad.Aug, na, na, j + 1};
-                job.stop = P64 / 64;
-                pj.push_back(job);
-                Step us = ps;
-                us.kind = STEP_CHOL_UNPACK; us.grid = (int)std::min<i64>(((i64)P * P + (i64)P * N + (i64)N * N + 255) / 256, 8192);
-                unpack.push_back(us);
-            }
-            CK(plan_potrf(c, c->p_cholS, pj));
-            for (const Step &us : unpack) c->p_cholS.steps.push_back(us);
-            q_from_factor = true;
-        } else {
-            std::vector<PotrfJob> pj;
-            std::vector<TrsmJob> tj;
-            Step ms; ms.kind = STEP_MEMSET_INFO;
-            c->p_cholS.steps.push_back(ms);
-            for (int j = 0; j < J; j++) {
-                pj.push_back(PotrfJob{c->d_S + c->Soff[j], c->P[j], c->P[j], j + 1});
-                if (N > 0) tj.push_back(TrsmJob{c->d_S + c->Soff[j], c->P[j], c->P[j], c->d_LB + c->coff[j], (int)c->xlen, N});
-            }
-            CK(plan_potrf(c, c->p_cholS, pj));
-            if (N > 0) {
-                add_memcpy(c->p_linvB, c->d_LB, c->d_B, sizeof(double) * (size_t)(c->xlen * N));
-                CK(plan_trsm(c, c->p_linvB, tj, 0));
-            }
-        }
-        if (N > 0) {
-            if (q_from_factor) {
-                // Q came out of the factorisation of S (k_chol_unpack); several clusters: their shares are added up in cluster order
-                if (J > 1) {
-                    Step s;
-                    s.kind = STEP_SUM_SLABS;
-                    c->p_Q.steps.push_back(s);
-                }
-            } else if (c->q_slabs) {
-                Step s;
-                s.kind = STEP_SUM_SLABS;
-                c->p_Q.steps.push_back(s);
-            } else if (N <= 16 && c->xlen >= 512) {
-                Step s;
-                s.kind = STEP_GRAM_SMALL;   // few free variables, many constraints: one reduction per entry of Q
-                c->p_Q.steps.push_back(s);
-            } else {
-                std::vector<GemmDesc> gq;   // Q = LB^T LB  (vcat + matmul, src/solver.jl:1268-1269)
-                gq.push_back(mk_gemm(1, 0, N, N, (int)c->xlen, 1.0, c->d_LB, (int)c->xlen, c->d_LB, (int)c->xlen, 0.0, c->d_Q, N));
-                CK(add_gemm_stage(c, c->p_Q, gq));
-            }
-            if (c->fused_q) {
-                std::vector<SmallPotrf> sp(1);
-                std::memset(&sp[0], 0, sizeof(SmallPotrf));
-                sp[0].in_off = 0; sp[0].out_off = 0; sp[0].dinv = c->d_dinvQ; sp[0].n = N; sp[0].ldin = N; sp[0].ldout = N; sp[0].code = J + 1;
-                sp[0].nslabs = 1; sp[0].slab_stride = 0;
-                SmallPotrf *dsp;
-                CK(upload(c, sp, &dsp));
-                Step s;
-                s.kind = STEP_SMALL_POTRF; s.grid = 1; s.d0 = dsp; s.dst = c->d_info; s.n = 1; s.bytes = (size_t)lds_square(N) * sizeof(double);
-                c->p_cholQ.steps.push_back(s);
-                if (c->q_slabs) {   // single-GPU path: sum the slabs while loading Q, no separate reduction launch
-                    sp[0].nslabs = J; sp[0].slab_stride = (i64)N * N;
-                    CK(upload(c, sp, &dsp));
-                    s.d0 = dsp; s.n = 2;
-                    c->p_cholQ_slabs.steps.push_back(s);
-                }
-                if (s.bytes > 64 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_small_potrf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_square(128) * sizeof(double))));
-            } else {
-                std::vector<PotrfJob> qj;
-                qj.push_back(PotrfJob{c->d_Q, N, N, J + 1});
-                CK(plan_potrf(c, c->p_cholQ, qj));
-            }
-        }
-    }
-    // ONE small cluster: the whole factorisation stage in one launch of one workgroup (measured: 1.6-1.9 us per step saved on
-    // polyopt 2d = 40 and delsarte(3,10)).  "factor_small" = 2 also takes 2-4 clusters, one wave per cluster -- slower than
-    // k_cluster_factor + k_small_potrf on cohnelkies(8,15) (23.4 us against 12.4 + 8.0): a single wave per 32 x 32 cluster is
-    // latency bound on its own dependent chains, the workgroup-per-cluster kernels overlap four waves on them.
-    if (g_cfg_factor_small && c->fused_fs && c->fused_q && N > 0 && (J == 1 || (g_cfg_factor_small == 2 && J <= 4)) && !c->p_cholQ_slabs.steps.empty()) {
-        bool ok = N <= 64;
-        for (int j = 0; j < J; j++) ok = ok && c->P[j] <= 64;
-        const size_t need = factor_small_lds_doubles(c->P.data(), J, N) * sizeof(double);
-        ok = ok && need <= 150 * 1024;
-        if (ok) {
-            std::memset(&c->fsmall, 0, sizeof(c->fsmall));
-            const double *Ssrc[4], *Bsrc[4];
-            for (int j = 0; j < J; j++) {
-                c->fsmall.c[j].S = c->d_S + c->Soff[j]; c->fsmall.c[j].LB = c->d_LB + c->coff[j]; c->fsmall.c[j].dinv = c->d_dinvS + c->coff[j];
-                c->fsmall.c[j].P = c->P[j]; c->fsmall.c[j].code = j + 1;
-                Ssrc[j] = c->d_S + c->Soff[j]; Bsrc[j] = c->d_B + c->coff[j];
-            }
-            c->fsmall.Q = c->d_Q; c->fsmall.dinvQ = c->d_dinvQ; c->fsmall.J = J; c->fsmall.N = N; c->fsmall.ldb = (int)c->xlen; c->fsmall.codeQ = J + 1;
-            ok = factor_small_jobs(c->fsmall_jobs, c->fsmall, Ssrc, Bsrc);
-        }
-        if (ok) {
-            Step s;
-            s.kind = STEP_FACTOR_SMALL; s.bytes = need;
-            c->p_factor_small.steps.push_back(s);
-            if (need > 64 * 1024) {
-#define CLRS_FS_ATTR(NJ) HIPCK(hipFuncSetAttribute((const void *)k_factor_small<NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
-                CLRS_FS_ATTR(8) CLRS_FS_ATTR(16) CLRS_FS_ATTR(24) CLRS_FS_ATTR(32) CLRS_FS_ATTR(48)
-#undef CLRS_FS_ATTR
-            }
-        }
-    }
-    // =============================================================================================
-    // plan: solve (src/solver.jl:1527-1582)
-    // =============================================================================================
-    {
-        std::vector<TrsmJob> tj;
-        for (int j = 0; j < J; j++) tj.push_back(TrsmJob{c->d_S + c->Soff[j], c->P[j], c->P[j], c->d_t + c->coff[j], (int)c->xlen, 1});
-        CSolve *dcs = nullptr;
-        size_t lds_cs = 0;
-        if (c->fused_fs) {
-            std::vector<CSolve> cs(J);
-            for (int j = 0; j < J; j++) {
-                cs[j].L = c->d_S + c->Soff[j]; cs[j].dinv = c->d_dinvS + c->coff[j]; cs[j].LB = c->d_LB + c->coff[j];
-                cs[j].off = c->coff[j]; cs[j].P = c->P[j]; cs[j].N = N; cs[j].ldb = (int)c->xlen; cs[j].pad = 0;
-                lds_cs = std::max(lds_cs, (size_t)(lds_square(c->P[j]) + ((c->P[j] + 15) & ~15) + 2) * sizeof(double));
-            }
-            CK(upload(c, cs, &dcs));
-            if (lds_cs > 64 * 1024) {
-                HIPCK(hipFuncSetAttribute((const void *)k_cluster_solve_fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cs));
-                HIPCK(hipFuncSetAttribute((const void *)k_cluster_solve_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cs));
-            }
-            Step s;
-            s.kind = STEP_CSOLVE_FWD; s.grid = J; s.d0 = dcs; s.bytes = lds_cs;
-            c->p_fwd.steps.push_back(s);                                                        // t_j = L_j^-1 rhs_x[j]   (:1538)
-        } else {
-            add_memcpy(c->p_fwd, c->d_t, c->d_rhsx, sizeof(double) * (size_t)c->xlen);
-            CK(plan_trsm(c, c->p_fwd, tj, 0, true));
-        }
-        if (N > 0) {
-            if (c->fused_fs) {
-                Step s;
-                s.kind = STEP_GEMV_T;                                                           // u = LB^T t             (:1546)
-                c->p_fwd.steps.push_back(s);
-            } else {
-                std::vector<GemmDesc> g;
-                g.push_back(mk_gemm(1, 0, N, 1, (int)c->xlen, 1.0, c->d_LB, (int)c->xlen, c->d_t, (int)c->xlen, 0.0, c->d_u, N));
-                CK(add_gemm_stage(c, c->p_fwd, g));
-            }
-            if (c->fused_q) {
-                Step s;
-                s.kind = STEP_Q_SOLVE; s.bytes = (size_t)(lds_square(N) + ((N + 15) & ~15) + 2) * sizeof(double);   // dy = Q^-1 (rhs_y - u)  (:1550-1558)
-                c->p_bwd.steps.push_back(s);
-                if (s.bytes > 64 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_q_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.bytes));
-            } else {
-                Step s;
-                s.kind = STEP_SUB; s.dst = c->d_dy; s.src = c->d_rhsy; s.d0 = c->d_u; s.n = N;
-                c->p_bwd.steps.push_back(s);
-                std::vector<TrsmJob> qj;
-                qj.push_back(TrsmJob{c->d_Q, N, N, c->d_dy, N, 1});
-                CK(plan_trsm(c, c->p_bwd, qj, 0));
-                CK(plan_trsm(c, c->p_bwd, qj, 1));
-            }
-            if (!c->fused_fs) {
-                std::vector<GemmDesc> g2;                                                       // t += LB dy             (:1568-1569)
-                g2.push_back(mk_gemm(0, 0, (int)c->xlen, 1, N, 1.0, c->d_LB, (int)c->xlen, c->d_dy, N, 1.0, c->d_t, (int)c->xlen));
-                CK(add_gemm_stage(c, c->p_bwd, g2));
-            }
-        }
-        if (c->fused_fs) {
-            Step s;
-            s.kind = STEP_CSOLVE_BWD; s.grid = J; s.d0 = dcs; s.bytes = lds_cs;                 // dx_j = L_j^-T (t_j + LB_j dy)  (:1566-1573)
-            c->p_bwd.steps.push_back(s);
-        } else {
-            CK(plan_trsm(c, c->p_bwd, tj, 1, true));
-        }
-    }
-    // a handful of small clusters: the whole solve stage in one workgroup, one launch
-    i64 solve_doubles = (i64)N * N + c->xlen * N;                     // operands of one solve: L_j, LinvB, L_Q
-    for (int j = 0; j < J; j++) solve_doubles += (i64)c->P[j] * c->P[j];
-    if (c->fused_fs && (c->fused_q || N == 0) && J <= 8 && c->xlen <= 1024 && solve_doubles <= g_cfg_solve_small_max) {
-        int maxP16 = (N + 15) & ~15;
-        for (int j = 0; j < J; j++) maxP16 = std::max(maxP16, (c->P[j] + 15) & ~15);
-        Step s = c->p_fwd.steps[0];                                   // reuses the CSolve table
-        s.kind = STEP_SOLVE_SMALL; s.n = maxP16;
-        s.bytes = (size_t)((maxP16 + 2) * maxP16 + 2 * maxP16 + 2 + ((c->xlen + 15) & ~15) + 2 * ((N + 15) & ~15) + 16) * sizeof(double);
-        if (s.bytes > 64 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_solve_small, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.bytes));
-        const size_t need2 = solve_small2_lds_doubles(c->P.data(), J, N, c->xlen) * sizeof(double);
-        bool fits2 = g_cfg_solve_small2 && need2 <= 150 * 1024;
-        if (fits2) {
-            HIPCK(hipMemcpy(c->solve8.d, s.d0, sizeof(CSolve) * J, hipMemcpyDeviceToHost));
-            for (int ph = 0; ph < 3 && fits2; ph++) {
-                clrs_ctx::SolveSmall2 &q = c->ss2[ph];
-                q.ok = solve_small2_jobs(q.jobs, c->solve8.d, J, c->d_Q, c->d_dinvQ, N, c->xlen, c->d_LB, q.rx_job, q.ry_job, ph, c->d_t, c->d_u);
-                fits2 = q.ok;
-            }
-        }
-        if (fits2) {                                                // everything resident at once: the latency-first variant
-            Step s1 = s, s2 = s;
-            s.aux0 = 2; s.bytes = need2;
-            s1.aux0 = 3; s1.bytes = need2; s2.aux0 = 4; s2.bytes = need2;
-            c->p_fwd_small.steps.push_back(s1);
-            c->p_bwd_small.steps.push_back(s2);
-            if (s.bytes > 64 * 1024) {
-#define CLRS_SS2_ATTR(NJ)                                                                                                                   \
-    HIPCK(hipFuncSetAttribute((const void *)k_solve_small2<NJ, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.bytes));               \
-    HIPCK(hipFuncSetAttribute((const void *)k_solve_small2<NJ, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.bytes));               \
-    HIPCK(hipFuncSetAttribute((const void *)k_solve_small2<NJ, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.bytes));
-                CLRS_SS2_ATTR(8) CLRS_SS2_ATTR(16) CLRS_SS2_ATTR(24) CLRS_SS2_ATTR(32) CLRS_SS2_ATTR(48)
-#undef CLRS_SS2_ATTR
-            }
-        }
-        c->p_solve_all.steps.push_back(s);
-    } else
-    // single-GPU solve in three launches: the u = LinvB^T t product moves into the Q-solve kernel
-    if (c->fused_fs && c->fused_q && c->xlen <= 4096) {
-        c->p_solve_all.steps.push_back(c->p_fwd.steps[0]);            // k_cluster_solve_fwd
-        Step q = c->p_bwd.steps[0];                                   // k_q_solve
-        q.n = 1;
-        c->p_solve_all.steps.push_back(q);
-        c->p_solve_all.steps.push_back(c->p_bwd.steps.back());        // k_cluster_solve_bwd
-    }
-    // plan: Cholesky of X blocks (src/solver.jl:388-399)
-    {
-        if (c->fused_x) {
-            std::vector<SmallPotrf> sp(NB);
-            size_t lds = 0;
-            for (int b = 0; b < NB; b++) {
-                std::memset(&sp[b], 0, sizeof(SmallPotrf));
-                sp[b].in_off = c->blk[b].xyoff; sp[b].out_off = c->blk[b].xyoff; sp[b].dinv = nullptr;
-                sp[b].n = c->blk[b].n; sp[b].ldin = c->blk[b].n; sp[b].ldout = c->blk[b].n; sp[b].code = b + 1; sp[b].nslabs = 1;
-                lds = std::max(lds, (size_t)lds_square(c->blk[b].n) * sizeof(double));
-            }
-            SmallPotrf *dsp;
-            CK(upload(c, sp, &dsp));
-            Step s;
-            s.kind = STEP_SMALL_POTRF; s.grid = NB; s.d0 = dsp; s.dst = c->d_info + 1; s.n = 0; s.bytes = lds;
-            c->p_cholX.steps.push_back(s);
-            if (lds > 64 * 1024) HIPCK(hipFuncSetAttribute((const void *)k_small_potrf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_square(128) * sizeof(double))));
-        } else {
-            std::vector<PotrfJob> pj;
-            Step ms; ms.kind = STEP_MEMSET_INFO; ms.dst = c->d_info + 1;
-            c->p_cholX.steps.push_back(ms);
-            for (int b = 0; b < NB; b++) pj.push_back(PotrfJob{c->d_X + c->blk[b].xyoff, c->blk[b].n, c->blk[b].n, b + 1});
-            CK(plan_potrf(c, c->p_cholX, pj, c->d_info + 1));
-            if (NB > 0) {   // strict upper triangles -> 0, the output format of approx_cholesky! (src/tools.jl:100-105)
-                std::vector<PotrfDesc> zd;
-                i64 maxnn = 0;
-                for (int b = 0; b < NB; b++) {
-                    zd.push_back(PotrfDesc{c->d_X + c->blk[b].xyoff, c->blk[b].n, c->blk[b].n, 0, 0});
-                    maxnn = std::max(maxnn, (i64)c->blk[b].n * c->blk[b].n);
-                }
-                PotrfDesc *dz;
-                CK(upload(c, zd, &dz));
-                Step zs;
-                zs.kind = STEP_ZERO_UPPER; zs.grid = NB; zs.d0 = dz; zs.n = maxnn;
-                c->p_cholX.steps.push_back(zs);
-            }
-        }
-    }
-
-    // ---- algorithmic work counters ----
-    for (int b = 0; b < NB; b++) {
-        BlockInfo &k = c->blk[b];
-        double n = k.n;
-        if (k.kind == 0) {
-            double U = 0.5 * (k.URt + k.ULt), m = k.m, dl = k.delta, nt = (double)(k.t1 - k.t0);
-            c->cnt_bytes += 8.0 * (2 * n * n + dl * U);
-            c->cnt_flops += (m == 1) ? 2.0 * (2 * n * n * U + 2 * n * U * U) + U * U : 2.0 * m * (2 * n * dl * U / m + 2 * U * dl * U / m) + nt * nt;
-        } else {
-            double Pc = k.cnt;
-            c->cnt_bytes += 8.0 * (Pc * n * n + 2 * n * n);
-            c->cnt_flops += Pc * 6 * n * n * n + Pc * Pc * n * n;
-        }
-    }
-    for (int j = 0; j < J; j++) {
-        double Pj = c->P[j];
-        c->cnt_bytes += 8.0 * Pj * Pj;
-        c->cnt_factor_flops += Pj * Pj * Pj / 3 + Pj * Pj * N + 2.0 * N * N * Pj;
-        c->cnt_solve_flops += 2 * Pj * Pj + 4 * Pj * N;
-    }
-    c->cnt_factor_flops += (double)N * N * N / 3;
-    c->cnt_solve_flops += 2.0 * N * N;
-    HIPCK(hipStreamSynchronize(c->stream));
-    *out = c;
+    CtxBuild build;
+    for (CtxStage stage : CTX_STAGES)
+        if (int rc = stage(c.get(), d, build)) return rc;
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    *out = c.release();
     return 0;
-#undef CK
-#undef HIPCK
 }
 
 static void ipm_free(clrs_ctx *c);
@@ -2812,30 +1444,30 @@ extern "C" const char *clrs_version(void) { return "clrs-hip 0.1.0 (gfx950)"; }
 // ------------------------------------------------------------------------------------------------
 // test hooks
 // ------------------------------------------------------------------------------------------------
-static clrs_ctx *mini_ctx(int device) {
-    clrs_ctx *c = new clrs_ctx();
+static CtxOwner mini_ctx(int device) {
+    CtxOwner c(new clrs_ctx(), clrs_ctx_destroy);
     c->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return nullptr; }
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) c.reset();
+    if (!c) return c;
     (void)hipFuncSetAttribute((const void *)k_gemm_f64_t<128, 128, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes(128, 128));
     (void)hipFuncSetAttribute((const void *)k_gemm_f64_t<128, 128, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes(128, 128));
     (void)hipFuncSetAttribute((const void *)k_gemm_f64_t<128, 128, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes(128, 128));
     (void)hipFuncSetAttribute((const void *)k_gemm_f64_t<128, 128, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gemm_lds_bytes(128, 128));
     std::vector<int> hi(1, INFO_NONE);
-    int *di;
-    if (upload(c, hi, &di)) { clrs_ctx_destroy(c); return nullptr; }
-    c->d_info = di;
+    if (upload(c.get(), hi, &c->d_info)) c.reset();
     return c;
 }
 
 extern "C" int clrs_test_gemm(int device, int ta, int tb, int M, int N, int K, double alpha, const double *A, int lda, const double *B,
                               int ldb, double beta, double *C, int ldc) {
-    clrs_ctx *c = mini_ctx(device);
+    const CtxOwner own = mini_ctx(device);
+    clrs_ctx *c = own.get();
     if (!c) return fail(CLRS_ERR_NO_DEVICE, "no device");
     int rc = 0;
     i64 na = (i64)lda * (ta ? M : K), nb = (i64)ldb * (tb ? K : N), nc = (i64)ldc * N;
     std::vector<double> hA(A, A + na), hB(B, B + nb), hC(C, C + nc);
     double *dA, *dB, *dC;
-    if ((rc = upload(c, hA, &dA)) || (rc = upload(c, hB, &dB)) || (rc = upload(c, hC, &dC))) { clrs_ctx_destroy(c); return rc; }
+    if ((rc = upload(c, hA, &dA)) || (rc = upload(c, hB, &dB)) || (rc = upload(c, hC, &dC))) return rc;
     Plan pl;
     std::vector<GemmDesc> g;
     g.push_back(mk_gemm(ta, tb, M, N, K, alpha, dA, lda, dB, ldb, beta, dC, ldc));
@@ -2843,24 +1475,23 @@ extern "C" int clrs_test_gemm(int device, int ta, int tb, int M, int N, int K, d
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(C, dC, sizeof(double) * nc, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(CLRS_ERR_HIP, "copy back failed");
     }
-    clrs_ctx_destroy(c);
     return rc;
 }
 
 extern "C" int clrs_test_potrf(int device, int n, double *A, int lda) {
-    clrs_ctx *c = mini_ctx(device);
+    const CtxOwner own = mini_ctx(device);
+    clrs_ctx *c = own.get();
     if (!c) return fail(CLRS_ERR_NO_DEVICE, "no device");
     int rc = 0, st = 0;
     std::vector<double> hA(A, A + (i64)lda * n);
     double *dA;
-    if ((rc = upload(c, hA, &dA))) { clrs_ctx_destroy(c); return rc; }
+    if ((rc = upload(c, hA, &dA))) return rc;
     Plan pl;
     std::vector<PotrfJob> pj;
     pj.push_back(PotrfJob{dA, lda, n, 1});
     if (!(rc = plan_potrf(c, pl, pj)) && !(rc = run_steps(c, pl)) && !(rc = read_info(c, &st))) {
         if (hipMemcpy(A, dA, sizeof(double) * (i64)lda * n, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(CLRS_ERR_HIP, "copy back failed");
     }
-    clrs_ctx_destroy(c);
     return rc ? rc : st;
 }
 
@@ -2922,12 +1553,13 @@ extern "C" int clrs_test_stream(int device, long long read_bytes, long long writ
 }
 
 extern "C" int clrs_test_trsm(int device, int trans, int n, int nrhs, const double *L, int ldl, double *B, int ldb) {
-    clrs_ctx *c = mini_ctx(device);
+    const CtxOwner own = mini_ctx(device);
+    clrs_ctx *c = own.get();
     if (!c) return fail(CLRS_ERR_NO_DEVICE, "no device");
     int rc = 0;
     std::vector<double> hL(L, L + (i64)ldl * n), hB(B, B + (i64)ldb * nrhs);
     double *dL, *dB;
-    if ((rc = upload(c, hL, &dL)) || (rc = upload(c, hB, &dB))) { clrs_ctx_destroy(c); return rc; }
+    if ((rc = upload(c, hL, &dL)) || (rc = upload(c, hB, &dB))) return rc;
     Plan pl;
     std::vector<TrsmJob> tj;
     tj.push_back(TrsmJob{dL, ldl, n, dB, ldb, nrhs});
@@ -2935,6 +1567,5 @@ extern "C" int clrs_test_trsm(int device, int trans, int n, int nrhs, const doub
         if (hipStreamSynchronize(c->stream) != hipSuccess || hipMemcpy(B, dB, sizeof(double) * (i64)ldb * nrhs, hipMemcpyDeviceToHost) != hipSuccess)
             rc = fail(CLRS_ERR_HIP, "copy back failed");
     }
-    clrs_ctx_destroy(c);
     return rc;
 }

@@ -844,6 +844,47 @@ def test_malformed_descriptions_are_rejected():
         MwSchurContext(g, limbs=3)
 
 
+def test_rejected_descriptions_leave_nothing_behind():
+    """Every rejection of clrs_ctx_create that test_malformed_descriptions_are_rejected does not reach: a flattened problem with one
+    array corrupted (a FlatSDP goes to the C layer as it is) is refused with its message, at whatever stage of the creation the check
+    stands, and a context of the sound problem created afterwards in the same process computes bit for bit what one computed before."""
+    import copy
+    from clrs_amd._lib import ClrsError
+    from clrs_amd.solver import SchurContext
+
+    def run(f):
+        ctx = SchurContext(f)
+        X, Y = spd_iterates(f, seed=2)
+        S, AY = ctx.compute_S_integrated(chol_blocks_np(f, X), Y)
+        assert ctx.factor() == 0
+        out = (S, AY, *ctx.get_factor(), *ctx.solve(np.linspace(1.0, 2.0, f.x_len), np.linspace(-1.0, 1.0, f.n_free)))
+        ctx.close()
+        return out
+
+    def corrupted(f, name, index, value):
+        g = copy.copy(f)
+        a = getattr(f, name).copy()
+        a[index] = value
+        setattr(g, name, a)
+        return g
+
+    lr, dense = flat("polyopt8"), flat("sdpa_small")
+    assert lr.n_terms > 0 and int(lr.block_kind[0]) == 0 and dense.n_blocks > 1 and int(dense.block_kind[0]) != 0 and int(dense.block_n[0]) > 1
+    before = [run(lr), run(dense)]
+    cases = [("cluster with no constraints", corrupted(lr, "cluster_P", 0, 0)),
+             ("bad block description", corrupted(dense, "block_cluster", -1, -1)),                  # the last block steps back
+             ("dense blocks need m == 1", corrupted(dense, "block_m", 0, 2)),
+             ("dense constraint index out of range", corrupted(dense, "dense_p", 0, int(dense.cluster_P[0]))),
+             ("bad term description", corrupted(lr, "term_r", 0, int(lr.block_m[0]))),
+             ("dense matrix has the wrong size", corrupted(dense, "dense_A_ptr", 1, int(dense.dense_A_ptr[1]) - 1))]
+    for message, g in cases:
+        with pytest.raises(ClrsError, match=message):
+            SchurContext(g)
+    for was, now in zip(before, [run(lr), run(dense)]):
+        for a, b in zip(was, now):
+            assert (a is None and b is None) or np.array_equal(a, b)
+
+
 # ---- BASELINE configs 4 and 5 at their named sizes ---------------------------------------------------------------------------
 def test_three_point_bound_n3_2d16_config4_as_named(oracle_built):
     """BASELINE config 4 as named ("ThreePointBound spherical code n=3, 2d=16": three_point_spherical_codes(3, 1/2, 8, 8),
