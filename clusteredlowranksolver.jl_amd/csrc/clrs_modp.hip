@@ -331,3 +331,4 @@ extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int
 #include "clrs_modp_lift.hip.h"      // clrs_modp_dixon_lift: the inverse mod p by the elimination above, then the p-adic lifting loop
 #include "clrs_modp_rec.hip.h"       // clrs_modp_dixon_reconstruct: Horner and the half-extended Euclid per entry of the lifted solution
 #include "clrs_modp_minors.hip.h"    // clrs_modp_minors: the leading principal minors of a symmetric integer matrix mod many primes, one workgroup per prime
+#include "clrs_modp_zz_gemm.hip.h"   // clrs_zz_gemm: the exact product of integer matrices given in digit planes, one fp64 MFMA GEMM of one-digit matrices

@@ -18,7 +18,8 @@ on the device (clrs_modp_rref): `rref_mod_p`, `find_pivots
 
 The rest of `project_to_affine_space` (src/rounding.jl:213-286, 336-364) is the exact solve of the integer system, the reference's `Nemo._solve_dixon`: Dixon's
 p-adic lifting, on the device (clrs_modp_dixon_lift): `dixon_lift`, `solve_dixon`, `solve_system_pseudoinverse`,
-`project_to_affine_space`.  The rational reconstruction and the products around the solve are exact host arithmetic in Python integers.
+`project_to_affine_space`.  The rational reconstruction and the products around the solve are exact host arithmetic in Python integers, unless
+`reconstruct=dixon_reconstruct` (section 16) and `matmul=zz_matmul` (the exact integer matrix product clrs_zz_gemm, section 18) move them to the device.
 
 The last numeric step of the chain is `is_valid_solution` (src/rounding.jl:367-415): zero slacks, and every block of the exact solution positive definite
 (`checkpd_cholesky`, src/rounding.jl:447-472, Arb's ball-arithmetic Cholesky).  Here the answer is exact: the leading principal minors of the block, cleared of
@@ -39,7 +40,7 @@ __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vecto
            "vectors_to_mp", "vectors_to_fractions", "rref_mod_p", "next_prime", "find_pivots_modular", "system_pivots", "PivotList", "to_balanced_digits", "from_balanced_digits",
            "prev_prime", "dixon_steps", "dixon_lift", "rational_reconstruction", "SingularSystemError", "DixonSolution", "solve_dixon",
            "solve_system_pseudoinverse", "project_to_affine_space", "to_digits24", "from_digits24", "dixon_reconstruct", "leading_minors_mod", "minor_bounds", "crt_tree",
-           "PDCertificate", "checkpd", "is_valid_solution"]
+           "PDCertificate", "checkpd", "is_valid_solution", "ints_to_planes", "planes_to_ints", "zz_matmul"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -681,7 +682,7 @@ def _fraction_rows(A, b, what):
     return [[Fraction(v) for v in A[r]] for r in range(A.shape[0])], [Fraction(v) for v in b], A.shape[1]
 
 
-def solve_dixon(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True, reconstruct=None) -> DixonSolution:
+def solve_dixon(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True, reconstruct=None, matmul=None) -> DixonSolution:
     """The exact solution of the square system A x = b (what the reference asks of `Nemo._solve_dixon`, src/rounding.jl:274, 351, 360): `A` (n, n) and `b`
     (n,) or (n, 1) of integers or `Fraction`s.  Every row of [A b] is cleared of denominators; the primes are tried downward from 8388593, the largest
     below 2^23 (the solution does not depend on the prime, and the largest needs the fewest steps), at most `maxprimes` of them, and the first at which A
@@ -691,7 +692,10 @@ def solve_dixon(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: boo
     `lift(A, b, p, steps, device=...)` -> `(X, r, rank)` replaces the device call (default `dixon_lift`).
     `reconstruct(X, p, N, D, device=..., want_x=...)` -> the list of `Fraction | None` (with `want_x` also the integers `sum_k X[k] p^k`) replaces the
     Horner loop and the per-entry `rational_reconstruction` on the host; `dixon_reconstruct` does both on the device.  With `check` the identity of the
-    lifted integers is then tested on the integers that `reconstruct` returned."""
+    lifted integers is then tested on the integers that `reconstruct` returned.
+    `matmul(A, B, device=...)` -> the exact product of integer matrices (`zz_matmul` forms it on the device) replaces the host products of the two checks:
+    `Ai x` of the lifted integers, and `A solution == b` as ONE integer product `Ai y == L bi` over the common denominator L of the solution (`y = L solution`;
+    Ai, bi the rows cleared of denominators).  `None`: the host arithmetic."""
     lift = dixon_lift if lift is None else lift
     if int(maxprimes) < 1:
         raise ValueError(f"solve_dixon: maxprimes must be at least 1, got {maxprimes}")
@@ -723,13 +727,17 @@ def solve_dixon(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: boo
         x = _object_vector([int(v) for v in x])
     else:
         sol, x = reconstruct(X, p, N, D, device=device, want_x=False), None
-    if check and any(int(v) != int(w) for v, w in zip(Ai.dot(x), bi - m * np.asarray(r, dtype=object))):
+    if check and any(int(v) != int(w) for v, w in zip(Ai.dot(x) if matmul is None else _matmul_vector(matmul, Ai, x, device), bi - m * np.asarray(r, dtype=object))):
         raise ArithmeticError(f"solve_dixon: A x != b - p^K r after {K} steps at p = {p}")
     if reconstruct is None:
         sol = [rational_reconstruction(int(v), m, N, D) for v in x]
     if any(v is None for v in sol):
         raise ArithmeticError(f"solve_dixon: entry {[v is None for v in sol].index(True)} has no rational reconstruction within the bounds")
-    if check and any(sum(rows[i][j] * sol[j] for j in range(n)) != bf[i] for i in range(n)):
+    if check and matmul is not None:
+        yv, L = _common_denominator(sol)
+        if any(v != L * int(w) for v, w in zip(_matmul_vector(matmul, Ai, yv, device), bi)):
+            raise ArithmeticError("solve_dixon: A solution != b")
+    elif check and any(sum(rows[i][j] * sol[j] for j in range(n)) != bf[i] for i in range(n)):
         raise ArithmeticError("solve_dixon: A solution != b")
     return DixonSolution(sol, p, primes, K)
 
@@ -742,12 +750,14 @@ def _gcd_of(values) -> int:
     return g if g else 1                                        # (a zero row or column: the matrix is singular, the solve says so)
 
 
-def solve_system_pseudoinverse(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True, reconstruct=None):
+def solve_system_pseudoinverse(A, b, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True, reconstruct=None, matmul=None):
     """The reference's `solve_system_pseudoinverse(A, b)` (src/rounding.jl:336-364): for `A` (nrows, ncols) with independent rows and more columns than rows
     the minimum-norm solution `v = A^T (A A^T)^-1 b` of A v = b; otherwise (independent columns) `v = (A^T A)^-1 A^T b`.  A and b are first multiplied by the least
     common multiple of the denominators of A so that the reference's gcds are gcds of integers; the Gram matrix is scaled on the right by `Dr = diag(1 / gcd(column))` and
-    then on the left by `Dl = diag(1 / gcd(row))` as there, solved by `solve_dixon` (to which `maxprimes`, `device`, `lift`, `check`, `reconstruct` go), and
-    `v = A^T (Dr y)` or `v = Dr y`.  All products are exact host arithmetic.  Returns a list of `Fraction`s; `SingularSystemError` when the Gram matrix is
+    then on the left by `Dl = diag(1 / gcd(row))` as there, solved by `solve_dixon` (to which `maxprimes`, `device`, `lift`, `check`, `reconstruct`, `matmul`
+    go), and `v = A^T (Dr y)` or `v = Dr y`.  All products are exact host arithmetic, unless `matmul(A, B, device=...)` is given (`zz_matmul`: on the device):
+    then the Gram matrix is one integer product, and `A^T b` and the back-substitution `A^T (Dr y)` are one integer product each over the common denominator
+    of the vector, divided by it entry by entry -- the same `Fraction`s.  Returns a list of `Fraction`s; `SingularSystemError` when the Gram matrix is
     singular."""
     from math import gcd
     rows, bf, ncols = _fraction_rows(A, b, "solve_system_pseudoinverse")
@@ -764,8 +774,16 @@ def solve_system_pseudoinverse(A, b, maxprimes: int = 3, device: int = 0, lift=N
         bf[r] = bf[r] * lcm
     bv = _object_vector(bf)
     wide = ncols > nrows
-    G = Ai.dot(Ai.T) if wide else Ai.T.dot(Ai)
-    rhs = bv if wide else Ai.T.dot(bv)
+    if matmul is None:
+        G = Ai.dot(Ai.T) if wide else Ai.T.dot(Ai)
+        rhs = bv if wide else Ai.T.dot(bv)
+    else:
+        AiT = np.ascontiguousarray(Ai.T)
+        G = np.array(matmul(Ai, AiT, device=device) if wide else matmul(AiT, Ai, device=device), dtype=object).reshape(min(nrows, ncols), min(nrows, ncols))
+        rhs = bv
+        if not wide:
+            bint, Lb = _common_denominator(bf)
+            rhs = _object_vector([Fraction(v, Lb) for v in _matmul_vector(matmul, AiT, bint, device)])
     k = G.shape[0]
     dr = [_gcd_of(G[:, c]) for c in range(k)]
     for c in range(k):
@@ -774,14 +792,17 @@ def solve_system_pseudoinverse(A, b, maxprimes: int = 3, device: int = 0, lift=N
     for r in range(k):
         G[r] = [int(v) // dl[r] for v in G[r]]
     y = solve_dixon(G, [Fraction(rhs[r]) / dl[r] for r in range(k)], maxprimes=maxprimes, device=device, lift=lift, check=check,
-                    reconstruct=reconstruct)
+                    reconstruct=reconstruct, matmul=matmul)
     y = [y[c] / dr[c] for c in range(k)]
     if not wide:
         return y
+    if matmul is not None:
+        yint, Ly = _common_denominator(y)
+        return [Fraction(v, Ly) for v in _matmul_vector(matmul, AiT, yint, device)]
     return [sum((int(Ai[r, c]) * y[r] for r in range(nrows)), Fraction(0)) for c in range(ncols)]
 
 
-def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, rng=None, device: int = 0, batch=None, lift=None, reconstruct=None):
+def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, rng=None, device: int = 0, batch=None, lift=None, reconstruct=None, matmul=None):
     """The reference's `project_to_affine_space(A, b; settings)` (src/rounding.jl:182-286): a solution of A x = b, `A` (nrows, ncols) and `b` (nrows,) or
     (nrows, 1) of `Fraction`s or integers.  Returns `(x, correct_slacks, finished)`, x a list of ncols `Fraction`s.
 
@@ -792,7 +813,10 @@ def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, r
     are solved by `solve_system_pseudoinverse`; `correct_slacks = (A x == b)`.  When that solve meets a singular matrix (`SingularSystemError`; the
     reference prints "The system is rank-deficient") or without `pseudo`: the pivot columns alone, by `solve_dixon` when they form a square system
     (`correct_slacks = True`), through the normal equations otherwise (`correct_slacks = (A_piv^T A_piv x == A_piv^T b)`).  Indices are 0-based.
-    `batch` / `lift` replace the device calls of `find_pivots_modular` / `solve_dixon`; `reconstruct` goes to `solve_dixon` as it is."""
+    `batch` / `lift` replace the device calls of `find_pivots_modular` / `solve_dixon`; `reconstruct` goes to `solve_dixon` as it is.
+    `matmul(A, B, device=...)` (`zz_matmul`: on the device) goes to `solve_system_pseudoinverse` and `solve_dixon` and replaces the `Fraction` loops here by
+    integer products: `A x == b` over the common denominator of x on the rows of [A b] cleared of denominators; the normal equations as `M^T M` and `M^T c`
+    for `[M c] = D [A_piv b]`, D the least common multiple of all denominators, divided by D^2; and their test as one more product.  The same results."""
     settings = RoundingSettings() if settings is None else settings
     rng = np.random.default_rng(0) if rng is None else rng
     rows_f, bf, ncols = _fraction_rows(A, b, "project_to_affine_space")
@@ -805,6 +829,11 @@ def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, r
         return zero, False, False
     pivots, rows = [int(c) for c in pivots], [int(r) for r in rows]
     residual_free = lambda x: all(sum((rows_f[r][c] * x[c] for c in range(ncols) if x[c] != 0), Fraction(0)) == bf[r] for r in range(nrows))
+    if matmul is not None:
+        def residual_free(x):
+            Ab = _rows_cleared_of_denominators([rows_f[r] + [bf[r]] for r in range(nrows)])
+            yv, L = _common_denominator(x)
+            return all(v == L * int(w) for v, w in zip(_matmul_vector(matmul, Ab[:, :ncols], yv, device), Ab[:, ncols]))
     if settings.pseudo:
         try:
             if settings.extracolumns_linindep:
@@ -826,7 +855,7 @@ def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, r
             subset = list(dict.fromkeys(pivots + [c for e in extracolumns for c in e]))
             subset = subset[:min(len(subset), int(round(settings.pseudo_columnfactor * nrows)))]
             newx = solve_system_pseudoinverse([[rows_f[r][c] for c in subset] for r in rows], [bf[r] for r in rows], device=device,
-                                              lift=lift, reconstruct=reconstruct)
+                                              lift=lift, reconstruct=reconstruct, matmul=matmul)
             x = list(zero)
             for c, v in zip(subset, newx):
                 x[c] = v
@@ -836,12 +865,27 @@ def project_to_affine_space(A, b, settings: Optional[RoundingSettings] = None, r
     Apiv = [[rows_f[r][c] for c in pivots] for r in range(nrows)]
     nA, nb = Apiv, list(bf)
     square = nrows == len(pivots)
-    if not square:                                              # the normal equations
+    Mi = None
+    if not square and matmul is not None and pivots:            # the normal equations as integer products of [M c] = D [A_piv b]
+        k = len(pivots)
+        scaled, D = _common_denominator([v for r in range(nrows) for v in Apiv[r] + [bf[r]]])
+        scaled = scaled.reshape(nrows, k + 1)
+        Mi, ci = scaled[:, :k], scaled[:, k]
+        MiT = np.ascontiguousarray(Mi.T)
+        nAi = np.array(matmul(MiT, Mi, device=device), dtype=object).reshape(k, k)
+        nbi = _matmul_vector(matmul, MiT, ci, device)
+        nA = [[Fraction(int(nAi[i, j]), D * D) for j in range(k)] for i in range(k)]
+        nb = [Fraction(v, D * D) for v in nbi]
+    elif not square:                                            # the normal equations
         k = len(pivots)
         nb = [sum((Apiv[r][i] * bf[r] for r in range(nrows)), Fraction(0)) for i in range(k)]
         nA = [[sum((Apiv[r][i] * Apiv[r][j] for r in range(nrows)), Fraction(0)) for j in range(k)] for i in range(k)]
-    newx = solve_dixon(nA, nb, device=device, lift=lift, reconstruct=reconstruct) if pivots else []
-    correct = True if square else all(sum((nA[i][j] * newx[j] for j in range(len(pivots))), Fraction(0)) == nb[i] for i in range(len(pivots)))
+    newx = solve_dixon(nA, nb, device=device, lift=lift, reconstruct=reconstruct, matmul=matmul) if pivots else []
+    if Mi is not None:
+        yv, L = _common_denominator(newx)
+        correct = all(v == L * w for v, w in zip(_matmul_vector(matmul, nAi, yv, device), nbi))
+    else:
+        correct = True if square else all(sum((nA[i][j] * newx[j] for j in range(len(pivots))), Fraction(0)) == nb[i] for i in range(len(pivots)))
     x = list(zero)
     for j, c in enumerate(pivots):
         x[c] = newx[j]
@@ -1070,10 +1114,12 @@ def checkpd(A, device: int = 0, minors=None) -> PDCertificate:
     return PDCertificate(failed is None, exact, failed, scale, primes, discarded)
 
 
-def is_valid_solution(blocks, A=None, b=None, x=None, check_slacks: bool = True, device: int = 0, minors=None):
+def is_valid_solution(blocks, A=None, b=None, x=None, check_slacks: bool = True, device: int = 0, minors=None, matmul=None):
     """The numeric part of the reference's `is_valid_solution` (src/rounding.jl:367-415): are the slacks zero, and is every block of the exact solution
     positive definite?  `blocks`: the symmetric blocks (`Fraction`s or integers), each through `checkpd` (`device`, `minors` go there).  With
-    `check_slacks` the slacks `A x - b` (`A` (nrows, ncols), `b` (nrows,), `x` (ncols,)) are formed in `Fraction` arithmetic on the host.  Returns
+    `check_slacks` the slacks `A x - b` (`A` (nrows, ncols), `b` (nrows,), `x` (ncols,)) are formed in `Fraction` arithmetic on the host, or, with
+    `matmul(A, B, device=...)` (`zz_matmul`: on the device), as ONE integer product of the rows of [A b] cleared of denominators with `L x`, L the common
+    denominator of x, divided by L and the row's multiplier entry by entry: the same `Fraction`s.  Returns
     `(success, failures)`: `failures` lists `("constraint", i, slack)` for every constraint i with a non-zero slack and `("block", j, failed_order)` for
     every block j that is not positive definite."""
     failures = []
@@ -1084,6 +1130,15 @@ def is_valid_solution(blocks, A=None, b=None, x=None, check_slacks: bool = True,
         xf = [Fraction(v) for v in np.asarray(x, dtype=object).reshape(-1)]
         if len(xf) != ncols:
             raise ValueError(f"is_valid_solution: x must have one entry per column of A, got {len(xf)} for {ncols} columns")
+        if matmul is not None and rows and ncols:
+            cleared = [_common_denominator(rows[i] + [bf[i]]) for i in range(len(rows))]       # row i of [A b] times its multiplier cleared[i][1]
+            Ab = np.array([list(c[0]) for c in cleared], dtype=object).reshape(len(rows), ncols + 1)
+            yv, L = _common_denominator(xf)
+            for i, v in enumerate(_matmul_vector(matmul, Ab[:, :ncols], yv, device)):
+                num = v - L * int(Ab[i, ncols])
+                if num != 0:
+                    failures.append(("constraint", i, Fraction(num, L * cleared[i][1])))
+            rows = []
         for i, row in enumerate(rows):
             slack = sum((row[c] * xf[c] for c in range(ncols) if xf[c] != 0), Fraction(0)) - bf[i]
             if slack != 0:
@@ -1093,3 +1148,155 @@ def is_valid_solution(blocks, A=None, b=None, x=None, check_slacks: bool = True,
         if not cert.pd:
             failures.append(("block", j, cert.failed_order))
     return not failures, failures
+
+
+# ---- exact integer matrix products on the device (clrs_zz_gemm): what `matmul=zz_matmul` routes the products of the functions above through ----
+ZZ_MAX_DIGITS = 32767                # digit planes of an operand or of the result of clrs_zz_gemm
+
+
+def _balanced_offset(count: int) -> int:
+    """H = sum_{l < count} 2^23 2^(24 l): v + H has the digits of v, each raised by 2^23, as its digits in [0, 2^24)"""
+    return (1 << (DIGIT_BITS - 1)) * (((1 << (DIGIT_BITS * count)) - 1) // ((1 << DIGIT_BITS) - 1))
+
+
+def _balanced_need(v: int) -> int:
+    """the number of balanced digits the Python integer v needs (at least one): the smallest c with 0 <= v + H_c < 2^(24 c)"""
+    c = max(abs(v).bit_length() // DIGIT_BITS, 1)                                 # c digits hold magnitudes below 2^(24 c) only: never too many, at most two too few
+    while not 0 <= v + _balanced_offset(c) < 1 << (DIGIT_BITS * c):
+        c += 1
+    return c
+
+
+def ints_to_planes(values, count: Optional[int] = None) -> np.ndarray:
+    """What `to_balanced_digits(values, count)` returns -- int32 (count, *shape), little-endian balanced base-2^24 digits -- in time linear in the digits of
+    every entry: with `H = sum_l 2^23 2^(24 l)` the bytes of `v + H` (`int.to_bytes`) are cut into 24-bit digits by numpy and 2^23 is taken off each.
+    `count=None`: as many digits as the largest value needs (at least one); otherwise `ValueError` when a value does not fit."""
+    a = np.asarray(values)
+    if a.dtype != object and a.dtype.kind not in "iu":
+        if a.size:
+            raise ValueError(f"ints_to_planes: the values must be integers, got dtype {a.dtype}")
+        a = a.astype(np.int64)
+    if a.dtype == object:
+        flat = [int(v) for v in a.flat]
+        if all(-(1 << 62) < v < 1 << 62 for v in flat):
+            a = np.array(flat, dtype=np.int64).reshape(a.shape)
+    if a.dtype != object and (a.size == 0 or _max_abs(a) < 1 << 62):
+        try:
+            return to_balanced_digits(a, count)                   # (vectorised there for values of this size, and linear)
+        except ValueError:
+            raise ValueError(f"ints_to_planes: a value does not fit in {count} balanced digits of {DIGIT_BITS} bits") from None
+    flat = [int(v) for v in a.flat]
+    if count is None:
+        top = max(abs(v).bit_length() for v in flat)
+        count = max(_balanced_need(v) for v in flat if abs(v).bit_length() + 2 * DIGIT_BITS >= top)     # (only the longest values can decide the count)
+    count = int(count)
+    if count < 1:
+        raise ValueError(f"ints_to_planes: count must be at least 1, got {count}")
+    H, nbytes = _balanced_offset(count), 3 * count
+    try:
+        raw = b"".join((v + H).to_bytes(nbytes, "little") for v in flat)
+    except OverflowError:                                           # v + H negative or 2^(24 count) and beyond
+        raise ValueError(f"ints_to_planes: a value does not fit in {count} balanced digits of {DIGIT_BITS} bits") from None
+    wide = np.zeros((len(flat), count, 4), np.uint8)
+    wide[:, :, :3] = np.frombuffer(raw, dtype=np.uint8).reshape(len(flat), count, 3)
+    digits = wide.view("<u4").reshape(len(flat), count).astype(np.int32) - np.int32(1 << (DIGIT_BITS - 1))
+    return np.ascontiguousarray(digits.T).reshape((count,) + a.shape)
+
+
+def planes_to_ints(planes) -> np.ndarray:
+    """What `from_balanced_digits(planes)` returns -- digit planes (count, *shape) -> an object array `shape` of the Python integers
+    `sum_l planes[l] 2^(24 l)` -- in time linear in the digits: every digit raised by 2^23, its three low bytes packed, `int.from_bytes`, and `H` taken off.
+    Digits in [-2^23, 2^23) take that way; planes with other digits go through `from_balanced_digits`."""
+    planes = np.asarray(planes)
+    if planes.ndim < 1 or planes.shape[0] < 1:
+        raise ValueError(f"planes_to_ints: at least one plane is needed, got shape {planes.shape}")
+    if planes.dtype.kind not in "iu":
+        raise ValueError(f"planes_to_ints: the digits must be integers, got dtype {planes.dtype}")
+    count, shape = planes.shape[0], planes.shape[1:]
+    half = 1 << (DIGIT_BITS - 1)
+    out = np.empty(shape, dtype=object)
+    if planes.size == 0:
+        return out
+    if int(planes.min()) < -half or int(planes.max()) >= half:
+        return from_balanced_digits(planes)
+    raised = np.ascontiguousarray((planes.reshape(count, -1).astype(np.int64) + half).T.astype("<u4"))               # (entries, count)
+    packed = np.ascontiguousarray(raised.view(np.uint8).reshape(raised.shape[0], count, 4)[:, :, :3])
+    H, step, raw = _balanced_offset(count), 3 * count, packed.tobytes()
+    out.flat = [int.from_bytes(raw[i * step:(i + 1) * step], "little") - H for i in range(raised.shape[0])]
+    return out
+
+
+def _zz_gemm_planes(Ad, Bd, ndc: int, device: int = 0):
+    """One call of clrs_zz_gemm on digit planes: `Ad` int32 (nda, m, k), `Bd` int32 (ndb, k, n) -> `(C, info)`, C int32 (ndc, m, n), info int32 (4,).  The
+    counters are written before the call raises, so `info` can be read from `zz_matmul.last_info` after a refusal for `ndc` too small."""
+    Ad, Bd = np.ascontiguousarray(Ad, dtype=np.int32), np.ascontiguousarray(Bd, dtype=np.int32)
+    if Ad.ndim != 3 or Bd.ndim != 3 or Ad.shape[2] != Bd.shape[1]:
+        raise ValueError(f"zz_matmul: the digits must be (nda, m, k) and (ndb, k, n), got {Ad.shape} and {Bd.shape}")
+    (nda, m, k), (ndb, _, n) = Ad.shape, Bd.shape
+    Cd, info = np.zeros((int(ndc), m, n), np.int32), np.zeros(4, np.int32)
+    ptr = lambda a: a.ctypes.data_as(_lib.p_i32) if a.size else C_NULL_I32
+    try:
+        _lib.check(_lib.load().clrs_zz_gemm(int(device), m, k, n, nda, ptr(Ad), ndb, ptr(Bd), int(ndc), ptr(Cd), info.ctypes.data_as(_lib.p_i32)))
+    finally:
+        zz_matmul.last_info = [int(v) for v in info]
+    return Cd, info
+
+
+def _integer_operand(M, what):
+    """-> (a two-dimensional array of integers, whether the input was a vector): a vector is a one-column matrix"""
+    a = np.asarray(M)
+    vector = a.ndim == 1
+    if vector:
+        a = a.reshape(-1, 1)
+    if a.size == 0:
+        if a.ndim != 2:
+            raise ValueError(f"{what}: the operands must be matrices or vectors, got shape {a.shape}")
+        return np.zeros(a.shape, dtype=np.int64), vector
+    return _integer_matrix(a, what), vector
+
+
+def zz_matmul(A, B, device: int = 0) -> np.ndarray:
+    """The exact product `A B` of integer matrices on the device, one call of clrs_zz_gemm: `A` (m, k) and `B` (k, n) of integers
+    of any size (anything `np.asarray` takes; object arrays of Python integers); a vector is a one-column matrix, and the product with a vector `B` is a
+    vector, as with `numpy.dot`.  Returns an object array of Python integers.  The operands cross in balanced base-2^24 digits (`ints_to_planes`); the
+    result takes `ndc` digits computed from `k max|A| max|B|`.  The counters of the call are kept in `zz_matmul.last_info` (`[entries that did not fit,
+    ranges of digits, GEMM workgroups, 0]`).  This is the `matmul=` of `solve_dixon`, `solve_system_pseudoinverse`, `project_to_affine_space` and
+    `is_valid_solution`."""
+    a, _ = _integer_operand(A, "zz_matmul")
+    b, vector = _integer_operand(B, "zz_matmul")
+    if a.shape[1] != b.shape[0]:
+        raise ValueError(f"zz_matmul: the shapes {a.shape} and {b.shape} do not match")
+    m, k, n = a.shape[0], a.shape[1], b.shape[1]
+    out = np.zeros((m, n), dtype=object)
+    if m and n and k:
+        Ad, Bd = ints_to_planes(a), ints_to_planes(b)
+        bound = k * max(abs(int(a.max())), abs(int(a.min()))) * max(abs(int(b.max())), abs(int(b.min())))
+        ndc = max((bound.bit_length() + DIGIT_BITS + 1) // DIGIT_BITS, 1)         # 24 ndc >= bits + 2: twice the bound is below 2^(24 ndc - 1), which ndc digits hold
+        if max(Ad.shape[0], Bd.shape[0], ndc) > ZZ_MAX_DIGITS:
+            raise ValueError(f"zz_matmul: an operand or the result needs more than {ZZ_MAX_DIGITS} digits")
+        Cd, _ = _zz_gemm_planes(Ad, Bd, ndc, device=device)
+        out = planes_to_ints(Cd)
+    else:
+        zz_matmul.last_info = [0, 0, 0, 0]
+    return out.reshape(m) if vector else out
+
+
+zz_matmul.last_info = None
+
+
+def _common_denominator(values):
+    """Fractions (or integers) -> `(y, L)`: L the least common multiple of the denominators, y the object vector of the integers `value L`"""
+    from math import gcd
+    fr = [Fraction(v) for v in values]
+    L = 1
+    for v in fr:
+        L = L * v.denominator // gcd(L, v.denominator)
+    return _object_vector([v.numerator * (L // v.denominator) for v in fr]), L
+
+
+def _matmul_vector(matmul, M, y, device):
+    """`matmul(M, y)` for an integer matrix M and an integer vector y, as a list of Python integers"""
+    out = np.asarray(matmul(M, y, device=device), dtype=object).reshape(-1)
+    if out.size != np.asarray(M).shape[0]:
+        raise ArithmeticError(f"matmul returned {out.size} entries for {np.asarray(M).shape[0]} rows")
+    return [int(v) for v in out]

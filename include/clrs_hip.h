@@ -429,6 +429,17 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   [-2^23, 2^23], planes that are not symmetric, a modulus that is no prime in [2, 2^23), a repeated prime.  Every device buffer is released on every path.
  *   clrs_config_set("modp_minors_chunk_bytes", b): the primes are taken in chunks whose residues (8 n^2 bytes per prime) stay below b bytes (0, the default: 256 MiB).
  * clrs_modp_minors_times: the milliseconds of the calling thread's last clrs_modp_minors: in the residue kernel, in the L D L^T kernel, and from the first
+ *   upload to the last download (device events).
+ * clrs_zz_gemm: C = A B over the integers (the exact matrix arithmetic around the steps above: Gram matrices, normal equations, the
+ *   checks A x == b), host pointers, no context.  A is [nda][m][k], B [ndb][k][n], C [ndc][m][n]: row-major planes of balanced base-2^24 digits, little-endian.
+ *   Input digits lie in [-2^23, 2^23]; C receives the unique representation with every digit ((v + 2^23) mod 2^24) - 2^23.  info[0]: entries of C that do not
+ *   fit in ndc digits: non-zero gives CLRS_ERR_INVALID and leaves C untouched; info[1]: ranges of digits of B the product was taken in (the (lo, hi) buffer of a
+ *   range, 16 nda m n bytes per digit of B, stays below 256 MiB, or below clrs_config_set("zz_gemm_chunk_bytes", b); never less than one digit per range);
+ *   info[2]: GEMM workgroups launched; info[3]: impossibilities (a flushed accumulator that is no integer, or of magnitude >= 2^53): non-zero gives
+ *   CLRS_ERR_HIP and leaves C untouched.  CLRS_ERR_INVALID before any device call: a negative size, nda, ndb or ndc outside [1, 32767], an operand or result of
+ *   2^31 elements or more (nda m and ndb n likewise, less one tile of 64), min(nda, ndb) k >= 2^30, a null pointer with a non-empty operand (info is always
+ *   needed), a digit outside [-2^23, 2^23].  m, n or k equal to 0 gives zeros without touching a device.  Every device buffer is released on every path.
+ * clrs_zz_gemm_times: the milliseconds of the calling thread's last clrs_zz_gemm: in the GEMM kernel, in the combine and carry kernels, and from the first
  *   upload to the last download (device events). */
 #define CLRS_MODP_MINORS_MAX_N 128
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
@@ -457,6 +468,8 @@ int clrs_modp_dixon_reconstruct(int device, int n, int p, int steps, const int32
 int clrs_modp_dixon_reconstruct_times(double *horner_ms, double *euclid_ms);
 int clrs_modp_minors(int device, int n, int nd, const int32_t *digits, int nprimes, const int32_t *primes, int32_t *minors, int32_t *breakdown, int32_t *info);
 int clrs_modp_minors_times(double *residues_ms, double *ldl_ms, double *total_ms);
+int clrs_zz_gemm(int device, int m, int k, int n, int nda, const int32_t *A, int ndb, const int32_t *B, int ndc, int32_t *C, int32_t *info);
+int clrs_zz_gemm_times(double *gemm_ms, double *combine_ms, double *whole_ms);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 
