@@ -165,6 +165,8 @@ SYMBOLS = {
     "clrs_modp_minors_times": (C.c_int, [p_d, p_d, p_d]),
     "clrs_zz_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, p_i32, C.c_int, p_i32, C.c_int, p_i32, p_i32]),
     "clrs_zz_gemm_times": (C.c_int, [p_d, p_d, p_d]),
+    "clrs_modp_dixon_lift_multi": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, p_i32, C.c_int, p_i32, C.c_int, p_i32, p_i32, p_i32]),
+    "clrs_modp_dixon_lift_multi_times": (C.c_int, [p_d, p_d, p_d, p_d]),
     "clrs_mw_schur_solve": (C.c_int, [C.c_void_p, p_d, p_d, p_d, p_d]),
     "clrs_mw_cholesky_blocks_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "clrs_mw_sync_status_cholesky": (C.c_int, [C.c_void_p]),
@@ -229,7 +231,7 @@ def _hipcc(args):
 # translation units of libclrs_hip.so: (object, source, extra flags, predicate selecting the files it depends on)
 _UNITS = (
     ("clrs_hip.o", "clrs_hip.hip", (), lambda f: not f.startswith(("clrs_mw", "clrs_modp"))),
-    # the elimination mod p, the p-adic lifting on it, the reconstruction and the leading minors mod many primes (clrs_modp_rref, clrs_modp_dixon_lift, clrs_modp_dixon_reconstruct, clrs_modp_minors) and the exact integer matrix product (clrs_zz_gemm): a small unit of its own, no multi-word flags
+    # the elimination mod p, the p-adic lifting on it, the reconstruction and the leading minors mod many primes (clrs_modp_rref, clrs_modp_dixon_lift, clrs_modp_dixon_lift_multi, clrs_modp_dixon_reconstruct, clrs_modp_minors) and the exact integer matrix product (clrs_zz_gemm): a small unit of its own, no multi-word flags
     ("clrs_modp.o", "clrs_modp.hip", (), lambda f: f.startswith("clrs_modp")),
     # the multi-word (extended precision) path: error-free transformations must not be contracted into FMAs
     ("clrs_mw.o", "clrs_mw.hip", ("-ffp-contract=off", "-DMW_SPLIT_UNITS"), lambda f: f.startswith("clrs_mw")),

@@ -332,3 +332,4 @@ extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int
 #include "clrs_modp_rec.hip.h"       // clrs_modp_dixon_reconstruct: Horner and the half-extended Euclid per entry of the lifted solution
 #include "clrs_modp_minors.hip.h"    // clrs_modp_minors: the leading principal minors of a symmetric integer matrix mod many primes, one workgroup per prime
 #include "clrs_modp_zz_gemm.hip.h"   // clrs_zz_gemm: the exact product of integer matrices given in digit planes, one fp64 MFMA GEMM of one-digit matrices
+#include "clrs_modp_liftm.hip.h"     // clrs_modp_dixon_lift_multi: the lifting with a matrix of right-hand sides, both products of a step as fp64 MFMA GEMMs

@@ -91,3 +91,21 @@ LIFTF void lift_power_table(int p, int count, int32_t *pw) {
         v = v * b % (long long)p;
     }
 }
+
+// The residual update of ONE entry when the products A x come from the exact GEMM of clrs_modp_zz_gemm.hip.h (clrs_modp_liftm.hip.h):
+// P holds (lo, hi) pairs of doubles, pair l (one per digit plane of A, l < nd) at P[2 l pstride] and P[2 l pstride + 1], with
+// sum_c a_l[i, c] x[c] = lo_l + hi_l 2^24 exactly, |lo_l| <= 2^23 and |hi_l| <= n 2^22 + n < 2^38.  Limb l of A x is therefore s_l = lo_l + hi_(l-1), an int64
+// far below 2^62; r_l - s_l goes through lift_carry up the nrl limbs at r and the working limb on top (nrl >= nd + 2, so the hi of the top plane has a limb), and
+// lift_finish_row does the rest.  Balanced digits are unique, so the limbs, the residue returned and *flags are those of k_lift_r on the same entry.
+LIFTF int32_t liftm_entry(const double *P, size_t pstride, int nd, int32_t *r, size_t rstride, int nrl, int p, const int32_t *pw, int *flags) {
+    long long carry = 0;
+    for (int l = 0; l < nrl + 1; l++) {
+        long long s = 0;
+        if (l < nd) s += (long long)P[2 * (size_t)l * pstride];
+        if (l >= 1 && l <= nd) s += (long long)P[2 * (size_t)(l - 1) * pstride + 1];
+        int32_t d;
+        carry = lift_carry(carry + (l < nrl ? (long long)r[(size_t)l * rstride] : 0ll) - s, &d);
+        r[(size_t)l * rstride] = d;
+    }
+    return lift_finish_row(r, rstride, nrl, p, pw, carry, flags);
+}

@@ -9,8 +9,8 @@ other pivot columns.
 
 With `rationalize=True` the entries of the vectors are also rounded to the field QQ on the device (src/rounding.jl:623-628: roundx -> clindep per entry;
 here the first continued-fraction convergent p / q with |q v - p| < kernel_round_errbound, clrs_mw_rationalize) and the rounded
-vectors are tested against the primal block again (src/rounding.jl:630-639).  Everything after that (number fields of degree > 1, LLL, the basis
-transformations, the exact solve) is exact arithmetic and stays with the caller.
+vectors are tested against the primal block again (src/rounding.jl:630-639).  Number fields of degree > 1 and the LLL / HNF reduction of the vectors stay
+with the caller; the basis transformations and the exact solve are described below.
 
 The next fixed-width step of the pipeline is the first work of `project_to_affine_space` (src/rounding.jl:182-211): "Finding the pivots of A using RREF mod p"
 (`find_pivots_modular`, src/rounding.jl:288-333), a reduced row-echelon form of the integer system [A b] over the integers mod a prime of about 10^4.  It runs
@@ -25,6 +25,13 @@ The last numeric step of the chain is `is_valid_solution` (src/rounding.jl:367-4
 (`checkpd_cholesky`, src/rounding.jl:447-472, Arb's ball-arithmetic Cholesky).  Here the answer is exact: the leading principal minors of the block, cleared of
 denominators, mod many primes on the device (clrs_modp_minors), lifted to integers on the host: `leading_minors_mod`, `minor_bounds`,
 `crt_tree`, `checkpd`, `is_valid_solution`.  Blocks of at most 128 rows.
+
+Between the kernel vectors and the projection stands `basis_transformations` (src/rounding.jl:750-858): per PSD block `B = [kernel vectors | completing standard
+basis vectors]`, `Binv = inv(B)` over QQ, its rows normalised by the lcm of their denominators, and `transform` / `undo_transform` (src/rounding.jl:1191-1253),
+which multiply with it.  The inverse is an exact solve with a matrix of right-hand sides: Dixon's lifting with both products of a step as fp64 MFMA GEMMs on
+the device (clrs_modp_dixon_lift_multi): `dixon_lift_multi`, `solve_dixon_multi`, `inverse_qq`, `complete_basis`,
+`basis_transformations`, `transform`, `undo_transform`.  Only the reference's unreduced branch is built: the HNF / LLL reduction of the kernel vectors
+(`reduce_kernelvectors`) and the assembly of the rational linear system are not on the device yet.
 """
 from __future__ import annotations
 
@@ -40,7 +47,8 @@ __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vecto
            "vectors_to_mp", "vectors_to_fractions", "rref_mod_p", "next_prime", "find_pivots_modular", "system_pivots", "PivotList", "to_balanced_digits", "from_balanced_digits",
            "prev_prime", "dixon_steps", "dixon_lift", "rational_reconstruction", "SingularSystemError", "DixonSolution", "solve_dixon",
            "solve_system_pseudoinverse", "project_to_affine_space", "to_digits24", "from_digits24", "dixon_reconstruct", "leading_minors_mod", "minor_bounds", "crt_tree",
-           "PDCertificate", "checkpd", "is_valid_solution", "ints_to_planes", "planes_to_ints", "zz_matmul"]
+           "PDCertificate", "checkpd", "is_valid_solution", "ints_to_planes", "planes_to_ints", "zz_matmul", "dixon_lift_multi", "DixonSolutionMatrix",
+           "solve_dixon_multi", "inverse_qq", "complete_basis", "basis_transformations", "transform", "undo_transform"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -49,13 +57,15 @@ LIMBS = (4, 5, 6, 8, 10)
 
 @dataclasses.dataclass
 class RoundingSettings:
-    """The kernel and pseudoinverse fields of the reference's RoundingSettings (src/rounding.jl:4-10, 23-25, 57-62) with its defaults."""
+    """The kernel, pseudoinverse and basis-change fields of the reference's RoundingSettings (src/rounding.jl:4-10, 23-25, 57-62) with its defaults."""
     kernel_errbound: float = 1e-10          # pivots / residuals below this are zero
     kernel_round_errbound: float = 1e-15    # the dual block is used while max |X_b| <= 1 / sqrt(this)
     kernel_use_dual: bool = True
     pseudo: bool = True                     # solve through the pseudoinverse of a few more columns than rows (src/rounding.jl:23, 213)
     pseudo_columnfactor: float = 1.05       # that many columns per row; at least 1 (src/rounding.jl:60-62)
     extracolumns_linindep: bool = False     # take the extra columns linearly independent of each other instead of at random
+    reduce_kernelvectors: bool = True       # HNF / LLL reduction of the kernel vectors (src/rounding.jl:860-1060): not built, basis_transformations refuses it
+    normalize_transformation: bool = True   # rows of Binv times the lcm of their denominators, columns of B divided by it (src/rounding.jl:844-850)
 
     def __post_init__(self):
         if self.pseudo_columnfactor < 1:
@@ -1300,3 +1310,324 @@ def _matmul_vector(matmul, M, y, device):
     if out.size != np.asarray(M).shape[0]:
         raise ArithmeticError(f"matmul returned {out.size} entries for {np.asarray(M).shape[0]} rows")
     return [int(v) for v in out]
+
+
+# ---- the exact solve with a matrix of right-hand sides, the inverse over QQ and the basis change (src/rounding.jl:750-858, 1191-1253; clrs_modp_dixon_lift_multi) ----
+def _object_matrix(M, what, cast=int) -> np.ndarray:
+    """anything two-dimensional -> an object array of `cast(entry)`; an empty input keeps its shape when it has two dimensions and becomes 0 x 0 otherwise"""
+    a = np.asarray(M, dtype=object)
+    if a.size == 0:
+        return np.zeros((a.shape[0], a.shape[1]) if a.ndim == 2 else (0, 0), dtype=object)
+    if a.ndim != 2:
+        raise ValueError(f"{what}: a matrix must be two-dimensional, got shape {a.shape}")
+    out = np.empty(a.shape, dtype=object)
+    out.flat = [cast(v) for v in a.flat]
+    return out
+
+
+def _dixon_lift_multi_digits(Ad, Bl, p: int, steps: int, device: int = 0):
+    """One call of clrs_modp_dixon_lift_multi on digit planes: `Ad` int32 (nd, n, n), `Bl` int32 (nbl, n, m).  Returns `(X, R_limbs, info)`: X int32
+    (steps, n, m), R_limbs int32 (nrl, n, m), info int32 (6,)."""
+    Ad, Bl = np.ascontiguousarray(Ad, dtype=np.int32), np.ascontiguousarray(Bl, dtype=np.int32)
+    if Ad.ndim != 3 or Bl.ndim != 3 or Ad.shape[2] != Ad.shape[1] or Bl.shape[1] != Ad.shape[1]:
+        raise ValueError(f"dixon_lift_multi: the digits of A must be (nd, n, n) and the limbs of B (nbl, n, m), got {Ad.shape} and {Bl.shape}")
+    nd, n, nbl, m, steps = Ad.shape[0], Ad.shape[1], Bl.shape[0], Bl.shape[2], int(steps)
+    nrl = max(nbl, nd + 1) + 1
+    X = np.zeros((max(steps, 0), n, m), np.int32)
+    R = np.zeros((nrl, n, m), np.int32)
+    info = np.zeros(6, np.int32)
+    ptr = lambda a: a.ctypes.data_as(_lib.p_i32) if a.size else C_NULL_I32
+    _lib.check(_lib.load().clrs_modp_dixon_lift_multi(int(device), n, m, int(p), nd, ptr(Ad), nbl, ptr(Bl), steps, ptr(X), ptr(R), ptr(info)))
+    dixon_lift_multi.last_info = [int(v) for v in info]
+    return X, R, info
+
+
+def dixon_lift_multi(A, B, p: int, steps: int, device: int = 0):
+    """`steps` steps of Dixon's p-adic lifting of the integer system A X = B (A n x n, B n x m, Python integers of any size) on the device: one call of
+    clrs_modp_dixon_lift_multi, which lifts all columns side by side (both products of a step are matrix products).  Per column the result is that of
+    `dixon_lift`.  Returns `(X, R, rank)`: X int32 (steps, n, m), residues in [0, p); R an object array (n, m), the last residual as Python integers, so that
+    `A sum_k X[k] p^k == B - p^steps R`; rank the rank of A mod p.  When rank < n nothing was lifted: `(None, None, rank)`.  With m = 0 (and n > 0) there is
+    nothing to lift and the rank is not examined: it is reported as n.  The counters of the call are kept in `dixon_lift_multi.last_info` (`[rank, steps,
+    remainders, overflows, chunks of columns, impossible GEMM pairs]`)."""
+    A, B = _object_matrix(_integer_matrix(A, "dixon_lift_multi"), "dixon_lift_multi"), np.asarray(B)
+    n = A.shape[0]
+    if A.shape[1] != n:
+        raise ValueError(f"dixon_lift_multi: A must be square, got {A.shape}")
+    if B.ndim != 2 or B.shape[0] != n:
+        raise ValueError(f"dixon_lift_multi: B must be (n, m) with one row per row of A, got shape {B.shape} for n = {n}")
+    m = B.shape[1]
+    B = _object_matrix(_integer_matrix(B, "dixon_lift_multi"), "dixon_lift_multi") if B.size else np.zeros((n, m), dtype=object)
+    p, steps = int(p), int(steps)
+    if p < 2 or p >= MODP_PRIME_LIMIT or not _is_prime(p):
+        raise ValueError(f"dixon_lift_multi: p must be a prime with 2 <= p < 2^23, got {p}")
+    if n > LIFT_MAX_N or steps < 0:
+        raise ValueError(f"dixon_lift_multi: n must be at most {LIFT_MAX_N} and steps at least 0, got n = {n}, steps = {steps}")
+    if n == 0 or m == 0:
+        dixon_lift_multi.last_info = [0, steps, 0, 0, 0, 0]
+        return np.zeros((steps, n, m), np.int32), np.zeros((n, m), dtype=object), n
+    X, R, info = _dixon_lift_multi_digits(ints_to_planes(A), ints_to_planes(B), p, steps, device=device)
+    rank = int(info[0])
+    if rank < n:
+        return None, None, rank
+    return X, planes_to_ints(R), rank
+
+
+dixon_lift_multi.last_info = None
+
+
+class DixonSolutionMatrix(np.ndarray):
+    """The solution `solve_dixon_multi` returns: an object array (n, m) of `Fraction`s with three attributes, `p` (the prime lifted at; None when nothing
+    was lifted), `primes` (the primes tried, in order) and `steps` (the lifting steps)."""
+
+    def __new__(cls, values, p=None, primes=(), steps=0):
+        obj = np.asarray(values, dtype=object).view(cls)
+        obj.p = None if p is None else int(p)
+        obj.primes = [int(q) for q in primes]
+        obj.steps = int(steps)
+        return obj
+
+    def __array_finalize__(self, obj):
+        self.p = getattr(obj, "p", None)
+        self.primes = list(getattr(obj, "primes", []))
+        self.steps = getattr(obj, "steps", 0)
+
+
+def _column_denominators(S):
+    """an object matrix of Fractions -> `(Y, L)`: L[j] the least common multiple of the denominators of column j, Y[:, j] = S[:, j] L[j] as Python integers"""
+    from math import gcd
+    Y, L = np.zeros(S.shape, dtype=object), []
+    for j in range(S.shape[1]):
+        l = 1
+        for v in S[:, j]:
+            l = l * v.denominator // gcd(l, v.denominator)
+        L.append(l)
+        Y[:, j] = [v.numerator * (l // v.denominator) for v in S[:, j]]
+    return Y, L
+
+
+def _matmul_matrix(matmul, A, B, device):
+    """the product of two integer matrices as an object matrix of Python integers: ONE call of `matmul`, or the host product when it is None"""
+    if matmul is None:
+        return _object_matrix(A.dot(B), "matmul")
+    out = _object_matrix(np.asarray(matmul(A, B, device=device), dtype=object).reshape(A.shape[0], B.shape[1]), "matmul")
+    return out
+
+
+def solve_dixon_multi(A, B, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True, reconstruct=None, matmul=None) -> DixonSolutionMatrix:
+    """The exact solution of the square system A X = B with a matrix of right-hand sides: `A` (n, n) and `B` (n, m) of integers or `Fraction`s;
+    `solve_dixon` column by column, as ONE lifting.  Every row of [A B] is cleared of denominators; the schedule of primes is that of `solve_dixon`
+    (downward from 8388593, at most `maxprimes`); there is one `K = dixon_steps(A, b, p)[0]` for all columns, b the column of B of largest norm (its Cramer
+    bound holds for every column); every entry is reconstructed from `sum_k X[k] p^k mod p^K`.  Returns a `DixonSolutionMatrix` (n, m).  Raises
+    `SingularSystemError` when A is singular mod every prime tried, `ValueError` for `maxprimes < 1` or shapes that do not match, and, with `check`,
+    `ArithmeticError` unless `A X == B - p^K R_K` holds for the lifted integers and `A solution == B` for the fractions; the second is tested as
+    `Ai Y == Bi diag(L)` over one common denominator L[j] per column (Y[:, j] = L[j] solution[:, j]; Ai, Bi the rows cleared of denominators).
+    `lift(A, B, p, steps, device=...)` -> `(X, R, rank)` replaces the device call (default `dixon_lift_multi`).
+    `reconstruct(X, p, N, D, device=..., want_x=...)` as in `solve_dixon`; it is fed `X.reshape(steps, n m)` in pieces of at most 32767 entries
+    (`dixon_reconstruct` takes no more).  `matmul(A, B, device=...)` (`zz_matmul`) takes the two products of the checks, as one matrix product each."""
+    lift = dixon_lift_multi if lift is None else lift
+    if int(maxprimes) < 1:
+        raise ValueError(f"solve_dixon_multi: maxprimes must be at least 1, got {maxprimes}")
+    Af, Bf = _object_matrix(A, "solve_dixon_multi", Fraction), np.asarray(B, dtype=object)
+    n = Af.shape[0]
+    if Af.shape[1] != n:
+        raise ValueError(f"solve_dixon_multi: A must be square, got {Af.shape[0]} x {Af.shape[1]}")
+    if Bf.ndim != 2 or Bf.shape[0] != n:
+        raise ValueError(f"solve_dixon_multi: B must be (n, m) with one row per row of A, got shape {Bf.shape} for n = {n}")
+    m = Bf.shape[1]
+    if n == 0 or m == 0:
+        return DixonSolutionMatrix(np.zeros((n, m), dtype=object))
+    Bf = _object_matrix(Bf, "solve_dixon_multi", Fraction)
+    AB = _rows_cleared_of_denominators([list(Af[r]) + list(Bf[r]) for r in range(n)])
+    Ai, Bi = AB[:, :n], AB[:, n:]
+    norms = [sum(int(v) * int(v) for v in Bi[:, j]) for j in range(m)]
+    bmax = Bi[:, norms.index(max(norms))]
+    p, primes = DIXON_FIRST_PRIME + 1, []
+    for _ in range(int(maxprimes)):
+        p = prev_prime(p)
+        primes.append(p)
+        K, N, D = dixon_steps(Ai, bmax, p)
+        X, R, rank = lift(Ai, Bi, p, K, device=device)
+        if rank == n:
+            break
+    else:
+        raise SingularSystemError(f"solve_dixon_multi: the matrix is singular mod every prime tried ({primes})")
+    q = p ** K
+    X = np.asarray(X)
+    sol, x = None, None
+    if reconstruct is None:
+        x = np.zeros((n, m), dtype=object)
+        for k in range(K - 1, -1, -1):                          # Horner: x = sum_k X[k] p^k
+            x = x * p + X[k].astype(object)
+        flat = None
+    else:
+        Xf = np.ascontiguousarray(X.reshape(K, n * m))
+        flat, xs = [], []
+        for a in range(0, n * m, LIFT_MAX_N):
+            piece = reconstruct(np.ascontiguousarray(Xf[:, a:a + LIFT_MAX_N]), p, N, D, device=device, want_x=bool(check))
+            if check:
+                flat.extend(piece[0]); xs.extend(int(v) for v in piece[1])
+            else:
+                flat.extend(piece)
+        if check:
+            x = _object_vector(xs).reshape(n, m)
+    if check:
+        lhs, rhs = _matmul_matrix(matmul, Ai, x, device), Bi - q * _object_matrix(R, "solve_dixon_multi")
+        if any(int(v) != int(w) for v, w in zip(lhs.flat, rhs.flat)):
+            raise ArithmeticError(f"solve_dixon_multi: A X != B - p^K R after {K} steps at p = {p}")
+    if flat is None:
+        flat = [rational_reconstruction(int(v), q, N, D) for v in x.flat]
+    if any(v is None for v in flat):
+        e = [v is None for v in flat].index(True)
+        raise ArithmeticError(f"solve_dixon_multi: entry {divmod(e, m)} has no rational reconstruction within the bounds")
+    sol = _object_vector(flat).reshape(n, m)
+    if check:
+        Y, L = _column_denominators(sol)
+        lhs = _matmul_matrix(matmul, Ai, Y, device)
+        if any(int(lhs[i, j]) != L[j] * int(Bi[i, j]) for i in range(n) for j in range(m)):
+            raise ArithmeticError("solve_dixon_multi: A solution != B")
+    return DixonSolutionMatrix(sol, p, primes, K)
+
+
+def inverse_qq(B, maxprimes: int = 3, device: int = 0, lift=None, check: bool = True, reconstruct=None, matmul=None) -> DixonSolutionMatrix:
+    """The inverse over QQ of a square matrix of integers or `Fraction`s (the reference's `inv(B)`, src/rounding.jl:836): `solve_dixon_multi(B, I)`, to which
+    every keyword goes.  Raises `SingularSystemError` on a singular matrix."""
+    Bf = _object_matrix(B, "inverse_qq", Fraction)
+    n = Bf.shape[0]
+    if Bf.shape[1] != n:
+        raise ValueError(f"inverse_qq: the matrix must be square, got {Bf.shape[0]} x {Bf.shape[1]}")
+    eye = np.zeros((n, n), dtype=object)
+    for i in range(n):
+        eye[i, i] = 1
+    return solve_dixon_multi(Bf, eye, maxprimes=maxprimes, device=device, lift=lift, check=check, reconstruct=reconstruct, matmul=matmul)
+
+
+def complete_basis(V, maxprimes: int = 3, device: int = 0, batch=None, below: Optional[int] = None) -> PivotList:
+    """The standard basis vectors that complete the independent columns of `V` ((N, s), integers or `Fraction`s) to a basis of QQ^N: the indices i of the pivot
+    columns s + i of the reduced row-echelon form mod a prime p of `[V with its rows cleared of denominators | I_N]` (scaling a row by a non-zero factor does
+    not change which e_i depend on the columns before them).  This is the greedy choice of the reference's Gram-Schmidt loop (src/rounding.jl:1032-1049) --
+    e_i in ascending order, kept when it is independent of the columns of V and the e_j kept so far -- but decided by exact arithmetic mod p and not at
+    a threshold of 1e-40 on 512-bit floating-point numbers.  The primes are taken downward from 8388593 (or from below `below`), at most `maxprimes` of
+    them; a prime is accepted only when the first s pivots are the columns 0 ... s - 1, i.e. when the columns of V stay independent mod p, otherwise the
+    next prime is taken; `ValueError` when no prime of the schedule is accepted (V has dependent columns, or `maxprimes` was too small).  Whatever the prime,
+    [V | e_i chosen] is invertible mod p and hence over QQ; the choice is the greedy one over QQ unless p divides one of the minors that decide it, which
+    `basis_transformations` rules out afterwards from the inverse.  Returns a `PivotList` of N - s indices with `.p` and `.primes`.
+    `batch(A, p, device=...)` -> `(pivots, rank)` replaces the device call (default `rref_mod_p`)."""
+    batch = rref_mod_p if batch is None else batch
+    if int(maxprimes) < 1:
+        raise ValueError(f"complete_basis: maxprimes must be at least 1, got {maxprimes}")
+    Vf = np.asarray(V, dtype=object)
+    if Vf.ndim != 2:
+        raise ValueError(f"complete_basis: V must be (N, s), got shape {Vf.shape}")
+    N, s = Vf.shape
+    if s > N:
+        raise ValueError(f"complete_basis: {s} vectors of {N} entries cannot be independent")
+    if s == 0:
+        return PivotList(range(N))
+    Vi = _rows_cleared_of_denominators([[Fraction(v) for v in Vf[r]] for r in range(N)])
+    M = np.zeros((N, s + N), dtype=object)
+    M[:, :s] = Vi
+    for i in range(N):
+        M[i, s + i] = 1
+    p, primes = (DIXON_FIRST_PRIME + 1 if below is None else int(below)), []
+    for _ in range(int(maxprimes)):
+        p = prev_prime(p)
+        primes.append(p)
+        pivots = [int(c) for c in batch(M, p, device=device)[0]]
+        if pivots[:s] == list(range(s)):
+            if len(pivots) != N:
+                raise ArithmeticError(f"complete_basis: {len(pivots)} pivots for {N} rows at p = {p}")
+            return PivotList([c - s for c in pivots[s:]], primes, p)
+    raise ValueError(f"complete_basis: the columns of V are dependent mod every prime tried ({primes})")
+
+
+def _rational_matmul(P, Q, matmul, device):
+    """the product of two object matrices of Fractions: in Fractions, or with `matmul` as ONE integer product over a common denominator per operand"""
+    if matmul is None or P.size == 0 or Q.size == 0:
+        return _object_matrix(P.dot(Q), "transform", Fraction) if P.shape[1] else _object_matrix(np.zeros((P.shape[0], Q.shape[1]), dtype=object), "transform", Fraction)
+    (pn, pl), (qn, ql) = _common_denominator(P.flat), _common_denominator(Q.flat)
+    prod = _matmul_matrix(matmul, pn.reshape(P.shape), qn.reshape(Q.shape), device)
+    return _object_matrix(prod, "transform", lambda v: Fraction(int(v), pl * ql))
+
+
+def transform(M, Binv, s: int, matmul=None, device: int = 0) -> np.ndarray:
+    """The reference's `transform(p, Binv, s)` (src/rounding.jl:1191-1196) for an exact rational matrix: `Binv[s:, :] M Binv^T[:, s:]`, an object array
+    (N - s, N - s) of `Fraction`s.  The two products are taken in `Fraction`s, or, with `matmul(A, B, device=...)` (`zz_matmul`), as integer products over
+    common denominators."""
+    Mf, Bf, s = _object_matrix(M, "transform", Fraction), _object_matrix(Binv, "transform", Fraction), int(s)
+    N = Bf.shape[0]
+    if Bf.shape[1] != N or Mf.shape != (N, N) or not 0 <= s <= N:
+        raise ValueError(f"transform: M and Binv must be (N, N) and 0 <= s <= N, got {Mf.shape}, {Bf.shape} and s = {s}")
+    P = Bf[s:, :]
+    return _rational_matmul(_rational_matmul(P, Mf, matmul, device), P.T, matmul, device)
+
+
+def undo_transform(Mt, Binv, s: int, matmul=None, device: int = 0) -> np.ndarray:
+    """The reference's `undo_transform` of one block (src/rounding.jl:1239-1253): `Mt` ((N - s, N - s), exact rationals) is padded with s zero rows and
+    columns in front and multiplied by `Binv^T` from the left and `Binv` from the right: `transform(padded, Binv^T, 0)`.  `matmul` as in `transform`."""
+    Bf, s = _object_matrix(Binv, "undo_transform", Fraction), int(s)
+    N = Bf.shape[0]
+    Mf = _object_matrix(Mt, "undo_transform", Fraction)
+    if Bf.shape[1] != N or not 0 <= s <= N or Mf.shape != (N - s, N - s):
+        raise ValueError(f"undo_transform: Binv must be (N, N) and Mt (N - s, N - s), got {Bf.shape}, {Mf.shape} and s = {s}")
+    padded = _object_matrix(np.zeros((N, N), dtype=object), "undo_transform", Fraction)
+    padded[s:, s:] = Mf
+    return transform(padded, Bf.T, 0, matmul=matmul, device=device)
+
+
+def basis_transformations(kernels, settings: Optional[RoundingSettings] = None, device: int = 0, maxprimes: int = 3, batch=None, lift=None, check: bool = True,
+                          reconstruct=None, matmul=None) -> dict:
+    """The reference's `basis_transformations` over QQ (src/rounding.jl:750-858), its unreduced branch (src/rounding.jl:967-971, 1017-1050).  `kernels` maps a
+    block key to `(N, vectors)`: the size of the block and its s rational kernel vectors, each of N entries (what `vectors_to_fractions(BlockKernel)`
+    returns); they become the first s columns of B.  Per key, in the order of `kernels`: `B = [V | E]` with the standard basis vectors E of
+    `complete_basis`, `Binv = inverse_qq(B)`, and, with `settings.normalize_transformation`, row i of Binv multiplied by the least common multiple of its
+    denominators and column i of B divided by it (src/rounding.jl:844-850).  A block without kernel vectors gives identities and s = 0.  Returns
+    `{key: (B^T, Binv, s)}`, object arrays (N, N) of `Fraction`s, like the reference.
+    The completion is tested against the inverse: an e_i that was not taken must lie in the span of V and the e_j taken before it, i.e. column i of Binv is
+    zero in the rows of the e_j taken with j > i; otherwise the prime of `complete_basis` divided a deciding minor and the next prime is taken (at most
+    `maxprimes` times, then `ArithmeticError`).
+    With `settings.reduce_kernelvectors` true (the default, as in the reference) this raises `NotImplementedError`: the HNF / LLL reduction of the kernel
+    vectors (`reduction_step`, src/rounding.jl:860-1060) is not on the device yet; neither are the assembly of the rational linear system and number fields
+    of degree above 1.  Pass `RoundingSettings(reduce_kernelvectors=False)`.
+    `batch` goes to `complete_basis`; `lift`, `check`, `reconstruct`, `matmul` go to `inverse_qq`."""
+    from math import gcd
+    settings = RoundingSettings() if settings is None else settings
+    if settings.reduce_kernelvectors:
+        raise NotImplementedError("basis_transformations: settings.reduce_kernelvectors is true, but the HNF / LLL reduction of the kernel vectors is not on "
+                                  "the device yet (nor are the assembly of the rational system and number fields of degree above 1); "
+                                  "pass RoundingSettings(reduce_kernelvectors=False)")
+    out = {}
+    for key, (N, vectors) in kernels.items():
+        N, vectors = int(N), list(vectors)
+        s = len(vectors)
+        B = _object_matrix(np.zeros((N, N), dtype=object), "basis_transformations", Fraction)
+        if s == 0:
+            for i in range(N):
+                B[i, i] = Fraction(1)
+            out[key] = (B.T.copy(), B.copy(), 0)
+            continue
+        for c, v in enumerate(vectors):
+            if len(v) != N:
+                raise ValueError(f"basis_transformations: block {key!r}: vector {c} has {len(v)} entries for a block of size {N}")
+            B[:, c] = [Fraction(x) for x in v]
+        below = None
+        for _ in range(int(maxprimes)):
+            extra = complete_basis(B[:, :s], maxprimes=maxprimes, device=device, batch=batch, below=below)
+            B[:, s:] = Fraction(0)
+            for c, i in enumerate(extra):
+                B[i, s + c] = Fraction(1)
+            Binv = np.asarray(inverse_qq(B, maxprimes=maxprimes, device=device, lift=lift, check=check, reconstruct=reconstruct, matmul=matmul))
+            taken = set(extra)
+            if all(Binv[s + c, i] == 0 for i in range(N) if i not in taken for c, j in enumerate(extra) if j > i):
+                break
+            below = extra.p
+        else:
+            raise ArithmeticError(f"basis_transformations: block {key!r}: no prime gave the greedy completion of the kernel vectors")
+        if settings.normalize_transformation:
+            for i in range(N):
+                l = 1
+                for v in Binv[i]:
+                    l = l * v.denominator // gcd(l, v.denominator)
+                Binv[i] = [v * l for v in Binv[i]]
+                B[:, i] = [v / l for v in B[:, i]]
+        out[key] = (B.T.copy(), Binv.copy(), s)
+    return out

@@ -440,7 +440,20 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   2^31 elements or more (nda m and ndb n likewise, less one tile of 64), min(nda, ndb) k >= 2^30, a null pointer with a non-empty operand (info is always
  *   needed), a digit outside [-2^23, 2^23].  m, n or k equal to 0 gives zeros without touching a device.  Every device buffer is released on every path.
  * clrs_zz_gemm_times: the milliseconds of the calling thread's last clrs_zz_gemm: in the GEMM kernel, in the combine and carry kernels, and from the first
- *   upload to the last download (device events). */
+ *   upload to the last download (device events).
+ * clrs_modp_dixon_lift_multi: clrs_modp_dixon_lift for a matrix of right-hand sides, A X = B with B n x m (the exact solve behind the
+ *   inverse over QQ of the reference's basis_transformations, src/rounding.jl:836), host pointers, no context.  A_digits is [nd][n][n], B_limbs [nbl][n][m],
+ *   X [steps][n][m] (residues in [0, p)), R_limbs [nrl][n][m] with nrl = max(nbl, nd + 1) + 1: per column j exactly what clrs_modp_dixon_lift gives for
+ *   b = B[:, j].  Both products of a step are fp64 MFMA GEMMs (k_liftm_x: X_k = A^-1 R_k mod p; k_zz_gemm: A X_k as (lo, hi) pairs), the residual update is
+ *   one thread per entry.  The columns are taken in chunks whose buffers (per column 16 nd n + 16 n + 4 (nrl + 1) n bytes) stay below 256 MiB, or below
+ *   clrs_config_set("liftm_chunk_bytes", b); never less than one column per chunk; the result does not depend on the chunks.  info (6 ints): [rank of A mod p,
+ *   steps done, divisions that left a remainder, residuals that left their limbs, chunks of columns, GEMM pairs found impossible]; a non-zero count in
+ *   info[2], info[3] or info[5] gives CLRS_ERR_HIP.  rank < n: no error, nothing lifted, X and R_limbs untouched.  CLRS_ERR_INVALID before any device call,
+ *   outputs untouched: what clrs_modp_dixon_lift refuses, m < 0, an operand or result (nd n^2, nbl n m, steps n m, (nrl + 1) n m) of 2^31 elements or more.
+ *   n == 0 or m == 0: nothing to lift, info = [0, steps, 0, 0, 0, 0] without touching a device (the rank of A is then not examined).  Every device buffer is
+ *   released on every path.
+ * clrs_modp_dixon_lift_multi_times: the milliseconds of the calling thread's last clrs_modp_dixon_lift_multi: in k_liftm_x, in k_zz_gemm and in k_liftm_r
+ *   over all steps and chunks, and from the first upload to the last download (device events). */
 #define CLRS_MODP_MINORS_MAX_N 128
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
@@ -470,6 +483,9 @@ int clrs_modp_minors(int device, int n, int nd, const int32_t *digits, int nprim
 int clrs_modp_minors_times(double *residues_ms, double *ldl_ms, double *total_ms);
 int clrs_zz_gemm(int device, int m, int k, int n, int nda, const int32_t *A, int ndb, const int32_t *B, int ndc, int32_t *C, int32_t *info);
 int clrs_zz_gemm_times(double *gemm_ms, double *combine_ms, double *whole_ms);
+int clrs_modp_dixon_lift_multi(int device, int n, int m, int p, int nd, const int32_t *A_digits, int nbl, const int32_t *B_limbs, int steps, int32_t *X,
+                               int32_t *R_limbs, int32_t *info);
+int clrs_modp_dixon_lift_multi_times(double *x_ms, double *gemm_ms, double *r_ms, double *whole_ms);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 
