@@ -248,7 +248,20 @@ struct ModpBufs {                      // every device buffer of a call, release
         return hipFree(d);
     }
 };
+struct ModpEvents {                    // the device events of a call: `count` null slots for the caller's hipEventCreate, destroyed on every path
+    std::vector<hipEvent_t> e;
+    explicit ModpEvents(size_t count) : e(count, nullptr) {}
+    ~ModpEvents() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+};
 }  // namespace
+
+// the grid of a kernel that strides `count` elements with workgroups of nt threads
+static dim3 modp_flat_grid(size_t count, int nt) { return dim3((unsigned)std::min<size_t>((count + nt - 1) / nt, 65536)); }
+
+static bool modp_prime_ok(int p) { return p >= 2 && p < (1 << MODP_MAX_PRIME_BITS) && modp_is_prime(p); }
+
+// the byte bound of a chunk: what clrs_config_set gave (for the tests), else the default
+static size_t modp_chunk_bound(int cfg, size_t dflt) { return cfg > 0 ? (size_t)cfg : dflt; }
 
 // The elimination itself, on a matrix of fp64 residues already on the device (row-major, nrows x ncols), which it leaves there in reduced form: pivots are
 // sought in the columns below `pcols` only (pcols = ncols: the reduced row-echelon form; pcols < ncols: the columns behind are carried along, as the
@@ -289,7 +302,7 @@ static int modp_eliminate(double *d_A, int nrows, int ncols, int pcols, int p, M
 extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int32_t *A, int32_t *pivots, int32_t *rank, int32_t *R) {
     if (nrows < 0 || ncols < 0) return modp_fail(CLRS_ERR_INVALID, "modp_rref: negative size");
     if ((long long)nrows * (long long)ncols >= (1ll << 31)) return modp_fail(CLRS_ERR_INVALID, "modp_rref: nrows * ncols must be below 2^31");
-    if (p < 2 || p >= (1 << MODP_MAX_PRIME_BITS) || !modp_is_prime(p)) return modp_fail(CLRS_ERR_INVALID, "modp_rref: p must be a prime with 2 <= p < 2^23");
+    if (!modp_prime_ok(p)) return modp_fail(CLRS_ERR_INVALID, "modp_rref: p must be a prime with 2 <= p < 2^23");
     const size_t count = (size_t)nrows * (size_t)ncols;
     if (count == 0) {
         if (rank) *rank = 0;
@@ -305,8 +318,8 @@ extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int
     int *d_flag = nullptr, *d_order = nullptr;
     MODPCHECK(bufs.get(&d_I, count)); MODPCHECK(bufs.get(&d_A, count));
     MODPCHECK(hipMemcpy(d_I, A, count * sizeof(int32_t), hipMemcpyHostToDevice));
-    const unsigned flat = (unsigned)std::min<size_t>((count + MODP_NT - 1) / MODP_NT, 65536);
-    hipLaunchKernelGGL(k_modp_widen, dim3(flat), dim3(MODP_NT), 0, nullptr, d_I, d_A, count);
+    const dim3 flat = modp_flat_grid(count, MODP_NT);
+    hipLaunchKernelGGL(k_modp_widen, flat, dim3(MODP_NT), 0, nullptr, d_I, d_A, count);
     MODPCHECK(hipGetLastError());
     MODPCHECK(bufs.drop(d_I));                                // the int32 copy is needed again only for R: 8 bytes per entry during the elimination, not 12
     d_I = nullptr;
@@ -318,7 +331,7 @@ extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int
         MODPCHECK(bufs.get(&d_I, count)); MODPCHECK(bufs.get(&d_order, (size_t)nrows));
         hipLaunchKernelGGL(k_modp_order, dim3((unsigned)(((long long)nrows + MODP_NT - 1) / MODP_NT)), dim3(MODP_NT), 0, nullptr, d_flag, nrows, d_order);
         MODPCHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_modp_gather, dim3(flat), dim3(MODP_NT), 0, nullptr, d_A, nrows, ncols, rk, d_order, d_I);
+        hipLaunchKernelGGL(k_modp_gather, flat, dim3(MODP_NT), 0, nullptr, d_A, nrows, ncols, rk, d_order, d_I);
         MODPCHECK(hipGetLastError());
     }
     MODPCHECK(hipStreamSynchronize(nullptr));
@@ -331,5 +344,6 @@ extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int
 #include "clrs_modp_lift.hip.h"      // clrs_modp_dixon_lift: the inverse mod p by the elimination above, then the p-adic lifting loop
 #include "clrs_modp_rec.hip.h"       // clrs_modp_dixon_reconstruct: Horner and the half-extended Euclid per entry of the lifted solution
 #include "clrs_modp_minors.hip.h"    // clrs_modp_minors: the leading principal minors of a symmetric integer matrix mod many primes, one workgroup per prime
+#include "clrs_modp_tile.hip.h"      // the 64 x 64 fp64 MFMA tile loop of the two exact products below
 #include "clrs_modp_zz_gemm.hip.h"   // clrs_zz_gemm: the exact product of integer matrices given in digit planes, one fp64 MFMA GEMM of one-digit matrices
 #include "clrs_modp_liftm.hip.h"     // clrs_modp_dixon_lift_multi: the lifting with a matrix of right-hand sides, both products of a step as fp64 MFMA GEMMs

@@ -2,8 +2,9 @@
 // section 15): what the reference's project_to_affine_space asks of Nemo._solve_dixon (src/rounding.jl:274, 351, 360), on the device.  Included at the end of
 // clrs_modp.hip, whose elimination (modp_eliminate) and buffers (ModpBufs) it uses.
 //
-//   C = A^-1 mod p      k_lift_residues builds [A mod p | I] (n x 2n fp64 residues) from the digit planes of A, modp_eliminate reduces it with the pivots
-//                       sought in the first n columns, k_lift_gather writes the right half in pivot-row order as int32.  rank < n: the call ends here.
+//   C = A^-1 mod p      lift_inverse_modp (shared with clrs_modp_liftm.hip.h): k_lift_residues builds [A mod p | I] (n x 2n fp64 residues) from the digit
+//                       planes of A, modp_eliminate reduces it with the pivots sought in the first n columns; then k_lift_gather writes the right half in
+//                       pivot-row order as int32.  rank < n: the call ends here.
 //   r_0 = b, and per step k:   x_k = C (r_k mod p) mod p             k_lift_x
 //                              r_{k+1} = (r_k - A x_k) / p, exactly   k_lift_r   (which also leaves r_{k+1} mod p for the next k_lift_x)
 //
@@ -42,12 +43,13 @@ __global__ __launch_bounds__(LIFT_NT) void k_lift_residues(const int32_t *__rest
     }
 }
 
-// C[j, c] = M[pivot row j, n + c] as int32, n x ld, the padding columns zero
-__global__ __launch_bounds__(LIFT_NT) void k_lift_gather(const double *__restrict__ M, int n, int ld, const int *__restrict__ order, int32_t *__restrict__ Cinv) {
+// C[j, c] = M[pivot row j, n + c] as T (int32 for k_lift_x, fp64 for k_liftm_x), n x ld, the padding columns zero
+template <class T>
+__global__ __launch_bounds__(LIFT_NT) void k_lift_gather(const double *__restrict__ M, int n, int ld, const int *__restrict__ order, T *__restrict__ Cinv) {
     const size_t count = (size_t)n * ld;
     for (size_t o = (size_t)blockIdx.x * LIFT_NT + threadIdx.x; o < count; o += (size_t)gridDim.x * LIFT_NT) {
         const size_t j = o / ld, c = o - j * ld;
-        Cinv[o] = c < (size_t)n ? (int32_t)M[(size_t)order[j] * 2 * n + n + c] : 0;
+        Cinv[o] = c < (size_t)n ? (T)M[(size_t)order[j] * 2 * n + n + c] : (T)0;
     }
 }
 
@@ -105,22 +107,57 @@ __global__ __launch_bounds__(LIFT_NT) void k_lift_r(const int32_t *__restrict__ 
     }
 }
 
+// The refusals clrs_modp_dixon_lift and clrs_modp_dixon_lift_multi (`who`; m = its columns, 1 for the former) share, in the order both make them
+static int lift_check_sizes(const std::string &who, int n, int m, int nd, int nbl, int steps, int p) {
+    if (n < 0 || n > LIFT_MAX_N) return modp_fail(CLRS_ERR_INVALID, who + ": n must lie in [0, 32767]");
+    if (m < 0) return modp_fail(CLRS_ERR_INVALID, who + ": m must not be negative");
+    if (nd < 1 || nbl < 1 || steps < 0) return modp_fail(CLRS_ERR_INVALID, who + ": nd and nbl must be at least 1 and steps at least 0");
+    if (nd > LIFT_MAX_N || nbl > LIFT_MAX_N) return modp_fail(CLRS_ERR_INVALID, who + ": more than 32767 limbs");
+    if (!modp_prime_ok(p)) return modp_fail(CLRS_ERR_INVALID, who + ": p must be a prime with 2 <= p < 2^23");
+    return 0;
+}
+
+// `what` ("a digit of A", "a limb of b") outside [-2^23, 2^23) among the `count` of v
+static int lift_check_digits(const std::string &who, const char *what, const int32_t *v, size_t count) {
+    for (size_t o = 0; o < count; o++)
+        if (v[o] < -LIFT_HALF || v[o] >= LIFT_HALF) return modp_fail(CLRS_ERR_INVALID, who + ": " + what + " outside [-2^23, 2^23)");
+    return 0;
+}
+
+// The inverse mod p, from the digit planes of A on the device (d_Ad: nd planes of n rows of `ld` ints; d_pw[j] = 2^(24 j) mod p): *d_M (n x 2n fp64, from
+// `bufs`) becomes [A mod p | I] and is left reduced with the pivots sought in the first n columns; *rank is the rank of A mod p.  rank == n: *d_order[j] is the
+// row of M that is pivot row j, so the right half of M in that order is A^-1 mod p (work may still be in flight).  rank < n: the stream is synchronised and
+// there is no *d_order; the caller ends its call.
+static int lift_inverse_modp(const int32_t *d_Ad, int n, int ld, int nd, int p, const int32_t *d_pw, ModpBufs &bufs, double **d_M, int **d_order, int *rank) {
+    int *d_flag = nullptr;
+    MODPCHECK(bufs.get(d_M, 2 * (size_t)n * n));
+    hipLaunchKernelGGL(k_lift_residues, modp_flat_grid((size_t)n * n, LIFT_NT), dim3(LIFT_NT), 0, nullptr, d_Ad, n, ld, nd, p, d_pw, *d_M);
+    MODPCHECK(hipGetLastError());
+    std::vector<int32_t> found;
+    const int code = modp_eliminate(*d_M, n, 2 * n, n, p, bufs, &d_flag, found);
+    if (code != 0) return code;
+    *rank = (int)found.size();
+    if (*rank < n) {                                           // singular mod p: no error, the caller takes another prime
+        MODPCHECK(hipStreamSynchronize(nullptr));
+        return 0;
+    }
+    MODPCHECK(bufs.get(d_order, (size_t)n));
+    hipLaunchKernelGGL(k_modp_order, dim3((unsigned)((n + MODP_NT - 1) / MODP_NT)), dim3(MODP_NT), 0, nullptr, d_flag, n, *d_order);
+    MODPCHECK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int clrs_modp_dixon_lift(int device, int n, int p, int nd, const int32_t *A_digits, int nbl, const int32_t *b_limbs, int steps, int32_t *X,
                                     int32_t *r_limbs, int32_t *info) {
-    if (n < 0 || n > LIFT_MAX_N) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift: n must lie in [0, 32767]");
-    if (nd < 1 || nbl < 1 || steps < 0) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift: nd and nbl must be at least 1 and steps at least 0");
-    if (nd > LIFT_MAX_N || nbl > LIFT_MAX_N) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift: more than 32767 limbs");
-    if (p < 2 || p >= (1 << MODP_MAX_PRIME_BITS) || !modp_is_prime(p)) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift: p must be a prime with 2 <= p < 2^23");
+    const char *who = "modp_dixon_lift";
+    if (int code = lift_check_sizes(who, n, 1, nd, nbl, steps, p)) return code;
     if (n == 0) {
         if (info) { info[0] = 0; info[1] = steps; info[2] = 0; info[3] = 0; }
         return 0;
     }
     if (!A_digits || !b_limbs || !r_limbs || !info || (!X && steps > 0)) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift: null argument");
-    const size_t nn = (size_t)n * n;
-    for (size_t o = 0; o < (size_t)nd * nn; o++)
-        if (A_digits[o] < -LIFT_HALF || A_digits[o] >= LIFT_HALF) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift: a digit of A outside [-2^23, 2^23)");
-    for (size_t o = 0; o < (size_t)nbl * n; o++)
-        if (b_limbs[o] < -LIFT_HALF || b_limbs[o] >= LIFT_HALF) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift: a limb of b outside [-2^23, 2^23)");
+    if (int code = lift_check_digits(who, "a digit of A", A_digits, (size_t)nd * n * n)) return code;
+    if (int code = lift_check_digits(who, "a limb of b", b_limbs, (size_t)nbl * n)) return code;
     const int nrl = std::max(nbl, nd + 1) + 1, nt = nrl + 1, ld = (n + 3) & ~3;
     std::vector<int32_t> pw((size_t)std::max(nd, nt));
     lift_power_table(p, (int)pw.size(), pw.data());
@@ -129,30 +166,20 @@ extern "C" int clrs_modp_dixon_lift(int device, int n, int p, int nd, const int3
     ModpBufs bufs;
     int32_t *d_Ad = nullptr, *d_pw = nullptr, *d_C = nullptr, *d_x = nullptr, *d_rbar = nullptr, *d_r = nullptr, *d_X = nullptr;
     double *d_M = nullptr;
-    int *d_flag = nullptr, *d_order = nullptr, *d_cnt = nullptr;
+    int *d_order = nullptr, *d_cnt = nullptr;
     const size_t plane = (size_t)n * ld;
-    MODPCHECK(bufs.get(&d_Ad, (size_t)nd * plane)); MODPCHECK(bufs.get(&d_pw, pw.size())); MODPCHECK(bufs.get(&d_M, 2 * nn));
+    MODPCHECK(bufs.get(&d_Ad, (size_t)nd * plane)); MODPCHECK(bufs.get(&d_pw, pw.size()));
     MODPCHECK(hipMemset(d_Ad, 0, (size_t)nd * plane * sizeof(int32_t)));
     MODPCHECK(hipMemcpy2D(d_Ad, (size_t)ld * sizeof(int32_t), A_digits, (size_t)n * sizeof(int32_t), (size_t)n * sizeof(int32_t), (size_t)nd * n, hipMemcpyHostToDevice));
     MODPCHECK(hipMemcpy(d_pw, pw.data(), pw.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    const auto flat = [](size_t count) { return dim3((unsigned)std::min<size_t>((count + LIFT_NT - 1) / LIFT_NT, 65536)); };
-    hipLaunchKernelGGL(k_lift_residues, flat(nn), dim3(LIFT_NT), 0, nullptr, d_Ad, n, ld, nd, p, d_pw, d_M);
-    MODPCHECK(hipGetLastError());
-    std::vector<int32_t> found;
-    {
-        const int code = modp_eliminate(d_M, n, 2 * n, n, p, bufs, &d_flag, found);
-        if (code != 0) return code;
-    }
-    const int rank = (int)found.size();
-    if (rank < n) {                                            // singular mod p: no error, the caller takes another prime
-        MODPCHECK(hipStreamSynchronize(nullptr));
+    int rank = 0;
+    if (int code = lift_inverse_modp(d_Ad, n, ld, nd, p, d_pw, bufs, &d_M, &d_order, &rank)) return code;
+    if (rank < n) {
         info[0] = rank; info[1] = 0; info[2] = 0; info[3] = 0;
         return 0;
     }
-    MODPCHECK(bufs.get(&d_order, (size_t)n)); MODPCHECK(bufs.get(&d_C, plane));
-    hipLaunchKernelGGL(k_modp_order, dim3((unsigned)((n + MODP_NT - 1) / MODP_NT)), dim3(MODP_NT), 0, nullptr, d_flag, n, d_order);
-    MODPCHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_lift_gather, flat(plane), dim3(LIFT_NT), 0, nullptr, d_M, n, ld, d_order, d_C);
+    MODPCHECK(bufs.get(&d_C, plane));
+    hipLaunchKernelGGL(k_lift_gather<int32_t>, modp_flat_grid(plane, LIFT_NT), dim3(LIFT_NT), 0, nullptr, d_M, n, ld, d_order, d_C);
     MODPCHECK(hipGetLastError());
     MODPCHECK(bufs.drop(d_M));                                 // 16 n^2 bytes the lifting does not need (hipFree waits for the gather)
     d_M = nullptr;

@@ -1,14 +1,15 @@
 // clrs_modp_liftm.hip.h -- Dixon's p-adic lifting of an integer system A X = B with a MATRIX of right-hand sides (clrs_modp_dixon_lift_multi, include/clrs_hip.h;
 // DESIGN.md section 19): the exact solve behind the inverse over QQ of the reference's basis_transformations (src/rounding.jl:836).  Included at the end of
-// clrs_modp.hip behind clrs_modp_zz_gemm.hip.h: it uses the elimination and the buffers of clrs_modp.hip, k_lift_residues of clrs_modp_lift.hip.h and k_zz_gemm.
+// clrs_modp.hip behind clrs_modp_zz_gemm.hip.h: it uses the buffers of clrs_modp.hip, the inverse mod p and k_lift_gather of clrs_modp_lift.hip.h, the tile loop and k_zz_gemm.
 //
 // Per column j the result is by definition that of clrs_modp_dixon_lift on b = B[:, j].  What changes is the shape of the work: with m columns side by side
 // the two products of a step are matrix products whose operands are reused from LDS, not m matrix-vector products that each read A and A^-1 mod p once.
 //
-//   setup      [A mod p | I] by k_lift_residues, modp_eliminate, then k_liftm_gather writes the right half in pivot-row order as fp64: Cd = A^-1 mod p (n x n).
+//   setup      lift_inverse_modp of clrs_modp_lift.hip.h ([A mod p | I] by k_lift_residues, modp_eliminate), then k_lift_gather writes the right half in pivot-row
+//              order as fp64: Cd = A^-1 mod p (n x n).
 //              The digit planes of A are widened once to fp64, A' = [A_0; ...; A_{nd-1}] ((nd n) x n, the planes as they lie).
 //   per chunk of columns (mc of them):  R_0 = B[:, chunk] as limbs [(nrl + 1)][n][mc], Rbar = R_0 mod p as fp64 (n x mc), and per step k, three launches:
-//     k_liftm_x    X_k = Cd Rbar mod p           the hot path: a tiled fp64 GEMM on v_mfma_f64_16x16x4 with the tile, panels and LDS strides of k_zz_gemm;
+//     k_liftm_x    X_k = Cd Rbar mod p           the hot path: the tile loop of clrs_modp_tile.hip.h (a tiled fp64 GEMM on v_mfma_f64_16x16x4), as in k_zz_gemm;
 //                                                writes X_k as int32 (row k of the chunk's X) and as fp64 (Xd)
 //     k_zz_gemm    P = A' Xd as (lo, hi) pairs   (nd n) x mc, unchanged
 //     k_liftm_r    R <- (R - A X_k) / p          one thread per entry: liftm_entry (clrs_modp_lift_arith.h); leaves Rbar = R mod p for the next step
@@ -33,78 +34,25 @@ static_assert(LIFTM_REDUCE_STEPS >= 1 && (1ll << MODP_MAX_PRIME_BITS) + 4ll * LI
 
 extern int g_cfg_liftm_chunk_bytes;            // clrs_hip.hip, clrs_config_set("liftm_chunk_bytes", bytes): 0 = LIFTM_CHUNK_BYTES
 
-// Cd[j, c] = M[pivot row j, n + c] as fp64, n x n
-__global__ __launch_bounds__(LIFTM_NT) void k_liftm_gather(const double *__restrict__ M, int n, const int *__restrict__ order, double *__restrict__ Cd) {
-    const size_t count = (size_t)n * n;
-    for (size_t o = (size_t)blockIdx.x * LIFTM_NT + threadIdx.x; o < count; o += (size_t)gridDim.x * LIFTM_NT) {
-        const size_t j = o / n, c = o - j * n;
-        Cd[o] = M[(size_t)order[j] * 2 * n + n + c];
-    }
-}
-
 // X[r, c] = sum_kk A[r, kk] B[kk, c] mod p for r < M, c < N; A is M x K residues (row stride K), B is K x N residues (row stride N); the result as int32 into Xi
-// and as fp64 into Xd (both M x N).  The tile, the panels and the operand / accumulator layout are those of k_zz_gemm; a flat grid of `colblocks` workgroups
+// and as fp64 into Xd (both M x N).  The main loop is zz_tile_loop (clrs_modp_tile.hip.h), reduced mod p every LIFTM_REDUCE_STEPS steps; a flat grid of `colblocks` workgroups
 // per row of tiles.  One code path: rows >= M, columns >= N and k >= K load zeros, stores are masked.
 __global__ __launch_bounds__(LIFTM_NT) void k_liftm_x(const double *__restrict__ A, int M, int K, const double *__restrict__ B, int N, int p_int,
                                                       int32_t *__restrict__ Xi, double *__restrict__ Xd, int colblocks) {
-    __shared__ double As[ZZ_BM * ZZ_LDA], Bs[ZZ_BK * ZZ_LDB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, l4 = lane >> 4;
     const int by = blockIdx.x / colblocks, bx = blockIdx.x - by * colblocks;
     const int row0 = by * ZZ_BM, col0 = bx * ZZ_BN;
     const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
     const double p = (double)p_int, pinv = 1.0 / p;
-    // the loads of a step: A panel row a_r + 16 i, column a_k; B panel row b_k + 4 i, column b_c
-    const int a_r = tid >> 4, a_k = tid & 15, b_k = tid >> 6, b_c = tid & 63;
-    double ra[4], rb[4];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int r = row0 + a_r + 16 * i, ka = k0 + a_k, kb = k0 + b_k + 4 * i, c = col0 + b_c;
-            ra[i] = (r < M && ka < K) ? A[(size_t)r * K + ka] : 0.0;
-            rb[i] = (kb < K && c < N) ? B[(size_t)kb * N + c] : 0.0;
-        }
-    };
     modp_v4d acc[2][2];
+    zz_tile_loop<LIFTM_REDUCE_STEPS>(A, M, K, B, N, 0, N, row0, col0, acc, [&](modp_v4d (&t)[2][2]) {
 #pragma unroll
-    for (int ti = 0; ti < 2; ti++)
+        for (int ti = 0; ti < 2; ti++)
 #pragma unroll
-        for (int tj = 0; tj < 2; tj++)
+            for (int tj = 0; tj < 2; tj++)
 #pragma unroll
-            for (int reg = 0; reg < 4; reg++) acc[ti][tj][reg] = 0.0;
-    const int nsteps = (K + ZZ_BK - 1) / ZZ_BK;
-    fetch(0);
-    for (int step = 0; step < nsteps; step++) {
-        __syncthreads();                                                                   // the panels of the step before are read
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            As[(a_r + 16 * i) * ZZ_LDA + a_k] = ra[i];
-            Bs[(b_k + 4 * i) * ZZ_LDB + b_c] = rb[i];
-        }
-        __syncthreads();
-        if (step + 1 < nsteps) fetch((step + 1) * ZZ_BK);                                  // (uniform) in flight while this step multiplies
-#pragma unroll
-        for (int kk = 0; kk < ZZ_BK / 4; kk++) {
-            // operands: A-side lane l holds A[row (l & 15), 4 kk + (l >> 4)], B-side lane l holds B[4 kk + (l >> 4), column (l & 15)]
-            double av[2], bv[2];
-#pragma unroll
-            for (int t = 0; t < 2; t++) {
-                av[t] = As[(wr + 16 * t + l15) * ZZ_LDA + 4 * kk + l4];
-                bv[t] = Bs[(4 * kk + l4) * ZZ_LDB + wc + 16 * t + l15];
-            }
-#pragma unroll
-            for (int ti = 0; ti < 2; ti++)
-#pragma unroll
-                for (int tj = 0; tj < 2; tj++) acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ti], bv[tj], acc[ti][tj], 0, 0, 0);
-        }
-        if ((step + 1) % LIFTM_REDUCE_STEPS == 0) {                                        // (uniform)
-#pragma unroll
-            for (int ti = 0; ti < 2; ti++)
-#pragma unroll
-                for (int tj = 0; tj < 2; tj++)
-#pragma unroll
-                    for (int reg = 0; reg < 4; reg++) acc[ti][tj][reg] = modp_reduce(acc[ti][tj][reg], p, pinv);
-        }
-    }
+                for (int reg = 0; reg < 4; reg++) t[ti][tj][reg] = modp_reduce(t[ti][tj][reg], p, pinv);
+    });
     // accumulator: column l & 15, row (l >> 4) + 4 reg
 #pragma unroll
     for (int ti = 0; ti < 2; ti++)
@@ -148,12 +96,8 @@ extern "C" int clrs_modp_dixon_lift_multi_times(double *x_ms, double *gemm_ms, d
 
 extern "C" int clrs_modp_dixon_lift_multi(int device, int n, int m, int p, int nd, const int32_t *A_digits, int nbl, const int32_t *B_limbs, int steps, int32_t *X,
                                           int32_t *R_limbs, int32_t *info) {
-    if (n < 0 || n > LIFT_MAX_N) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift_multi: n must lie in [0, 32767]");
-    if (m < 0) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift_multi: m must not be negative");
-    if (nd < 1 || nbl < 1 || steps < 0) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift_multi: nd and nbl must be at least 1 and steps at least 0");
-    if (nd > LIFT_MAX_N || nbl > LIFT_MAX_N) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift_multi: more than 32767 limbs");
-    if (p < 2 || p >= (1 << MODP_MAX_PRIME_BITS) || !modp_is_prime(p))
-        return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift_multi: p must be a prime with 2 <= p < 2^23");
+    const char *who = "modp_dixon_lift_multi";
+    if (int code = lift_check_sizes(who, n, m, nd, nbl, steps, p)) return code;
     const int nrl = std::max(nbl, nd + 1) + 1, nt = nrl + 1;
     const unsigned long long lim = 1ull << 31, nm = (unsigned long long)n * (unsigned long long)m;
     if ((unsigned long long)nd * n * n >= lim || (unsigned long long)nbl * nm >= lim || (unsigned long long)steps * nm >= lim || (unsigned long long)nt * nm >= lim)
@@ -165,55 +109,39 @@ extern "C" int clrs_modp_dixon_lift_multi(int device, int n, int m, int p, int n
     }
     if (!A_digits || !B_limbs || !R_limbs || !info || (!X && steps > 0)) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift_multi: null argument");
     const size_t nn = (size_t)n * n;
-    for (size_t o = 0; o < (size_t)nd * nn; o++)
-        if (A_digits[o] < -LIFT_HALF || A_digits[o] >= LIFT_HALF) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift_multi: a digit of A outside [-2^23, 2^23)");
-    for (size_t o = 0; o < (size_t)nbl * (size_t)nm; o++)
-        if (B_limbs[o] < -LIFT_HALF || B_limbs[o] >= LIFT_HALF) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_lift_multi: a limb of B outside [-2^23, 2^23)");
+    if (int code = lift_check_digits(who, "a digit of A", A_digits, (size_t)nd * nn)) return code;
+    if (int code = lift_check_digits(who, "a limb of B", B_limbs, (size_t)nbl * (size_t)nm)) return code;
     std::vector<int32_t> pw((size_t)std::max(nd, nt));
     lift_power_table(p, (int)pw.size(), pw.data());
     // the columns of a chunk: P (16 nd n bytes per column), Xd and Rbar (8 n each) and the limbs of R (4 (nrl + 1) n) stay below the bound
-    const size_t bound = g_cfg_liftm_chunk_bytes > 0 ? (size_t)g_cfg_liftm_chunk_bytes : LIFTM_CHUNK_BYTES;
+    const size_t bound = modp_chunk_bound(g_cfg_liftm_chunk_bytes, LIFTM_CHUNK_BYTES);
     const size_t percol = (size_t)n * ((size_t)nd * sizeof(double2) + 2 * sizeof(double) + (size_t)nt * sizeof(int32_t));
     const int mc_max = (int)std::min<size_t>((size_t)m, std::max<size_t>(bound / percol, 1));
 
     MODPCHECK(hipSetDevice(device));
     ModpBufs bufs;
-    struct Events {                                            // (released on every path, like the buffers)
-        std::vector<hipEvent_t> e;
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    ev.e.assign((size_t)3 * steps + 3, nullptr);               // [0], [1]: the whole call; [2 + 3 k + t]: before launch t of step k, [2 + 3 steps]: after the last
+    ModpEvents ev((size_t)3 * steps + 3);                      // [0], [1]: the whole call; [2 + 3 k + t]: before launch t of step k, [2 + 3 steps]: after the last
     for (hipEvent_t &x : ev.e) MODPCHECK(hipEventCreate(&x));
     hipEvent_t *step_ev = ev.e.data() + 2;
     int32_t *d_Ai = nullptr, *d_pw = nullptr, *d_r = nullptr, *d_X = nullptr;
     double *d_M = nullptr, *d_Cd = nullptr, *d_Ap = nullptr, *d_Xd = nullptr, *d_rbar = nullptr;
     double2 *d_P = nullptr;
-    int *d_flag = nullptr, *d_order = nullptr, *d_cnt = nullptr;                           // cnt: [0] remainders, [1] limb overflows, [2] impossible GEMM pairs
+    int *d_order = nullptr, *d_cnt = nullptr;                           // cnt: [0] remainders, [1] limb overflows, [2] impossible GEMM pairs
     MODPCHECK(hipEventRecord(ev.e[0], nullptr));
-    MODPCHECK(bufs.get(&d_Ai, (size_t)nd * nn)); MODPCHECK(bufs.get(&d_pw, pw.size())); MODPCHECK(bufs.get(&d_M, 2 * nn));
+    MODPCHECK(bufs.get(&d_Ai, (size_t)nd * nn)); MODPCHECK(bufs.get(&d_pw, pw.size()));
     MODPCHECK(hipMemcpy(d_Ai, A_digits, (size_t)nd * nn * sizeof(int32_t), hipMemcpyHostToDevice));
     MODPCHECK(hipMemcpy(d_pw, pw.data(), pw.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    const auto flat = [](size_t count) { return dim3((unsigned)std::min<size_t>((count + LIFTM_NT - 1) / LIFTM_NT, 65536)); };
-    hipLaunchKernelGGL(k_lift_residues, flat(nn), dim3(LIFT_NT), 0, nullptr, d_Ai, n, n, nd, p, d_pw, d_M);      // (row pitch n: the planes as they lie)
-    MODPCHECK(hipGetLastError());
-    std::vector<int32_t> found;
-    {
-        const int code = modp_eliminate(d_M, n, 2 * n, n, p, bufs, &d_flag, found);
-        if (code != 0) return code;
-    }
-    const int rank = (int)found.size();
-    if (rank < n) {                                            // singular mod p: no error, the caller takes another prime
-        MODPCHECK(hipStreamSynchronize(nullptr));
+    int rank = 0;
+    if (int code = lift_inverse_modp(d_Ai, n, n, nd, p, d_pw, bufs, &d_M, &d_order, &rank)) return code;      // (row pitch n: the planes as they lie)
+    if (rank < n) {
         info[0] = rank; info[1] = 0; info[2] = 0; info[3] = 0; info[4] = 0; info[5] = 0;
         g_liftm_ms[0] = g_liftm_ms[1] = g_liftm_ms[2] = g_liftm_ms[3] = 0.0;
         return 0;
     }
-    MODPCHECK(bufs.get(&d_order, (size_t)n)); MODPCHECK(bufs.get(&d_Cd, nn)); MODPCHECK(bufs.get(&d_Ap, (size_t)nd * nn));
-    hipLaunchKernelGGL(k_modp_order, dim3((unsigned)((n + MODP_NT - 1) / MODP_NT)), dim3(MODP_NT), 0, nullptr, d_flag, n, d_order);
+    MODPCHECK(bufs.get(&d_Cd, nn)); MODPCHECK(bufs.get(&d_Ap, (size_t)nd * nn));
+    hipLaunchKernelGGL(k_lift_gather<double>, modp_flat_grid(nn, LIFT_NT), dim3(LIFT_NT), 0, nullptr, d_M, n, n, d_order, d_Cd);
     MODPCHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_liftm_gather, flat(nn), dim3(LIFTM_NT), 0, nullptr, d_M, n, d_order, d_Cd);
-    MODPCHECK(hipGetLastError());
-    hipLaunchKernelGGL(k_modp_widen, flat((size_t)nd * nn), dim3(MODP_NT), 0, nullptr, d_Ai, d_Ap, (size_t)nd * nn);
+    hipLaunchKernelGGL(k_modp_widen, modp_flat_grid((size_t)nd * nn, MODP_NT), dim3(MODP_NT), 0, nullptr, d_Ai, d_Ap, (size_t)nd * nn);
     MODPCHECK(hipGetLastError());
     MODPCHECK(bufs.drop(d_M)); MODPCHECK(bufs.drop(d_Ai));     // (hipFree waits for the gather and the widening)
     d_M = nullptr; d_Ai = nullptr;

@@ -198,11 +198,11 @@ extern "C" int clrs_modp_minors(int device, int n, int nd, const int32_t *digits
         std::sort(sorted.begin(), sorted.end());
         for (int q = 0; q < nprimes; q++) {
             const int v = sorted[q];
-            if (v < 2 || v >= (1 << MODP_MAX_PRIME_BITS) || !modp_is_prime(v)) return modp_fail(CLRS_ERR_INVALID, "modp_minors: every modulus must be a prime with 2 <= p < 2^23");
+            if (!modp_prime_ok(v)) return modp_fail(CLRS_ERR_INVALID, "modp_minors: every modulus must be a prime with 2 <= p < 2^23");
             if (q > 0 && sorted[q - 1] == v) return modp_fail(CLRS_ERR_INVALID, "modp_minors: a repeated prime");
         }
     }
-    const size_t bound = g_cfg_modp_minors_chunk_bytes > 0 ? (size_t)g_cfg_modp_minors_chunk_bytes : MINORS_CHUNK_BYTES;
+    const size_t bound = modp_chunk_bound(g_cfg_modp_minors_chunk_bytes, MINORS_CHUNK_BYTES);
     const int chunk = (int)std::min<size_t>((size_t)nprimes, std::max<size_t>(bound / (plane * sizeof(double)), 1));
     const int npad = (n + 15) / 16 * 16;
     const size_t lds = minors_lds_bytes(n);
@@ -215,10 +215,7 @@ extern "C" int clrs_modp_minors(int device, int n, int nd, const int32_t *digits
     int *d_err = nullptr;
     MODPCHECK(bufs.get(&d_digits, (size_t)nd * plane)); MODPCHECK(bufs.get(&d_primes, (size_t)nprimes)); MODPCHECK(bufs.get(&d_R, (size_t)chunk * plane));
     MODPCHECK(bufs.get(&d_minors, (size_t)nprimes * n)); MODPCHECK(bufs.get(&d_break, (size_t)nprimes)); MODPCHECK(bufs.get(&d_err, (size_t)1));
-    struct Events {                                                    // (released on every path, like the buffers)
-        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
+    ModpEvents ev(5);
     for (hipEvent_t &x : ev.e) MODPCHECK(hipEventCreate(&x));
     MODPCHECK(hipEventRecord(ev.e[3], nullptr));
     MODPCHECK(hipMemcpy(d_digits, digits, (size_t)nd * plane * sizeof(int32_t), hipMemcpyHostToDevice));

@@ -283,8 +283,7 @@ extern "C" int clrs_modp_dixon_reconstruct(int device, int n, int p, int steps, 
                                            int nl, int32_t *num, int32_t *den, int32_t *neg, int32_t *status, int nx, int32_t *x_limbs, int32_t *info) {
     if (n < 0 || n > LIFT_MAX_N) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_reconstruct: n must lie in [0, 32767]");
     if (steps < 1) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_reconstruct: steps must be at least 1");
-    if (p < 2 || p >= (1 << MODP_MAX_PRIME_BITS) || !modp_is_prime(p))
-        return modp_fail(CLRS_ERR_INVALID, "modp_dixon_reconstruct: p must be a prime with 2 <= p < 2^23");
+    if (!modp_prime_ok(p)) return modp_fail(CLRS_ERR_INVALID, "modp_dixon_reconstruct: p must be a prime with 2 <= p < 2^23");
     if (n == 0) {
         if (info) { info[0] = 0; info[1] = 0; info[2] = 0; info[3] = 0; }
         return 0;
@@ -327,10 +326,7 @@ extern "C" int clrs_modp_dixon_reconstruct(int device, int n, int p, int steps, 
     if (lD > 0) MODPCHECK(hipMemcpy(d_D, D_limbs, (size_t)lD * sizeof(int32_t), hipMemcpyHostToDevice));
     MODPCHECK(hipMemcpy(d_pw, pw.data(), (size_t)cap * sizeof(int32_t), hipMemcpyHostToDevice));
     MODPCHECK(hipMemset(d_err, 0, sizeof(int)));
-    struct Events {                                                    // (released on every path, like the buffers)
-        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
+    ModpEvents ev(3);
     for (hipEvent_t &x : ev.e) MODPCHECK(hipEventCreate(&x));
     double ms[2] = {0.0, 0.0};
     for (int i0 = 0; i0 < n; i0 += chunk) {

@@ -1,28 +1,21 @@
 // clrs_modp_zz_gemm.hip.h -- the exact product C = A B of integer matrices given in balanced base-2^24 digit planes (clrs_zz_gemm, include/clrs_hip.h;
 // DESIGN.md section 18): the matrix arithmetic around the fixed-width steps of the rounding chain (Gram matrices, normal equations, the checks A x == b of
 // project_to_affine_space / is_valid_solution, src/rounding.jl:182-415).  No context, host pointers.  Included at the end of clrs_modp.hip, whose ModpBufs,
-// modp_fail and MODPCHECK it uses.
+// modp_fail and MODPCHECK it uses, behind clrs_modp_tile.hip.h.
 //
 // A digit-by-digit product is ONE ordinary GEMM of one-digit matrices: A' = [A_0; ...; A_{nda-1}] ((nda m) x k: the planes as they lie in memory),
 // B' = [B_0 | ... | B_{ndb-1}] (k x (ndb n)), P = A' B', and plane s of the product is C_s = sum_i P[i m + r, (s - i) n + j] before carries.  A vector of long
 // integers is thus a matrix of digits whose columns are reused from LDS like any GEMM's.
 //
 //   k_zz_widen     int32 -> fp64; B repacked to B'.
-//   k_zz_gemm      the hot path: P = A' B'[:, columns of a range of digits] on v_mfma_f64_16x16x4 (the builtin and the operand / accumulator layout of
-//                  k_modp_update).  A workgroup of four waves takes a 64 x 64 tile of P, a wave 32 x 32 of it as 2 x 2 tiles of 16 x 16; the operand panels of a
-//                  step of k-extent 16 (64 x 16 of A', 16 x 64 of B') are staged in LDS, the next step's panels are already in flight in registers.  Every
-//                  accumulator is flushed after 7 steps = 28 MFMAs (clrs_modp_zz_arith.h: at most 31 keep the sum below 2^53) and once at the end; the kernel
-//                  writes (lo, hi) per entry, value = lo + hi 2^24.  One code path: rows >= nda m, columns >= the range and k >= the inner extent load zeros,
-//                  stores are masked.
+//   k_zz_gemm      the hot path: P = A' B'[:, columns of a range of digits] by the tile loop of clrs_modp_tile.hip.h (a 64 x 64 tile of P per workgroup of four
+//                  waves on v_mfma_f64_16x16x4, the panels staged in LDS).  Every accumulator is flushed after 7 steps = 28 MFMAs (clrs_modp_zz_arith.h: at most
+//                  31 keep the sum below 2^53) and once at the end; the kernel writes (lo, hi) per entry, value = lo + hi 2^24.  One code path: rows >= nda m,
+//                  columns >= the range and k >= the inner extent load zeros, stores are masked.
 //   k_zz_combine   S[s] += sum_i lo(P[i m + r, (s - i) n + j]) + hi(P[i m + r, (s - 1 - i) n + j]) over the digits of the range, int64 planes
 //                  S[nda + ndb][m][n]: sums of at most 2 min(nda, ndb) terms, below 2^62 by the refusal min(nda, ndb) k < 2^30.  One thread per entry of S that
 //                  the range reaches, no atomics (the ranges run one after the other on one stream).
 //   k_zz_carry     one thread per entry of C: zz_carry_walk (clrs_modp_zz_arith.h) upward through the planes of S.
-//
-// LDS layout against the bank rule (64 banks of 4 bytes for ds_read_b64, conflicts counted within a half of 32 lanes): the A-side operand of lane l is
-// As[row (l & 15)][4 kk + (l >> 4)] with row stride ZZ_LDA = 18 doubles: within a half the double index is 18 (l & 15) + (l >> 4) + const, and 18 r mod 32 takes
-// the 16 even values once each, so the 32 lanes fall on 32 different pairs of banks; lanes l and l + 16 are neighbours.  The B-side operand is
-// Bs[4 kk + (l >> 4)][col (l & 15)] with row stride ZZ_LDB = 80 = 16 mod 32: lanes l + 16 read 16 doubles further on, again 32 different pairs of banks.
 //
 // P takes 16 bytes per entry of an (nda m) x (digits n) matrix: B' is cut into ranges of digits so that P stays below ZZ_GEMM_CHUNK_BYTES (256 MiB;
 // clrs_config_set("zz_gemm_chunk_bytes", b) lowers it, for the tests; a range is never less than one digit).  Everything after the GEMM is integer arithmetic,
@@ -32,11 +25,6 @@
 #include "clrs_modp_zz_arith.h"
 
 #define ZZ_NT 256                     // threads of a workgroup of every kernel: four waves
-#define ZZ_BM 64                      // tile of P per workgroup
-#define ZZ_BN 64
-#define ZZ_BK 16                      // k-extent of a step: four MFMAs per accumulator
-#define ZZ_LDA (ZZ_BK + 2)            // row stride of the A panel in LDS (doubles)
-#define ZZ_LDB (ZZ_BN + 16)           // row stride of the B panel in LDS (doubles)
 #define ZZ_FLUSH_STEPS (ZZ_FLUSH_MFMAS / (ZZ_BK / 4))
 #define ZZ_GEMM_CHUNK_BYTES ((size_t)256 << 20)
 #define ZZ_MAX_DIGITS 32767
@@ -63,67 +51,29 @@ __global__ __launch_bounds__(ZZ_NT) void k_zz_widen(const int32_t *__restrict__ 
 // per row of tiles; *err counts pairs that are not what a flushed accumulator can be
 __global__ __launch_bounds__(ZZ_NT) void k_zz_gemm(const double *__restrict__ A, int M, int K, const double *__restrict__ B, size_t ldb, size_t c0, int N,
                                                    double2 *__restrict__ P, int colblocks, int *__restrict__ err) {
-    __shared__ double As[ZZ_BM * ZZ_LDA], Bs[ZZ_BK * ZZ_LDB];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, l4 = lane >> 4;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, l4 = lane >> 4;
     const int by = blockIdx.x / colblocks, bx = blockIdx.x - by * colblocks;
     const int row0 = by * ZZ_BM, col0 = bx * ZZ_BN;
     const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    // the loads of a step: A panel row a_r + 16 i, column a_k; B panel row b_k + 4 i, column b_c
-    const int a_r = tid >> 4, a_k = tid & 15, b_k = tid >> 6, b_c = tid & 63;
-    double ra[4], rb[4];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int r = row0 + a_r + 16 * i, ka = k0 + a_k, kb = k0 + b_k + 4 * i, c = col0 + b_c;
-            ra[i] = (r < M && ka < K) ? A[(size_t)r * K + ka] : 0.0;
-            rb[i] = (kb < K && c < N) ? B[(size_t)kb * ldb + c0 + c] : 0.0;
-        }
-    };
     modp_v4d acc[2][2], hi[2][2];
 #pragma unroll
     for (int ti = 0; ti < 2; ti++)
 #pragma unroll
         for (int tj = 0; tj < 2; tj++)
 #pragma unroll
-            for (int reg = 0; reg < 4; reg++) { acc[ti][tj][reg] = 0.0; hi[ti][tj][reg] = 0.0; }
-    const int nsteps = (K + ZZ_BK - 1) / ZZ_BK;
-    fetch(0);
-    for (int step = 0; step < nsteps; step++) {
-        __syncthreads();                                                                   // the panels of the step before are read
+            for (int reg = 0; reg < 4; reg++) hi[ti][tj][reg] = 0.0;
+    zz_tile_loop<ZZ_FLUSH_STEPS>(A, M, K, B, ldb, c0, N, row0, col0, acc, [&](modp_v4d (&lo)[2][2]) {
 #pragma unroll
-        for (int i = 0; i < 4; i++) {
-            As[(a_r + 16 * i) * ZZ_LDA + a_k] = ra[i];
-            Bs[(b_k + 4 * i) * ZZ_LDB + b_c] = rb[i];
-        }
-        __syncthreads();
-        if (step + 1 < nsteps) fetch((step + 1) * ZZ_BK);                                  // (uniform) in flight while this step multiplies
+        for (int ti = 0; ti < 2; ti++)
 #pragma unroll
-        for (int kk = 0; kk < ZZ_BK / 4; kk++) {
-            // operands: A-side lane l holds A[row (l & 15), 4 kk + (l >> 4)], B-side lane l holds B[4 kk + (l >> 4), column (l & 15)]
-            double av[2], bv[2];
+            for (int tj = 0; tj < 2; tj++)
 #pragma unroll
-            for (int t = 0; t < 2; t++) {
-                av[t] = As[(wr + 16 * t + l15) * ZZ_LDA + 4 * kk + l4];
-                bv[t] = Bs[(4 * kk + l4) * ZZ_LDB + wc + 16 * t + l15];
-            }
-#pragma unroll
-            for (int ti = 0; ti < 2; ti++)
-#pragma unroll
-                for (int tj = 0; tj < 2; tj++) acc[ti][tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ti], bv[tj], acc[ti][tj], 0, 0, 0);
-        }
-        if ((step + 1) % ZZ_FLUSH_STEPS == 0) {                                            // (uniform)
-#pragma unroll
-            for (int ti = 0; ti < 2; ti++)
-#pragma unroll
-                for (int tj = 0; tj < 2; tj++)
-#pragma unroll
-                    for (int reg = 0; reg < 4; reg++) {
-                        double a = acc[ti][tj][reg], h = hi[ti][tj][reg];
-                        zz_flush(&a, &h);
-                        acc[ti][tj][reg] = a; hi[ti][tj][reg] = h;
-                    }
-        }
-    }
+                for (int reg = 0; reg < 4; reg++) {
+                    double a = lo[ti][tj][reg], h = hi[ti][tj][reg];
+                    zz_flush(&a, &h);
+                    lo[ti][tj][reg] = a; hi[ti][tj][reg] = h;
+                }
+    });
     // accumulator: column l & 15, row (l >> 4) + 4 reg
     int bad = 0;
 #pragma unroll
@@ -201,7 +151,7 @@ extern "C" int clrs_zz_gemm(int device, int m, int k, int n, int nda, const int3
     }
     const size_t mn = (size_t)m * n, M = (size_t)nda * m, ldb = (size_t)ndb * n;
     const int ns = nda + ndb;
-    const size_t bound = g_cfg_zz_gemm_chunk_bytes > 0 ? (size_t)g_cfg_zz_gemm_chunk_bytes : ZZ_GEMM_CHUNK_BYTES;
+    const size_t bound = modp_chunk_bound(g_cfg_zz_gemm_chunk_bytes, ZZ_GEMM_CHUNK_BYTES);
     const int dc = (int)std::min<size_t>((size_t)ndb, std::max<size_t>(bound / (M * (size_t)n * sizeof(double2)), 1));      // digits of B per range
     const size_t rowtiles = (M + ZZ_BM - 1) / ZZ_BM, maxcolblocks = ((size_t)dc * n + ZZ_BN - 1) / ZZ_BN;
     if (rowtiles * maxcolblocks >= (size_t)lim) return modp_fail(CLRS_ERR_INVALID, "zz_gemm: one digit of B already needs 2^31 workgroups or more");
@@ -215,18 +165,14 @@ extern "C" int clrs_zz_gemm(int device, int m, int k, int n, int nda, const int3
     int *d_cnt = nullptr;                                                                  // [0] impossibilities, [1] entries that do not fit
     MODPCHECK(bufs.get(&d_A, (size_t)na)); MODPCHECK(bufs.get(&d_B, (size_t)nb)); MODPCHECK(bufs.get(&d_Ad, (size_t)na)); MODPCHECK(bufs.get(&d_Bp, (size_t)nb));
     MODPCHECK(bufs.get(&d_P, M * (size_t)dc * n)); MODPCHECK(bufs.get(&d_S, (size_t)ns * mn)); MODPCHECK(bufs.get(&d_cnt, (size_t)2));
-    struct Events {                                                    // (released on every path, like the buffers)
-        hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
+    ModpEvents ev(5);
     for (hipEvent_t &x : ev.e) MODPCHECK(hipEventCreate(&x));
     MODPCHECK(hipEventRecord(ev.e[3], nullptr));
     MODPCHECK(hipMemcpy(d_A, A, (size_t)na * sizeof(int32_t), hipMemcpyHostToDevice));
     MODPCHECK(hipMemcpy(d_B, B, (size_t)nb * sizeof(int32_t), hipMemcpyHostToDevice));
     MODPCHECK(hipMemset(d_S, 0, (size_t)ns * mn * sizeof(long long)));
     MODPCHECK(hipMemset(d_cnt, 0, 2 * sizeof(int)));
-    const auto flat = [](size_t count) { return (unsigned)std::min<size_t>((count + ZZ_NT - 1) / ZZ_NT, 65536); };
-    hipLaunchKernelGGL(k_zz_widen, dim3(flat((size_t)na + (size_t)nb)), dim3(ZZ_NT), 0, nullptr, d_A, (size_t)na, d_Ad, d_B, k, n, ndb, d_Bp);
+    hipLaunchKernelGGL(k_zz_widen, modp_flat_grid((size_t)na + (size_t)nb, ZZ_NT), dim3(ZZ_NT), 0, nullptr, d_A, (size_t)na, d_Ad, d_B, k, n, ndb, d_Bp);
     MODPCHECK(hipGetLastError());
     double ms[2] = {0.0, 0.0};
     long long launched = 0;
@@ -239,7 +185,7 @@ extern "C" int clrs_zz_gemm(int device, int m, int k, int n, int nda, const int3
                            colblocks, d_cnt);
         MODPCHECK(hipGetLastError());
         MODPCHECK(hipEventRecord(ev.e[1], nullptr));
-        hipLaunchKernelGGL(k_zz_combine, dim3(flat((size_t)(t1 - t0 + nda) * mn)), dim3(ZZ_NT), 0, nullptr, d_P, m, n, nda, t0, t1, d_S);
+        hipLaunchKernelGGL(k_zz_combine, modp_flat_grid((size_t)(t1 - t0 + nda) * mn, ZZ_NT), dim3(ZZ_NT), 0, nullptr, d_P, m, n, nda, t0, t1, d_S);
         MODPCHECK(hipGetLastError());
         MODPCHECK(hipEventRecord(ev.e[2], nullptr));
         MODPCHECK(hipEventSynchronize(ev.e[2]));

@@ -307,6 +307,11 @@ def next_prime(x) -> int:
     return n
 
 
+def _check_modp_prime(what: str, p: int) -> None:
+    if p < 2 or p >= MODP_PRIME_LIMIT or not _is_prime(p):
+        raise ValueError(f"{what}: p must be a prime with 2 <= p < 2^23, got {p}")
+
+
 def _integer_matrix(A, what):
     """anything np.asarray takes -> a 2-d array of a numpy integer type, or of Python integers (dtype object) where those do not fit; an empty input
     becomes 0 x 0"""
@@ -346,8 +351,7 @@ def rref_mod_p(A, p: int, device: int = 0, want_rref: bool = False):
     pivot rows first and the rows behind them zero."""
     a = _integer_matrix(A, "rref_mod_p")
     p = int(p)
-    if p < 2 or p >= MODP_PRIME_LIMIT or not _is_prime(p):
-        raise ValueError(f"rref_mod_p: p must be a prime with 2 <= p < 2^23, got {p}")
+    _check_modp_prime("rref_mod_p", p)
     nrows, ncols = a.shape
     res = _residues(a, p)
     pivots = np.full(max(min(nrows, ncols), 1), -1, np.int32)
@@ -446,38 +450,114 @@ DIXON_FIRST_PRIME = 8388593          # the largest prime below 2^23: the fewest 
 LIFT_MAX_N = 32767
 
 
-def to_balanced_digits(values, count: Optional[int] = None) -> np.ndarray:
-    """Python integers of any size (anything `np.asarray` takes, any shape) -> balanced base-2^24 digits, little-endian: int32 (count, *shape), every
-    digit `d = ((v + 2^23) mod 2^24) - 2^23`, then `v <- (v - d) / 2^24`.  `count=None`: as many digits as the largest value needs (at least one);
-    otherwise `ValueError` when a value does not fit."""
+def _digits24_from_bytes(raw, rows: int, count: int) -> np.ndarray:
+    """`rows * count` little-endian digits of three bytes each (bytes, as `int.to_bytes` makes them) -> uint32 (rows, count)"""
+    wide = np.zeros((rows, count, 4), np.uint8)
+    wide[:, :, :3] = np.frombuffer(raw, dtype=np.uint8).reshape(rows, count, 3)
+    return wide.view("<u4").reshape(rows, count)
+
+
+def _digits24_to_bytes(digits) -> np.ndarray:
+    """digits in [0, 2^24), uint32 (rows, count) -> uint8 (rows, 3 count): the three low bytes of every digit, what `int.from_bytes` takes row by row"""
+    d = np.ascontiguousarray(digits, dtype="<u4")
+    return np.ascontiguousarray(d.view(np.uint8).reshape(d.shape[0], d.shape[1], 4)[:, :, :3]).reshape(d.shape[0], 3 * d.shape[1])
+
+
+def _balanced_offset(count: int) -> int:
+    """H = sum_{l < count} 2^23 2^(24 l): v + H has the digits of v, each raised by 2^23, as its digits in [0, 2^24)"""
+    return (1 << (DIGIT_BITS - 1)) * (((1 << (DIGIT_BITS * count)) - 1) // ((1 << DIGIT_BITS) - 1))
+
+
+def _balanced_need(v: int) -> int:
+    """the number of balanced digits the Python integer v needs (at least one): the smallest c with 0 <= v + H_c < 2^(24 c)"""
+    c = max(abs(v).bit_length() // DIGIT_BITS, 1)                                 # c digits hold magnitudes below 2^(24 c) only: never too many, at most two too few
+    while not 0 <= v + _balanced_offset(c) < 1 << (DIGIT_BITS * c):
+        c += 1
+    return c
+
+
+def _ints_to_planes(name: str, values, count: Optional[int]) -> np.ndarray:
+    """`to_balanced_digits` and `ints_to_planes` (`name`, for the messages): linear in the digits of every entry.  Values below 2^62 in magnitude are cut by
+    numpy on int64; for larger ones, with `H = sum_l 2^23 2^(24 l)`, the bytes of `v + H` (`int.to_bytes`) are cut into 24-bit digits and 2^23 is taken off
+    each."""
     a = np.asarray(values)
     if a.dtype != object and a.dtype.kind not in "iu":
         if a.size:
-            raise ValueError(f"to_balanced_digits: the values must be integers, got dtype {a.dtype}")
+            raise ValueError(f"{name}: the values must be integers, got dtype {a.dtype}")
         a = a.astype(np.int64)
+    if count is not None and int(count) < 1:
+        raise ValueError(f"{name}: count must be at least 1, got {count}")
+    misfit = f"{name}: a value does not fit in {count} balanced digits of {DIGIT_BITS} bits"
     half, base = 1 << (DIGIT_BITS - 1), 1 << DIGIT_BITS
-    small = a.dtype != object and (a.size == 0 or _max_abs(a) < 1 << 62)
-    v = a.astype(np.int64) if small else np.array([int(t) for t in a.flat], dtype=object).reshape(a.shape)
-    planes = []
-    while True:
-        d = ((v + half) & (base - 1)) - half if small else np.array([((int(t) + half) % base) - half for t in v.flat], dtype=object).reshape(a.shape)
-        planes.append(np.asarray(d, dtype=np.int64).astype(np.int32))
-        v = (v - d) >> DIGIT_BITS if small else np.array([(int(t) - int(e)) >> DIGIT_BITS for t, e in zip(v.flat, d.flat)], dtype=object).reshape(a.shape)
-        done = not np.any(v != 0)
-        if (count is None and done) or (count is not None and len(planes) == int(count)):
-            break
-    if not done:
-        raise ValueError(f"to_balanced_digits: a value does not fit in {count} balanced digits of {DIGIT_BITS} bits")
-    return np.ascontiguousarray(np.stack(planes))
+    if a.dtype == object:
+        flat = [int(v) for v in a.flat]
+        if all(-(1 << 62) < v < 1 << 62 for v in flat):
+            a = np.array(flat, dtype=np.int64).reshape(a.shape)
+    if a.dtype != object and (a.size == 0 or _max_abs(a) < 1 << 62):
+        v, planes = a.astype(np.int64), []
+        while True:
+            d = ((v + half) & (base - 1)) - half
+            planes.append(np.asarray(d, dtype=np.int64).astype(np.int32))
+            v = (v - d) >> DIGIT_BITS
+            done = not np.any(v != 0)
+            if done if count is None else len(planes) == int(count):
+                break
+        if not done:
+            raise ValueError(misfit)
+        return np.ascontiguousarray(np.stack(planes))
+    flat = [int(v) for v in a.flat]
+    if count is None:
+        top = max(abs(v).bit_length() for v in flat)
+        count = max(_balanced_need(v) for v in flat if abs(v).bit_length() + 2 * DIGIT_BITS >= top)     # (only the longest values can decide the count)
+    count = int(count)
+    H, nbytes = _balanced_offset(count), 3 * count
+    try:
+        raw = b"".join((v + H).to_bytes(nbytes, "little") for v in flat)
+    except OverflowError:                                           # v + H negative or 2^(24 count) and beyond
+        raise ValueError(misfit) from None
+    digits = _digits24_from_bytes(raw, len(flat), count).astype(np.int32) - np.int32(half)
+    return np.ascontiguousarray(digits.T).reshape((count,) + a.shape)
+
+
+def to_balanced_digits(values, count: Optional[int] = None) -> np.ndarray:
+    """Python integers of any size (anything `np.asarray` takes, any shape) -> balanced base-2^24 digits, little-endian: int32 (count, *shape), every
+    digit `d = ((v + 2^23) mod 2^24) - 2^23`, then `v <- (v - d) / 2^24`.  `count=None`: as many digits as the largest value needs (at least one);
+    otherwise `ValueError` when a value does not fit.  Linear in the digits of every entry."""
+    return _ints_to_planes("to_balanced_digits", values, count)
+
+
+def ints_to_planes(values, count: Optional[int] = None) -> np.ndarray:
+    """`to_balanced_digits` under the name the product functions use (its own name in the messages)."""
+    return _ints_to_planes("ints_to_planes", values, count)
 
 
 def from_balanced_digits(planes) -> np.ndarray:
-    """Digit planes (count, *shape) -> the integers `sum_l planes[l] 2^(24 l)` as Python integers (an object array of shape `shape`)."""
+    """Digit planes (count, *shape) -> the integers `sum_l planes[l] 2^(24 l)` as Python integers (an object array of shape `shape`).  Integer digits in
+    [-2^23, 2^23) take the linear way: every digit raised by 2^23, its three low bytes packed, `int.from_bytes`, and `H` taken off.  Planes with other
+    digits (2^23 itself, which clrs_zz_gemm accepts as input) go through a Horner loop."""
     planes = np.asarray(planes)
-    out = np.zeros(planes.shape[1:], dtype=object)
-    for l in range(planes.shape[0] - 1, -1, -1):
-        out = out * (1 << DIGIT_BITS) + planes[l].astype(object)
+    count, shape = planes.shape[0], planes.shape[1:]
+    half = 1 << (DIGIT_BITS - 1)
+    if planes.dtype.kind not in "iu" or planes.size == 0 or not shape or int(planes.min()) < -half or int(planes.max()) >= half:
+        out = np.zeros(shape, dtype=object)                        # (one integer, `shape` empty, leaves this loop as a Python integer, not an array)
+        for l in range(count - 1, -1, -1):
+            out = out * (1 << DIGIT_BITS) + planes[l].astype(object)
+        return out
+    packed = _digits24_to_bytes((planes.reshape(count, -1).astype(np.int64) + half).T)                                   # (entries, 3 count)
+    H, step, raw = _balanced_offset(count), 3 * count, packed.tobytes()
+    out = np.empty(shape, dtype=object)
+    out.flat = [int.from_bytes(raw[i * step:(i + 1) * step], "little") - H for i in range(packed.shape[0])]
     return out
+
+
+def planes_to_ints(planes) -> np.ndarray:
+    """`from_balanced_digits` for the planes a device call returns: at least one plane of an integer dtype, `ValueError` otherwise."""
+    planes = np.asarray(planes)
+    if planes.ndim < 1 or planes.shape[0] < 1:
+        raise ValueError(f"planes_to_ints: at least one plane is needed, got shape {planes.shape}")
+    if planes.dtype.kind not in "iu":
+        raise ValueError(f"planes_to_ints: the digits must be integers, got dtype {planes.dtype}")
+    return np.asarray(from_balanced_digits(planes), dtype=object)
 
 
 def prev_prime(x) -> int:
@@ -560,17 +640,16 @@ def dixon_lift(A, b, p: int, steps: int, device: int = 0):
     A mod p.  When rank < n nothing was lifted and X and r are None."""
     A, b = _square_system(A, b, "dixon_lift")
     n, p, steps = A.shape[0], int(p), int(steps)
-    if p < 2 or p >= MODP_PRIME_LIMIT or not _is_prime(p):
-        raise ValueError(f"dixon_lift: p must be a prime with 2 <= p < 2^23, got {p}")
+    _check_modp_prime("dixon_lift", p)
     if n > LIFT_MAX_N or steps < 0:
         raise ValueError(f"dixon_lift: n must be at most {LIFT_MAX_N} and steps at least 0, got n = {n}, steps = {steps}")
-    Ad = to_balanced_digits(A) if n else np.zeros((1, 0, 0), np.int32)
-    bl = to_balanced_digits(b) if n else np.zeros((1, 0), np.int32)
+    Ad = ints_to_planes(A) if n else np.zeros((1, 0, 0), np.int32)
+    bl = ints_to_planes(b) if n else np.zeros((1, 0), np.int32)
     X, r, info = _dixon_lift_digits(Ad, bl, p, steps, device=device)
     rank = int(info[0])
     if rank < n:
         return None, None, rank
-    return X, from_balanced_digits(r), rank
+    return X, planes_to_ints(r), rank
 
 
 def rational_reconstruction(a: int, m: int, N: int, D: int):
@@ -597,21 +676,17 @@ def to_digits24(value: int, count: Optional[int] = None) -> np.ndarray:
     count = need if count is None else int(count)
     if count < need:
         raise ValueError(f"to_digits24: the value does not fit in {count} digits of {DIGIT_BITS} bits")
-    raw = np.frombuffer(value.to_bytes(3 * count, "little"), dtype=np.uint8).reshape(count, 3)
-    out = np.zeros((count, 4), np.uint8)
-    out[:, :3] = raw
-    return np.ascontiguousarray(out.view("<u4").reshape(count).astype(np.int32))
+    return np.ascontiguousarray(_digits24_from_bytes(value.to_bytes(3 * count, "little"), 1, count)[0].astype(np.int32))
 
 
 def from_digits24(digits) -> list:
     """Rows of little-endian digits in [0, 2^24) (int32, shape (count,) or (rows, count)) -> the Python integer of every row (an integer for one row given
-    as (count,), else a list).  Linear in the digit count: the three low bytes of every digit packed, then `int.from_bytes` (`from_balanced_digits` is a
-    Horner loop over the digits, quadratic)."""
+    as (count,), else a list).  Linear in the digit count: the three low bytes of every digit packed, then `int.from_bytes`."""
     d = np.ascontiguousarray(digits, dtype="<u4")
     if d.size and int(d.max()) >= 1 << DIGIT_BITS:
         raise ValueError("from_digits24: a digit outside [0, 2^24)")
     rows = d.reshape(-1, d.shape[-1]) if d.ndim > 1 else d.reshape(1, -1)
-    packed = np.ascontiguousarray(rows.view(np.uint8).reshape(rows.shape[0], rows.shape[1], 4)[:, :, :3])
+    packed = _digits24_to_bytes(rows)
     out = [int.from_bytes(packed[i].tobytes(), "little") for i in range(rows.shape[0])]
     return out if d.ndim > 1 else out[0]
 
@@ -636,8 +711,7 @@ def dixon_reconstruct(X, p: int, N: int, D: int, device: int = 0, want_x: bool =
         raise ValueError(f"dixon_reconstruct: X must be (steps, n), got shape {X.shape}")
     steps, n = X.shape
     p, N, D = int(p), int(N), int(D)
-    if p < 2 or p >= MODP_PRIME_LIMIT or not _is_prime(p):
-        raise ValueError(f"dixon_reconstruct: p must be a prime with 2 <= p < 2^23, got {p}")
+    _check_modp_prime("dixon_reconstruct", p)
     if steps < 1 or n > LIFT_MAX_N or N < 0 or D < 0:
         raise ValueError(f"dixon_reconstruct: steps must be at least 1, n at most {LIFT_MAX_N} and the bounds not negative")
     if n == 0:
@@ -1164,78 +1238,6 @@ def is_valid_solution(blocks, A=None, b=None, x=None, check_slacks: bool = True,
 ZZ_MAX_DIGITS = 32767                # digit planes of an operand or of the result of clrs_zz_gemm
 
 
-def _balanced_offset(count: int) -> int:
-    """H = sum_{l < count} 2^23 2^(24 l): v + H has the digits of v, each raised by 2^23, as its digits in [0, 2^24)"""
-    return (1 << (DIGIT_BITS - 1)) * (((1 << (DIGIT_BITS * count)) - 1) // ((1 << DIGIT_BITS) - 1))
-
-
-def _balanced_need(v: int) -> int:
-    """the number of balanced digits the Python integer v needs (at least one): the smallest c with 0 <= v + H_c < 2^(24 c)"""
-    c = max(abs(v).bit_length() // DIGIT_BITS, 1)                                 # c digits hold magnitudes below 2^(24 c) only: never too many, at most two too few
-    while not 0 <= v + _balanced_offset(c) < 1 << (DIGIT_BITS * c):
-        c += 1
-    return c
-
-
-def ints_to_planes(values, count: Optional[int] = None) -> np.ndarray:
-    """What `to_balanced_digits(values, count)` returns -- int32 (count, *shape), little-endian balanced base-2^24 digits -- in time linear in the digits of
-    every entry: with `H = sum_l 2^23 2^(24 l)` the bytes of `v + H` (`int.to_bytes`) are cut into 24-bit digits by numpy and 2^23 is taken off each.
-    `count=None`: as many digits as the largest value needs (at least one); otherwise `ValueError` when a value does not fit."""
-    a = np.asarray(values)
-    if a.dtype != object and a.dtype.kind not in "iu":
-        if a.size:
-            raise ValueError(f"ints_to_planes: the values must be integers, got dtype {a.dtype}")
-        a = a.astype(np.int64)
-    if a.dtype == object:
-        flat = [int(v) for v in a.flat]
-        if all(-(1 << 62) < v < 1 << 62 for v in flat):
-            a = np.array(flat, dtype=np.int64).reshape(a.shape)
-    if a.dtype != object and (a.size == 0 or _max_abs(a) < 1 << 62):
-        try:
-            return to_balanced_digits(a, count)                   # (vectorised there for values of this size, and linear)
-        except ValueError:
-            raise ValueError(f"ints_to_planes: a value does not fit in {count} balanced digits of {DIGIT_BITS} bits") from None
-    flat = [int(v) for v in a.flat]
-    if count is None:
-        top = max(abs(v).bit_length() for v in flat)
-        count = max(_balanced_need(v) for v in flat if abs(v).bit_length() + 2 * DIGIT_BITS >= top)     # (only the longest values can decide the count)
-    count = int(count)
-    if count < 1:
-        raise ValueError(f"ints_to_planes: count must be at least 1, got {count}")
-    H, nbytes = _balanced_offset(count), 3 * count
-    try:
-        raw = b"".join((v + H).to_bytes(nbytes, "little") for v in flat)
-    except OverflowError:                                           # v + H negative or 2^(24 count) and beyond
-        raise ValueError(f"ints_to_planes: a value does not fit in {count} balanced digits of {DIGIT_BITS} bits") from None
-    wide = np.zeros((len(flat), count, 4), np.uint8)
-    wide[:, :, :3] = np.frombuffer(raw, dtype=np.uint8).reshape(len(flat), count, 3)
-    digits = wide.view("<u4").reshape(len(flat), count).astype(np.int32) - np.int32(1 << (DIGIT_BITS - 1))
-    return np.ascontiguousarray(digits.T).reshape((count,) + a.shape)
-
-
-def planes_to_ints(planes) -> np.ndarray:
-    """What `from_balanced_digits(planes)` returns -- digit planes (count, *shape) -> an object array `shape` of the Python integers
-    `sum_l planes[l] 2^(24 l)` -- in time linear in the digits: every digit raised by 2^23, its three low bytes packed, `int.from_bytes`, and `H` taken off.
-    Digits in [-2^23, 2^23) take that way; planes with other digits go through `from_balanced_digits`."""
-    planes = np.asarray(planes)
-    if planes.ndim < 1 or planes.shape[0] < 1:
-        raise ValueError(f"planes_to_ints: at least one plane is needed, got shape {planes.shape}")
-    if planes.dtype.kind not in "iu":
-        raise ValueError(f"planes_to_ints: the digits must be integers, got dtype {planes.dtype}")
-    count, shape = planes.shape[0], planes.shape[1:]
-    half = 1 << (DIGIT_BITS - 1)
-    out = np.empty(shape, dtype=object)
-    if planes.size == 0:
-        return out
-    if int(planes.min()) < -half or int(planes.max()) >= half:
-        return from_balanced_digits(planes)
-    raised = np.ascontiguousarray((planes.reshape(count, -1).astype(np.int64) + half).T.astype("<u4"))               # (entries, count)
-    packed = np.ascontiguousarray(raised.view(np.uint8).reshape(raised.shape[0], count, 4)[:, :, :3])
-    H, step, raw = _balanced_offset(count), 3 * count, packed.tobytes()
-    out.flat = [int.from_bytes(raw[i * step:(i + 1) * step], "little") - H for i in range(raised.shape[0])]
-    return out
-
-
 def _zz_gemm_planes(Ad, Bd, ndc: int, device: int = 0):
     """One call of clrs_zz_gemm on digit planes: `Ad` int32 (nda, m, k), `Bd` int32 (ndb, k, n) -> `(C, info)`, C int32 (ndc, m, n), info int32 (4,).  The
     counters are written before the call raises, so `info` can be read from `zz_matmul.last_info` after a refusal for `ndc` too small."""
@@ -1358,8 +1360,7 @@ def dixon_lift_multi(A, B, p: int, steps: int, device: int = 0):
     m = B.shape[1]
     B = _object_matrix(_integer_matrix(B, "dixon_lift_multi"), "dixon_lift_multi") if B.size else np.zeros((n, m), dtype=object)
     p, steps = int(p), int(steps)
-    if p < 2 or p >= MODP_PRIME_LIMIT or not _is_prime(p):
-        raise ValueError(f"dixon_lift_multi: p must be a prime with 2 <= p < 2^23, got {p}")
+    _check_modp_prime("dixon_lift_multi", p)
     if n > LIFT_MAX_N or steps < 0:
         raise ValueError(f"dixon_lift_multi: n must be at most {LIFT_MAX_N} and steps at least 0, got n = {n}, steps = {steps}")
     if n == 0 or m == 0:

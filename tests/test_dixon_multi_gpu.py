@@ -86,6 +86,22 @@ def test_extreme_and_boundary_systems():
         assert np.array_equal(A.dot(x), B - p ** STEPS * R)
 
 
+@pytest.mark.parametrize("n", [160, 240])                          # 10 and 15 steps of k_liftm_x: across its period of 7 once and twice
+def test_row_sums_past_2_53_need_the_periodic_reduction(n):
+    """Operands planted so that the first product of the lifting, X_0 = A^-1 B mod p, has exact row sums that are odd and above 2^53: no fp64 value equals
+    them, so k_liftm_x is right only if it reduces on the way.  C = -(2J + I) mod p (J all ones: p - 2 off the diagonal, p - 3 on it) is the inverse mod p of
+    A = -(I - 2J / (2n + 1)) mod p, taken entrywise into [0, p): one digit; every entry of B is p - 2."""
+    p = du.PMAX
+    t = 2 * pow(2 * n + 1, -1, p) % p
+    A = du.objects([[(t - 1) % p if i == j else t for j in range(n)] for i in range(n)])
+    C = np.array([[p - 3 if i == j else p - 2 for j in range(n)] for i in range(n)], dtype=object)
+    assert ((A.dot(C) - np.eye(n, dtype=np.int64)) % p == 0).all()
+    rowsum = (n - 1) * (p - 2) ** 2 + (p - 3) * (p - 2)
+    assert rowsum > 2 ** 53 and rowsum % 2 == 1 and int(float(rowsum)) != rowsum
+    X, R, nd = check_case(A, du.objects(np.full((n, 2), p - 2)), p, steps=2)
+    assert nd == 1 and (X[0] == rowsum % p).all()
+
+
 def test_chunks_do_not_change_the_result():
     L = _lib.load()
     n, m, nd, p = 65, 65, 2, du.PMAX

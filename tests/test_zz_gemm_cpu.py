@@ -24,8 +24,10 @@ def test_flush_period_of_the_kernel_is_within_the_bound():
     assert (most, bits) == (31, 24) and 1 <= taken <= most and steps * 4 == taken
     # the bound itself: a remainder of 2^23 plus 4 F products of 2^46 stays below 2^53 iff F <= 31
     assert HALF + 4 * 31 * 2 ** 46 < 2 ** 53 <= HALF + 4 * 32 * 2 ** 46
-    src = open(os.path.join(ROOT, "clusteredlowranksolver.jl_amd", "csrc", "clrs_modp_zz_gemm.hip.h")).read()
-    assert re.search(r"^#define ZZ_BK 16\b", src, flags=re.M) and "ZZ_FLUSH_MFMAS / (ZZ_BK / 4)" in src and "static_assert(ZZ_FLUSH_STEPS" in src
+    csrc = os.path.join(ROOT, "clusteredlowranksolver.jl_amd", "csrc")
+    src, tile = open(os.path.join(csrc, "clrs_modp_zz_gemm.hip.h")).read(), open(os.path.join(csrc, "clrs_modp_tile.hip.h")).read()
+    assert re.search(r"^#define ZZ_BK 16\b", tile, flags=re.M) and "ZZ_FLUSH_MFMAS / (ZZ_BK / 4)" in src and "static_assert(ZZ_FLUSH_STEPS" in src
+    assert "zz_tile_loop<ZZ_FLUSH_STEPS>" in src                    # the period the kernel hands to the shared loop is the one asserted
 
 
 def test_split_at_the_ends_at_ties_and_at_zero():
@@ -157,44 +159,54 @@ def test_sanitizer_program_ends_clean():
 # ---- the digit conversions -------------------------------------------------------------------------------------------------------------------------------------
 def _boundary_values():
     out = [0, 1, -1, HALF, -HALF, HALF - 1, 1 - HALF, HALF + 1, -HALF - 1]
+    out += [s << (24 * c - 1) for c in (1, 2, 3) for s in (1, -1)]   # +-2^(24 c - 1): one digit more on the positive side than on the negative
     for l in (1, 2, 3, 10, 100, 417):
         for base in (1 << (24 * l), (1 << (24 * l)) // 2, zu.rounding._balanced_offset(l), (1 << (24 * l)) - 1 - zu.rounding._balanced_offset(l)):
             out += [s * (base + d) for s in (1, -1) for d in (-1, 0, 1)]
     return out
 
 
+TO_PLANES = (rounding.ints_to_planes, rounding.to_balanced_digits)
+FROM_PLANES = (rounding.planes_to_ints, rounding.from_balanced_digits)
+
+
 def test_ints_to_planes_and_back_against_the_oracles():
+    """both names of either direction against tests/zz_util.py's plain restatement of the definition (which shares no code with them)"""
     rng = np.random.default_rng(11)
     values = _boundary_values()
-    for bits in (1, 23, 24, 25, 47, 48, 62, 63, 64, 65, 1000, 24 * 300, 100000):
+    for bits in (1, 23, 24, 25, 47, 48, 62, 63, 64, 65, 1000, 5000, 24 * 300, 100000):
         for _ in range(3):
             v = int.from_bytes(rng.bytes((bits + 7) // 8), "little") >> ((-bits) % 8)
             values += [v, -v]
+    assert any(abs(v).bit_length() == 5000 for v in values)
     for v in values:                                                # one by one: the count of each
         a = np.array([v], dtype=object)
-        planes = rounding.ints_to_planes(a)
-        if abs(v).bit_length() <= 24 * 300:
-            assert np.array_equal(planes, rounding.to_balanced_digits(a)), v
-        else:                                                       # (the oracle is quadratic: at 10^5 bits only the properties)
-            assert planes.dtype == np.int32 and planes.min() >= -HALF and planes.max() < HALF and planes[-1, 0] != 0
-        assert rounding.planes_to_ints(planes)[0] == v
-        assert rounding._balanced_need(v) == planes.shape[0]
-        if abs(v).bit_length() <= 24 * 100:
-            assert rounding.from_balanced_digits(planes)[0] == v
+        for to_planes, from_planes in zip(TO_PLANES, FROM_PLANES):
+            planes = to_planes(a)
+            if abs(v).bit_length() <= 24 * 300:
+                want = zu.digits_restated(a)
+                assert planes.dtype == want.dtype and planes.shape == want.shape and np.array_equal(planes, want), v
+                assert zu.values_of(planes)[0] == v
+            else:                                                   # (the restatement is quadratic: at 10^5 bits only the properties)
+                assert planes.dtype == np.int32 and planes.min() >= -HALF and planes.max() < HALF and planes[-1, 0] != 0
+            assert from_planes(planes)[0] == v and type(from_planes(planes)[0]) is int
+            assert rounding._balanced_need(v) == planes.shape[0]
+    assert zu.digits_restated([HALF - 1]).tolist() == [[HALF - 1]] and zu.digits_restated([HALF]).shape[0] == 2 and zu.digits_restated([-HALF]).shape[0] == 1
     short = [v for v in values if abs(v).bit_length() <= 24 * 100]
     mixed = np.array(short + [0] * (-len(short) % 4), dtype=object).reshape(4, -1)        # together: one count for all, shapes kept
-    planes = rounding.ints_to_planes(mixed)
-    assert planes.shape[1:] == mixed.shape and np.array_equal(planes, rounding.to_balanced_digits(mixed))
-    assert np.array_equal(rounding.ints_to_planes(mixed, count=planes.shape[0] + 5), rounding.to_balanced_digits(mixed, count=planes.shape[0] + 5))
-    back = rounding.planes_to_ints(planes)
-    assert back.shape == mixed.shape and back.dtype == object and all(type(v) is int for v in back.flat) and (back == mixed).all()
     small = np.array([[1, -2 ** 40], [HALF, -HALF]], dtype=np.int64)
-    assert np.array_equal(rounding.ints_to_planes(small), rounding.to_balanced_digits(small))
-    assert np.array_equal(rounding.ints_to_planes([[3, 4]], count=3), rounding.to_balanced_digits([[3, 4]], count=3))
-    assert rounding.ints_to_planes(np.zeros((0, 3), np.int64)).shape == rounding.to_balanced_digits(np.zeros((0, 3), np.int64)).shape
-    # digits that include 2^23 (what clrs_zz_gemm accepts as input) still give the value
-    loose = np.array([[[HALF, -HALF]], [[HALF, 5]]], np.int32)
-    assert (rounding.planes_to_ints(loose) == rounding.from_balanced_digits(loose)).all()
+    loose = np.array([[[HALF, -HALF]], [[HALF, 5]]], np.int32)      # digits that include 2^23 (what clrs_zz_gemm accepts as input) still give the value
+    for to_planes, from_planes in zip(TO_PLANES, FROM_PLANES):
+        planes = to_planes(mixed)
+        assert planes.shape[1:] == mixed.shape and np.array_equal(planes, zu.digits_restated(mixed))
+        assert np.array_equal(to_planes(mixed, count=planes.shape[0] + 5), zu.digits_restated(mixed, count=planes.shape[0] + 5))
+        back = from_planes(planes)
+        assert back.shape == mixed.shape and back.dtype == object and all(type(v) is int for v in back.flat) and (back == mixed).all()
+        assert np.array_equal(to_planes(small), zu.digits_restated(small))
+        assert np.array_equal(to_planes([[3, 4]], count=3), zu.digits_restated([[3, 4]], count=3))
+        empty = to_planes(np.zeros((0, 3), np.int64))
+        assert empty.shape == (1, 0, 3) and empty.dtype == np.int32 and to_planes(np.zeros((0, 3), np.int64), count=4).shape == (4, 0, 3)
+        assert (from_planes(loose) == zu.values_of(loose)).all() and from_planes(loose).tolist() == [[HALF + HALF * BASE, -HALF + 5 * BASE]]
 
 
 def test_ints_to_planes_refuses_a_count_too_small():
@@ -211,6 +223,13 @@ def test_ints_to_planes_refuses_a_count_too_small():
         rounding.ints_to_planes(np.array([0.5]))
     with pytest.raises(ValueError):
         rounding.planes_to_ints(np.zeros((0, 3), np.int32))
+    # every name speaks for itself
+    for name in ("ints_to_planes", "to_balanced_digits"):
+        for a in (np.array([HALF]), np.array([10 ** 400], dtype=object)):
+            with pytest.raises(ValueError, match=f"^{name}: a value does not fit in 1 balanced digits of 24 bits$"):
+                getattr(rounding, name)(a, count=1)
+        with pytest.raises(ValueError, match=f"^{name}: the values must be integers, got dtype float64$"):
+            getattr(rounding, name)(np.array([0.5]))
 
 
 # ---- the matmul= hooks -------------------------------------------------------------------------------------------------------------------------------------------

@@ -24,9 +24,37 @@ _pd = lambda a: a.ctypes.data_as(_lib.p_d)
 
 
 # ---- the oracle --------------------------------------------------------------------------------------------------------------------------------------------
+def digits_restated(values, count=None):
+    """The definition of balanced base-2^24 digits, digit by digit on Python integers, independent of clrs_amd.rounding: d = ((v + 2^23) mod 2^24) - 2^23,
+    v <- (v - d) / 2^24.  Any shape -> int32 (count, *shape); `count=None`: as many digits as the longest value needs (at least one); a value that does not
+    fit in `count` digits is an AssertionError."""
+    a = np.asarray(values, dtype=object)
+    rows = []
+    for v in a.flat:
+        v, row = int(v), []
+        while True:
+            d = ((v + HALF) % BASE) - HALF
+            row.append(d)
+            v = (v - d) // BASE
+            if v == 0 and (count is None or len(row) >= count):
+                break
+        rows.append(row)
+    nd = max([len(r) for r in rows] + [1]) if count is None else count
+    assert all(len(r) <= nd for r in rows), "a value does not fit"
+    out = np.zeros((nd, len(rows)), np.int32)
+    for e, row in enumerate(rows):
+        out[:len(row), e] = row
+    return out.reshape((nd,) + a.shape)
+
+
 def values_of(planes):
-    """digit planes (nd, rows, cols), digits anywhere in [-2^23, 2^23] -> the object matrix of Python integers"""
-    return rounding.from_balanced_digits(np.asarray(planes))
+    """digit planes (nd, *shape), digits anywhere in [-2^23, 2^23] -> the object array of the Python integers sum_l planes[l] 2^(24 l), by Horner: like
+    `digits_restated` independent of clrs_amd.rounding"""
+    planes = np.asarray(planes)
+    out = np.zeros(planes.shape[1:], dtype=object)
+    for l in range(planes.shape[0] - 1, -1, -1):
+        out = out * BASE + planes[l].astype(object)
+    return out
 
 
 def exact_product(Ad, Bd):
@@ -35,11 +63,11 @@ def exact_product(Ad, Bd):
 
 
 def digits_needed(exact):
-    return rounding.to_balanced_digits(exact).shape[0]
+    return digits_restated(exact).shape[0]
 
 
 def expected_planes(exact, ndc):
-    return rounding.to_balanced_digits(exact, count=ndc)
+    return digits_restated(exact, count=ndc)
 
 
 # ---- operands ----------------------------------------------------------------------------------------------------------------------------------------------
