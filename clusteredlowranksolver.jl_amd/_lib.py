@@ -167,6 +167,8 @@ SYMBOLS = {
     "clrs_zz_gemm_times": (C.c_int, [p_d, p_d, p_d]),
     "clrs_modp_dixon_lift_multi": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, p_i32, C.c_int, p_i32, C.c_int, p_i32, p_i32, p_i32]),
     "clrs_modp_dixon_lift_multi_times": (C.c_int, [p_d, p_d, p_d, p_d]),
+    "clrs_zz_lowrank_system": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_i32, C.c_int, p_i32, C.c_int, p_i32, C.c_int, p_i32, p_i32, C.c_int, p_i32, p_i32]),
+    "clrs_zz_lowrank_system_times": (C.c_int, [p_d, p_d, p_d]),
     "clrs_mw_schur_solve": (C.c_int, [C.c_void_p, p_d, p_d, p_d, p_d]),
     "clrs_mw_cholesky_blocks_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "clrs_mw_sync_status_cholesky": (C.c_int, [C.c_void_p]),

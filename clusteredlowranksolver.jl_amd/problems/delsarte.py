@@ -77,3 +77,36 @@ def delsarte_exact(n, d, costheta, prec=DEFAULT_PREC) -> ClusteredLowRankSDP:
         Cs.append(np.zeros((d, d)))
         return ClusteredLowRankSDP(maximize=False, constant=1.0, blocks=[blocks], B=[np.zeros((ns, 0))], c=[-np.ones(ns)], C=[Cs],
                                    b=np.zeros(0), names={"free": [], "blocks": [[b.name for b in blocks]]})
+
+
+def delsarte_exact_problem(n, d, costheta):
+    """`delsarte_exact` over QQ, the problem `rounding.exact_solution` rounds to: the same four-decimal samples, the Chebyshev and Gegenbauer recurrences of
+    polytools in `Fraction`s.  `delsarte_exact_problem(n, d, costheta).to_sdp(prec)` is `delsarte_exact(n, d, costheta, prec)`."""
+    from fractions import Fraction as F
+    from ..rounding import ExactBlock, ExactLowRank, ExactProblem
+    ct = F(costheta)
+    with mp.workprec(DEFAULT_PREC):
+        xs = [F(int(mp.nint(x * 10 ** 4)), 10 ** 4) for x in sample_points_chebyshev(2 * d)]
+    ns = len(xs)
+
+    def recurrence(deg, step):
+        V = np.empty((ns, deg + 1), dtype=object)
+        for i, x in enumerate(xs):
+            V[i, 0] = F(1)
+            if deg >= 1:
+                V[i, 1] = x
+            for l in range(2, deg + 1):
+                V[i, l] = step(l, x, V[i, l - 1], V[i, l - 2])
+        return V
+    V = recurrence(d, lambda l, x, v1, v2: 2 * x * v1 - v2)
+    G = recurrence(2 * d, lambda l, x, v1, v2: F(2 * l + n - 4, l + n - 3) * x * v1 - F(l - 1, l + n - 3) * v2)
+    blocks, Cs = [], []
+    for k in range(2 * d + 1):
+        blocks.append(ExactBlock(1, 1, {(0, 0): {p: np.array([[G[p, k]]], dtype=object) for p in range(ns)}}, ("a", k)))
+        Cs.append(np.array([[F(1)]], dtype=object))
+    blocks.append(ExactBlock(1, d + 1, {(0, 0): {p: ExactLowRank([F(1)], V[p:p + 1, :d + 1], V[p:p + 1, :d + 1]) for p in range(ns)}}, "A"))
+    Cs.append(np.full((d + 1, d + 1), F(0), dtype=object))
+    blocks.append(ExactBlock(1, d, {(0, 0): {p: ExactLowRank([(1 + xs[p]) * (ct - xs[p])], V[p:p + 1, :d], V[p:p + 1, :d]) for p in range(ns)}}, "B"))
+    Cs.append(np.full((d, d), F(0), dtype=object))
+    return ExactProblem(False, F(1), [blocks], [np.zeros((ns, 0), dtype=object)], [np.full(ns, F(-1), dtype=object)], [Cs], np.zeros(0, dtype=object),
+                        {"free": [], "blocks": [[b.name for b in blocks]]})

@@ -31,7 +31,12 @@ basis vectors]`, `Binv = inv(B)` over QQ, its rows normalised by the lcm of thei
 which multiply with it.  The inverse is an exact solve with a matrix of right-hand sides: Dixon's lifting with both products of a step as fp64 MFMA GEMMs on
 the device (clrs_modp_dixon_lift_multi): `dixon_lift_multi`, `solve_dixon_multi`, `inverse_qq`, `complete_basis`,
 `basis_transformations`, `transform`, `undo_transform`.  Only the reference's unreduced branch is built: the HNF / LLL reduction of the kernel vectors
-(`reduce_kernelvectors`) and the assembly of the rational linear system are not on the device yet.
+(`reduce_kernelvectors`) is not on the device yet.
+
+The system the projection solves is assembled from an `ExactProblem` (the problem over QQ; `to_sdp` gives the numeric one) by `linear_system`
+(`partial_linearsystem`, src/interface.jl:1354-1535): per low-rank block one call of clrs_zz_lowrank_system, a row-wise Gram of long
+integers with the digit index in the k-extent of the fp64 MFMA: `lowrank_system`, `system_index`, `select_columns` (src/rounding.jl:95-153),
+`get_rational_system` (src/rounding.jl:1284-1296).  `exact_solution` (src/rounding.jl:1366-1409) calls the steps in order.
 """
 from __future__ import annotations
 
@@ -48,7 +53,8 @@ __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vecto
            "prev_prime", "dixon_steps", "dixon_lift", "rational_reconstruction", "SingularSystemError", "DixonSolution", "solve_dixon",
            "solve_system_pseudoinverse", "project_to_affine_space", "to_digits24", "from_digits24", "dixon_reconstruct", "leading_minors_mod", "minor_bounds", "crt_tree",
            "PDCertificate", "checkpd", "is_valid_solution", "ints_to_planes", "planes_to_ints", "zz_matmul", "dixon_lift_multi", "DixonSolutionMatrix",
-           "solve_dixon_multi", "inverse_qq", "complete_basis", "basis_transformations", "transform", "undo_transform"]
+           "solve_dixon_multi", "inverse_qq", "complete_basis", "basis_transformations", "transform", "undo_transform", "lowrank_system", "ExactLowRank", "ExactBlock",
+           "ExactProblem", "ExactSolution", "system_index", "linear_system", "select_columns", "vectorize_solution", "get_rational_system", "exact_solution"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -66,6 +72,8 @@ class RoundingSettings:
     extracolumns_linindep: bool = False     # take the extra columns linearly independent of each other instead of at random
     reduce_kernelvectors: bool = True       # HNF / LLL reduction of the kernel vectors (src/rounding.jl:860-1060): not built, basis_transformations refuses it
     normalize_transformation: bool = True   # rows of Binv times the lcm of their denominators, columns of B divided by it (src/rounding.jl:844-850)
+    approximation_decimals: int = 40        # the numeric solution is cut to this many decimals before the projection (roundx, src/rounding.jl:515)
+    redundancyfactor: int = 10              # select_columns takes about this many columns per constraint; negative: all (src/rounding.jl:95-153)
 
     def __post_init__(self):
         if self.pseudo_columnfactor < 1:
@@ -1587,15 +1595,14 @@ def basis_transformations(kernels, settings: Optional[RoundingSettings] = None, 
     zero in the rows of the e_j taken with j > i; otherwise the prime of `complete_basis` divided a deciding minor and the next prime is taken (at most
     `maxprimes` times, then `ArithmeticError`).
     With `settings.reduce_kernelvectors` true (the default, as in the reference) this raises `NotImplementedError`: the HNF / LLL reduction of the kernel
-    vectors (`reduction_step`, src/rounding.jl:860-1060) is not on the device yet; neither are the assembly of the rational linear system and number fields
-    of degree above 1.  Pass `RoundingSettings(reduce_kernelvectors=False)`.
+    vectors (`reduction_step`, src/rounding.jl:860-1060) is not on the device yet; neither are number fields of degree above 1.  Pass
+    `RoundingSettings(reduce_kernelvectors=False)`.
     `batch` goes to `complete_basis`; `lift`, `check`, `reconstruct`, `matmul` go to `inverse_qq`."""
     from math import gcd
     settings = RoundingSettings() if settings is None else settings
     if settings.reduce_kernelvectors:
         raise NotImplementedError("basis_transformations: settings.reduce_kernelvectors is true, but the HNF / LLL reduction of the kernel vectors is not on "
-                                  "the device yet (nor are the assembly of the rational system and number fields of degree above 1); "
-                                  "pass RoundingSettings(reduce_kernelvectors=False)")
+                                  "the device yet (nor are number fields of degree above 1); pass RoundingSettings(reduce_kernelvectors=False)")
     out = {}
     for key, (N, vectors) in kernels.items():
         N, vectors = int(N), list(vectors)
@@ -1632,3 +1639,473 @@ def basis_transformations(kernels, settings: Optional[RoundingSettings] = None, 
                 B[:, i] = [v / l for v in B[:, i]]
         out[key] = (B.T.copy(), Binv.copy(), s)
     return out
+
+
+# ---- the rational linear system and the driver (src/interface.jl:1354-1535, src/rounding.jl:95-179, 1284-1296, 1366-1409; clrs_zz_lowrank_system) ----
+LRSYS_MAX_K = 1 << 14                # clrs_zz_lowrank_system: (most terms of a row) min(ndu, ndw) stays below this
+
+
+def _lowrank_system_planes(Ud, Wd, rowptr, col_a, col_b, ndc: int, device: int = 0):
+    """One call of clrs_zz_lowrank_system on digit planes: `Ud` int32 (ndu, n, T), `Wd` int32 (ndw, n, T), `rowptr` (R + 1,), the pairs `col_a`, `col_b`
+    (nc,) -> `(C, info)`, C int32 (ndc, R, nc), info int32 (4,).  The counters are written before the call raises: `lowrank_system.last_info`."""
+    Ud, Wd = np.ascontiguousarray(Ud, dtype=np.int32), np.ascontiguousarray(Wd, dtype=np.int32)
+    rowptr, col_a, col_b = (np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (rowptr, col_a, col_b))
+    if Ud.ndim != 3 or Wd.ndim != 3 or Ud.shape[1:] != Wd.shape[1:] or rowptr.size < 1 or col_a.size != col_b.size:
+        raise ValueError(f"lowrank_system: the digits must be (ndu, n, T) and (ndw, n, T), got {Ud.shape} and {Wd.shape}")
+    (ndu, n, T), ndw, R, nc = Ud.shape, Wd.shape[0], rowptr.size - 1, col_a.size
+    Cd, info = np.zeros((int(ndc), R, nc), np.int32), np.zeros(4, np.int32)
+    ptr = lambda a: a.ctypes.data_as(_lib.p_i32) if a.size else C_NULL_I32
+    try:
+        _lib.check(_lib.load().clrs_zz_lowrank_system(int(device), n, T, R, ptr(rowptr), ndu, ptr(Ud), ndw, ptr(Wd), nc, ptr(col_a), ptr(col_b), int(ndc), ptr(Cd),
+                                                      info.ctypes.data_as(_lib.p_i32)))
+    finally:
+        lowrank_system.last_info = [int(v) for v in info]
+    return Cd, info
+
+
+def _pairs_of(pairs, n: int, what: str):
+    """pairs (a, b) with 0 <= a <= b < n -> two int32 vectors"""
+    p = np.asarray(list(pairs), dtype=np.int64).reshape(-1, 2)
+    if p.size and (p.min() < 0 or p.max() >= n or np.any(p[:, 0] > p[:, 1])):
+        raise ValueError(f"{what}: every pair (a, b) needs 0 <= a <= b < {n}")
+    return np.ascontiguousarray(p[:, 0], dtype=np.int32), np.ascontiguousarray(p[:, 1], dtype=np.int32)
+
+
+def _row_pointer(rowptr, T: int, what: str) -> np.ndarray:
+    rp = np.asarray(rowptr, dtype=np.int64).reshape(-1)
+    if rp.size < 1 or rp[0] != 0 or rp[-1] != T or np.any(np.diff(rp) < 0):
+        raise ValueError(f"{what}: rowptr must be non-decreasing from 0 to the number of terms {T}")
+    return rp
+
+
+def lowrank_system(U, W, rowptr, pairs, device: int = 0) -> np.ndarray:
+    """The rows of a linear system from low-rank terms on the device, one call of clrs_zz_lowrank_system: `U`, `W` (n, T) integer
+    matrices of any size (one column per term), `rowptr` (R + 1,) the terms of every row, `pairs` the (a, b), 0 <= a <= b < n, of the nc columns.  Returns the
+    object array (R, nc) of the Python integers `2^(a != b) sum_{t in row i} U[a, t] W[b, t]`.  The operands cross in balanced base-2^24 digits
+    (`ints_to_planes`); the result takes `ndc` digits computed from `2 (most terms of a row) max|U| max|W|`.  The counters of the call are kept in
+    `lowrank_system.last_info` (`[entries that did not fit, chunks of rows, tile workgroups, 0]`).  This is the default `assemble=` of `linear_system`."""
+    u, _ = _integer_operand(U, "lowrank_system")
+    w, _ = _integer_operand(W, "lowrank_system")
+    if u.shape != w.shape:
+        raise ValueError(f"lowrank_system: U and W must have the same shape (n, T), got {u.shape} and {w.shape}")
+    n, T = u.shape
+    rp = _row_pointer(rowptr, T, "lowrank_system")
+    col_a, col_b = _pairs_of(pairs, n, "lowrank_system")
+    R, nc = rp.size - 1, col_a.size
+    out = np.zeros((R, nc), dtype=object)
+    if R and nc and T:
+        Ud, Wd = ints_to_planes(u), ints_to_planes(w)
+        rmax = int(np.diff(rp).max())
+        if rmax * min(Ud.shape[0], Wd.shape[0]) >= LRSYS_MAX_K:
+            raise ValueError(f"lowrank_system: (terms of a row) * (digits of the shorter operand) = {rmax * min(Ud.shape[0], Wd.shape[0])} must be below {LRSYS_MAX_K}")
+        bound = 2 * rmax * max(abs(int(u.max())), abs(int(u.min()))) * max(abs(int(w.max())), abs(int(w.min())))
+        ndc = max((bound.bit_length() + DIGIT_BITS + 1) // DIGIT_BITS, 1)          # 24 ndc >= bits + 2, as in zz_matmul
+        if max(Ud.shape[0], Wd.shape[0], ndc) > ZZ_MAX_DIGITS:
+            raise ValueError(f"lowrank_system: an operand or the result needs more than {ZZ_MAX_DIGITS} digits")
+        Cd, _ = _lowrank_system_planes(Ud, Wd, rp, col_a, col_b, ndc, device=device)
+        out = planes_to_ints(Cd)
+    else:
+        lowrank_system.last_info = [0, 0, 0, 0]
+    return out
+
+
+lowrank_system.last_info = None
+
+
+def _fraction_array(a, shape=None) -> np.ndarray:
+    """anything -> an object array of `Fraction`s (of the given shape)"""
+    src = np.asarray(a, dtype=object)
+    out = np.empty(src.shape, dtype=object)
+    out.flat = [Fraction(v) for v in src.flat]
+    return out if shape is None else out.reshape(shape)
+
+
+@dataclasses.dataclass
+class ExactLowRank:
+    """`sdp.LowRankMat` over QQ: sum_k lam[k] vs[k] ws[k]^T with `lam` (rank,), `vs`, `ws` (rank, delta) object arrays of `Fraction`s."""
+    lam: np.ndarray
+    vs: np.ndarray
+    ws: np.ndarray
+
+    def __post_init__(self):
+        self.lam, self.vs, self.ws = _fraction_array(self.lam).reshape(-1), _fraction_array(self.vs), _fraction_array(self.ws)
+        if self.vs.ndim != 2 or self.vs.shape != self.ws.shape or self.lam.shape[0] != self.vs.shape[0]:
+            raise ValueError("ExactLowRank should have the same number of values as vectors")
+
+    @property
+    def rank(self) -> int:
+        return self.lam.shape[0]
+
+    @property
+    def delta(self) -> int:
+        return self.vs.shape[1]
+
+
+@dataclasses.dataclass
+class ExactBlock:
+    """`sdp.Block` over QQ: `entries[(r, s)][p]` is an `ExactLowRank` or a dense (n, n) object array of `Fraction`s (then m == 1)."""
+    m: int
+    delta: int
+    entries: dict
+    name: object = None
+
+    @property
+    def n(self) -> int:
+        return self.m * self.delta
+
+    @property
+    def high_rank(self) -> bool:
+        return any(not isinstance(e, ExactLowRank) for d in self.entries.values() for e in d.values())
+
+
+@dataclasses.dataclass
+class ExactProblem:
+    """`sdp.ClusteredLowRankSDP` over QQ, the problem `exact_solution` rounds to: `blocks[j][l]` are `ExactBlock`s, `B[j]` (P_j, N), `c[j]` (P_j,), `C[j][l]`
+    (n, n) and `b` (N,) object arrays of `Fraction`s, `constant` a `Fraction`.  Constraint p of cluster j reads
+    `sum_l <A_l^p, Y_l> + (B[j] y)[p] = c[j][p]`, the objective `constant + sum <C[j][l], Y_l> + b . y`."""
+    maximize: bool
+    constant: Fraction
+    blocks: list
+    B: list
+    c: list
+    C: list
+    b: np.ndarray
+    names: dict = dataclasses.field(default_factory=dict)
+
+    def __post_init__(self):
+        self.constant = Fraction(self.constant)
+        self.b = _fraction_array(self.b).reshape(-1)
+        self.c = [_fraction_array(x).reshape(-1) for x in self.c]
+        self.B = [_fraction_array(x, (len(cj), self.b.size)) for x, cj in zip(self.B, self.c)]
+        self.C = [[_fraction_array(x) for x in cl] for cl in self.C]
+
+    def flat_blocks(self):
+        """[(cluster j, block)] in flat block order"""
+        return [(j, bl) for j, cl in enumerate(self.blocks) for bl in cl]
+
+    @property
+    def block_n(self) -> np.ndarray:
+        return np.array([bl.n for _, bl in self.flat_blocks()], dtype=np.int32)
+
+    def to_sdp(self, prec: int = 256):
+        """The numeric problem: every `Fraction` as the quotient of two mpmath integers at `prec` bits, in a `ClusteredLowRankSDP` of the same structure."""
+        import mpmath as mp
+        from .sdp import Block, ClusteredLowRankSDP, HiLo, LowRankMat
+
+        def num(a):
+            src = np.asarray(a, dtype=object)
+            if src.size == 0:
+                return np.zeros(src.shape)
+            out = np.empty(src.shape, dtype=object)
+            out.flat = [mp.mpf(v.numerator) / mp.mpf(v.denominator) for v in src.flat]
+            return out
+
+        with mp.workprec(int(prec)):
+            ent = lambda e: LowRankMat(num(e.lam), num(e.vs), num(e.ws)) if isinstance(e, ExactLowRank) else HiLo.of(num(e))
+            blocks = [[Block(bl.m, bl.delta, {rs: {p: ent(e) for p, e in d.items()} for rs, d in bl.entries.items()}, bl.name) for bl in cl] for cl in self.blocks]
+            return ClusteredLowRankSDP(bool(self.maximize), float(self.constant), blocks, [num(x) for x in self.B], [num(x) for x in self.c],
+                                       [[num(x) for x in cl] for cl in self.C], num(self.b), self.names)
+
+
+@dataclasses.dataclass
+class ExactSolution:
+    """What `exact_solution` returns: `Y` the blocks (object arrays of `Fraction`s; untransformed unless `transformed`), `y` the free variables, `objective`,
+    `correct_slacks` of the projection, `certificates` (one `PDCertificate` per block that kept a dimension), `Bs` of `basis_transformations`, and
+    `success = correct_slacks and every certificate positive`."""
+    success: bool
+    Y: list
+    y: list
+    objective: Fraction
+    correct_slacks: bool
+    certificates: list
+    Bs: dict
+
+
+def _kept_rows(problem, Bs):
+    """per block in flat order: (P, n') with P = Binv[s:, :] ((n', N) `Fraction`s; None: the identity)"""
+    out = []
+    for bi, (_, bl) in enumerate(problem.flat_blocks()):
+        if Bs is not None and bi in Bs:
+            _, Binv, s = Bs[bi]
+            P = _object_matrix(Binv, "linear_system", Fraction)[int(s):, :]
+            if P.shape[1] != bl.n:
+                raise ValueError(f"linear_system: the transformation of block {bi} has {P.shape[1]} columns for a block of size {bl.n}")
+            out.append((P, P.shape[0]))
+        else:
+            out.append((None, bl.n))
+    return out
+
+
+def system_index(problem, Bs=None) -> list:
+    """The columns of `linear_system`: `(block, a, b)`, a <= b row-major, block by block in flat order (blocks whose transformation keeps no dimension give
+    none), then `("free", k)`."""
+    index = [(bi, a, b) for bi, (_, nk) in enumerate(_kept_rows(problem, Bs)) for a in range(nk) for b in range(a, nk)]
+    return index + [("free", k) for k in range(problem.b.size)]
+
+
+def _lcm_of(values) -> int:
+    from math import gcd
+    l = 1
+    for v in values:
+        l = l * v.denominator // gcd(l, v.denominator)
+    return l
+
+
+def linear_system(problem, Bs=None, columns=None, assemble=None, matmul=None, device: int = 0):
+    """The reference's `linearsystem` / `partial_linearsystem` (src/interface.jl:1354-1535) over QQ for an `ExactProblem`: `(A, b, index)` with
+    `A x = b` the constraints in the variables x = (entries (a <= b) of the blocks, free variables).  Rows: cluster by cluster, constraint by constraint;
+    columns: `system_index(problem, Bs)`, or its entries `columns` (indices into it) in the given order; `b` the concatenated `c[j]`.  `A` is an object array
+    of `Fraction`s, `b` a list of `Fraction`s: what `project_to_affine_space(A, b)` takes as it is.  With `Bs` from `basis_transformations` (keys: flat block
+    indices) block l is transformed, `A_l -> P_l A_l P_l^T` with `P_l = Binv_l[s_l:, :]` (src/rounding.jl:1182-1196).
+
+    A low-rank block takes ONE call `assemble(U, W, rowptr, pairs, device=...)` (default `lowrank_system`, on the device): a term of sub-block (r, s) places
+    `lam v` at rows r delta ... and `w` at rows s delta ... of a column of length n; the columns of the terms of a constraint are multiplied by the least
+    common multiple of their denominators, P_l by that of its own, `U = P_l [lam v]`, `W = P_l [w]` as integer products (`matmul(A, B, device=...)`, e.g.
+    `zz_matmul`; default: Python integers), and entry (i, (a, b)) is `assemble`'s integer over the product of the four multipliers.  Clearing denominators is
+    host work of the size of the vectors; the quotient per entry is the only host work of the size of A.  The transposed partners `ClusteredLowRankSDP.check`
+    demands make the sum over the terms symmetric, which the factor 2 off the diagonal relies on.  Dense entries go through `transform`."""
+    assemble = lowrank_system if assemble is None else assemble
+    kept = _kept_rows(problem, Bs)
+    index = system_index(problem, Bs)
+    take = list(range(len(index))) if columns is None else [int(c) for c in columns]
+    if any(not 0 <= c < len(index) for c in take):
+        raise ValueError(f"linear_system: a column outside [0, {len(index)})")
+    where = {}
+    for pos, c in enumerate(take):
+        where.setdefault(c, []).append(pos)
+    sizes = [len(cj) for cj in problem.c]
+    row0 = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    A = np.empty((int(row0[-1]), len(take)), dtype=object)
+    A.fill(Fraction(0))
+    first = {}                                               # block -> its first column in `index`
+    for ci, e in enumerate(index):
+        first.setdefault(e[0], ci)
+    for bi, (j, bl) in enumerate(problem.flat_blocks()):
+        P, nk = kept[bi]
+        cols = [(a, b) for a in range(nk) for b in range(a, nk)]
+        sel = [(t, ab) for t, ab in enumerate(cols) if first.get(bi, 0) + t in where] if nk else []
+        if not sel:
+            continue
+        Pj, n, delta = sizes[j], bl.n, bl.delta
+        if bl.high_rank:
+            for p, M in bl.entries.get((0, 0), {}).items():
+                Mt = _object_matrix(M, "linear_system", Fraction) if P is None else transform(M, Bs[bi][1], Bs[bi][2], matmul=matmul, device=device)
+                for t, (a, b) in sel:
+                    v = Mt[a, b] if a == b else Mt[a, b] + Mt[b, a]
+                    for pos in where[first[bi] + t]:
+                        A[row0[j] + p, pos] = v
+            continue
+        terms = [[] for _ in range(Pj)]                         # per constraint: (r, s, lam, v, w) in the order of `flatten`
+        for (r, s), d in bl.entries.items():
+            for p, e in d.items():
+                for k in range(e.rank):
+                    terms[p].append((r, s, k, e))
+        rowptr, Vc, Wc, mult = [0], [], [], []
+        for p in range(Pj):
+            terms[p].sort(key=lambda t: t[:3])
+            vcols, wcols = [], []
+            for r, s, k, e in terms[p]:
+                v, w = [Fraction(0)] * n, [Fraction(0)] * n
+                v[r * delta:(r + 1) * delta] = [e.lam[k] * x for x in e.vs[k]]
+                w[s * delta:(s + 1) * delta] = list(e.ws[k])
+                vcols.append(v); wcols.append(w)
+            lv, lw = _lcm_of(x for col in vcols for x in col), _lcm_of(x for col in wcols for x in col)
+            Vc += [[int(x * lv) for x in col] for col in vcols]
+            Wc += [[int(x * lw) for x in col] for col in wcols]
+            mult.append(lv * lw)
+            rowptr.append(len(Vc))
+        T = len(Vc)
+        Vi = np.array(Vc, dtype=object).reshape(T, n).T         # (n, T) integers
+        Wi = np.array(Wc, dtype=object).reshape(T, n).T
+        lp = 1
+        if P is not None and T:
+            Pn, lp = _common_denominator(P.flat)
+            Pn = Pn.reshape(P.shape)
+            Vi = _matmul_matrix(matmul, Pn, Vi, device) if matmul is not None else Pn.dot(Vi)
+            Wi = _matmul_matrix(matmul, Pn, Wi, device) if matmul is not None else Pn.dot(Wi)
+        G = np.asarray(assemble(Vi, Wi, rowptr, [ab for _, ab in sel], device=device), dtype=object)
+        if G.shape != (Pj, len(sel)):
+            raise ArithmeticError(f"linear_system: assemble returned shape {G.shape} for {Pj} rows and {len(sel)} columns")
+        for p in range(Pj):
+            den = lp * lp * mult[p]
+            for q, (t, _) in enumerate(sel):
+                g = int(G[p, q])
+                if g:
+                    v = Fraction(g, den)
+                    for pos in where[first[bi] + t]:
+                        A[row0[j] + p, pos] = v
+    nY = len(index) - problem.b.size
+    for k in range(problem.b.size):
+        for pos in where.get(nY + k, ()):
+            for j in range(len(sizes)):
+                A[row0[j]:row0[j + 1], pos] = problem.B[j][:, k]
+    b = [Fraction(v) for cj in problem.c for v in cj]
+    return A, b, [index[c] for c in take]
+
+
+def _objective_marks(problem, Bs, matmul, device):
+    """per column of `system_index(problem, Bs)`: does the (transformed) objective touch it?"""
+    marks = []
+    for bi, ((j, bl), (P, nk)) in enumerate(zip(problem.flat_blocks(), _kept_rows(problem, Bs))):
+        if not nk:
+            continue
+        l = bi - sum(len(cl) for cl in problem.blocks[:j])
+        Ct = problem.C[j][l] if P is None else transform(problem.C[j][l], Bs[bi][1], Bs[bi][2], matmul=matmul, device=device)
+        marks += [Ct[a, b] != 0 or Ct[b, a] != 0 for a in range(nk) for b in range(a, nk)]
+    return marks + [v != 0 for v in problem.b]
+
+
+def select_columns(problem_or_index, redundancyfactor: int = 10, rng=None, nconstraints: Optional[int] = None, objective=None, Bs=None) -> list:
+    """The reference's `select_columns` (src/rounding.jl:95-153): the columns of the system the projection works with.  `problem_or_index`: an `ExactProblem`
+    (its index with `Bs`, its number of constraints and its objective are used) or the index of `linear_system` with `nconstraints` and, optionally,
+    `objective` (per column: is it in the objective?).  Entries on the diagonal and next to it get the mark 1, columns of the objective +2.  A negative
+    factor takes all columns.  Otherwise, with K = redundancyfactor * nconstraints: the columns marked >= 2 and then those marked 1 -- or, when they are more
+    than K, a random K of them (`rng.permutation`, where the reference shuffles), those of the objective first -- followed by
+    `max((redundancyfactor - 2) * nconstraints, K - taken)` unmarked columns at random.  `rng`: a `numpy.random.Generator` (default `default_rng(0)`).
+    0-based indices."""
+    rng = np.random.default_rng(0) if rng is None else rng
+    if isinstance(problem_or_index, ExactProblem):
+        index = system_index(problem_or_index, Bs)
+        nconstraints = sum(len(cj) for cj in problem_or_index.c) if nconstraints is None else nconstraints
+        objective = _objective_marks(problem_or_index, Bs, None, 0) if objective is None else objective
+    else:
+        index = list(problem_or_index)
+        if nconstraints is None:
+            raise ValueError("select_columns: an index needs nconstraints")
+    redundancyfactor, nconstraints = int(redundancyfactor), int(nconstraints)
+    if redundancyfactor < 0:
+        return list(range(len(index)))
+    objective = [False] * len(index) if objective is None else [bool(v) for v in objective]
+    if len(objective) != len(index):
+        raise ValueError(f"select_columns: objective has {len(objective)} entries for {len(index)} columns")
+    marks = [(1 if e[0] != "free" and e[2] - e[1] <= 1 else 0) + (2 if o else 0) for e, o in zip(index, objective)]
+    obj_cols = [i for i, v in enumerate(marks) if v >= 2]
+    chosen = [i for i, v in enumerate(marks) if v == 1]
+    K = redundancyfactor * nconstraints
+    if len(obj_cols) + len(chosen) > K:
+        both = obj_cols + chosen
+        cut = [both[t] for t in rng.permutation(len(both))][:K]
+        in_obj = set(obj_cols)
+        pivot_cols = list(dict.fromkeys([i for i in cut if i in in_obj] + cut))
+    else:
+        pivot_cols = obj_cols + chosen
+    needed = max((redundancyfactor - 2) * nconstraints, K - len(pivot_cols), 0)
+    rest = [i for i, v in enumerate(marks) if v == 0]
+    rest = [rest[t] for t in rng.permutation(len(rest))]
+    return pivot_cols + rest[:min(needed, len(rest))]
+
+
+def vectorize_solution(Yt, y, index) -> list:
+    """the vector x of `linear_system` for the blocks `Yt` (a list in flat block order, or a dict by block) and the free variables `y`"""
+    return [Fraction(y[e[1]]) if e[0] == "free" else Fraction(Yt[e[0]][e[1], e[2]]) for e in index]
+
+
+def get_rational_system(problem, Yt, y, Bs=None, columns=None, settings: Optional[RoundingSettings] = None, assemble=None, matmul=None, device: int = 0):
+    """The reference's `get_rational_system` over QQ (src/rounding.jl:1284-1296): `(A_cols, rhs, x_rounded, columns)`.  x = the entries (a <= b) of the
+    transformed blocks `Yt` and the free variables `y` (exact rationals) in the order of `system_index(problem, Bs)`;
+    `x_rounded = floor(x 10^dec) / 10^dec` entry by entry with `dec = settings.approximation_decimals` (`roundx`, src/rounding.jl:515-517);
+    `rhs = b - A x_rounded` over ALL columns of the transformed system (with `matmul`: one integer product of the rows cleared of denominators), and
+    `A_cols` its columns `columns` (default: all).  The full triangle is assembled once (`linear_system`)."""
+    settings = RoundingSettings() if settings is None else settings
+    A, b, index = linear_system(problem, Bs=Bs, assemble=assemble, matmul=matmul, device=device)
+    scale = 10 ** int(settings.approximation_decimals)
+    x_rounded = [Fraction((v * scale).__floor__(), scale) for v in vectorize_solution(Yt, y, index)]
+    nrows, ncols = A.shape
+    if matmul is not None and nrows and ncols:
+        cleared = [_common_denominator(list(A[i])) for i in range(nrows)]
+        Ai = np.array([list(cl[0]) for cl in cleared], dtype=object).reshape(nrows, ncols)
+        xv, L = _common_denominator(x_rounded)
+        rhs = [b[i] - Fraction(v, L * cleared[i][1]) for i, v in enumerate(_matmul_vector(matmul, Ai, xv, device))]
+    else:
+        rhs = [b[i] - sum((A[i, c] * x_rounded[c] for c in range(ncols) if A[i, c] != 0), Fraction(0)) for i in range(nrows)]
+    columns = list(range(ncols)) if columns is None else [int(c) for c in columns]
+    return A[:, columns], rhs, x_rounded, columns
+
+
+def _exact_blocks(result_Y, block_n, limbs=None):
+    """the blocks of a solution (fp64 (len,) or planar limbs (planes, len), column-major per block) as symmetric matrices of exact dyadic `Fraction`s"""
+    a = np.asarray(result_Y, dtype=np.float64)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    if limbs is not None:
+        a = a[:int(limbs)]
+    off = np.concatenate([[0], np.cumsum(np.asarray(block_n, dtype=np.int64) ** 2)])
+    if a.shape[1] != off[-1]:
+        raise ValueError(f"exact_solution: the solution holds {a.shape[1]} numbers per plane for blocks of {int(off[-1])} entries")
+    out = []
+    for bi, n in enumerate(int(v) for v in block_n):
+        vals = [sum((Fraction(float(a[l, o])) for l in range(a.shape[0]) if a[l, o] != 0.0), Fraction(0)) for o in range(off[bi], off[bi + 1])]
+        M = np.array(vals, dtype=object).reshape(n, n).T if n else np.zeros((0, 0), dtype=object)
+        out.append(_object_matrix((M + M.T) / 2 if n else M, "exact_solution", Fraction))
+    return out
+
+
+def _lift_by_columns(lift):
+    """the `lift` hook of `solve_dixon` (one right-hand side) as the `lift` hook of `solve_dixon_multi`: column by column"""
+    def multi(A, B, p, steps, device=0):
+        B = np.asarray(B, dtype=object)
+        cols = [lift(A, B[:, j], p, steps, device=device) for j in range(B.shape[1])]
+        if cols[0][0] is None:
+            return None, None, cols[0][2]
+        R = np.zeros(B.shape, dtype=object)
+        for j, c in enumerate(cols):
+            R[:, j] = [int(v) for v in c[1]]
+        return np.ascontiguousarray(np.stack([np.asarray(c[0]) for c in cols], axis=2)), R, cols[0][2]
+    return multi
+
+
+def exact_solution(problem, result, settings: Optional[RoundingSettings] = None, limbs: Optional[int] = None, transformed: bool = False, rng=None,
+                   device: int = 0, batch=None, lift=None, reconstruct=None, matmul=None, minors=None, round_batch=None, assemble=None) -> ExactSolution:
+    """The reference's `exact_solution` over QQ (src/rounding.jl:1366-1409, 155-179) for an `ExactProblem` and a numeric solution `result` of
+    `problem.to_sdp(...)` (a `SolveResult` of `solvesdp_mw`, or anything with `X`, `Y` (fp64 or planar limbs) and `y`):
+
+      1. `kernel_vectors(..., rationalize=True)`;  2. `basis_transformations`;  3. the blocks Y as the exact dyadic rationals their limbs sum to,
+      `Yt = B^T[s:, :] Y B[:, s:]`;  4. the loop of the reference's `project_to_affine_space(problem, sol)`: `select_columns` with
+      `settings.redundancyfactor + extra`, `get_rational_system`, `project_to_affine_space(A, b)`; an inconsistent system takes `extra += 2`, and is an
+      `ArithmeticError` when all columns were already taken;  5. the positive-definiteness part of `is_valid_solution(..., check_slacks=False)`: `checkpd`
+      of every transformed block, the certificates kept;  6. `undo_transform`, unless `transformed`.
+
+    With the default `settings.reduce_kernelvectors` `basis_transformations` raises its `NotImplementedError`, which passes through.  The hooks replace the
+    device calls of the steps: `round_batch` (`kernel_vectors`), `batch` (`rref_mod_p`), `lift` (the one-column hook of `solve_dixon`; the inverse of
+    `basis_transformations` then takes it column by column), `reconstruct`, `matmul`, `minors` (`checkpd`), `assemble` (`linear_system`).  `rng`: the generator of `select_columns` and `project_to_affine_space`."""
+    settings = RoundingSettings() if settings is None else settings
+    rng = np.random.default_rng(0) if rng is None else rng
+    block_n = problem.block_n
+    kernels = kernel_vectors(block_n, result, result, limbs=limbs, settings=settings, device=device, rationalize=True, round_batch=round_batch)
+    Bs = basis_transformations({bi: (int(n), vectors_to_fractions(k)) for bi, (n, k) in enumerate(zip(block_n, kernels))}, settings, device=device, batch=batch,
+                               lift=None if lift is None else _lift_by_columns(lift), reconstruct=reconstruct, matmul=matmul)
+    Y = _exact_blocks(result.Y, block_n, limbs)
+    y = [sum((Fraction(float(v)) for v in np.atleast_2d(np.asarray(getattr(result, "y", np.zeros(0)), dtype=np.float64))[:, k]), Fraction(0))
+         for k in range(problem.b.size)]
+    Yt = {bi: transform(Y[bi], Bs[bi][0], Bs[bi][2], matmul=matmul, device=device) for bi in Bs}
+    index = system_index(problem, Bs)
+    nconstraints = sum(len(cj) for cj in problem.c)
+    objective = _objective_marks(problem, Bs, matmul, device)
+    extra = 0
+    while True:
+        columns = select_columns(index, settings.redundancyfactor + extra, rng, nconstraints=nconstraints, objective=objective)
+        A, rhs, x, columns = get_rational_system(problem, Yt, y, Bs, columns, settings, assemble=assemble, matmul=matmul, device=device)
+        x_extra, correct_slacks, finished = project_to_affine_space(A, rhs, settings=settings, rng=rng, device=device, batch=batch, lift=lift,
+                                                                    reconstruct=reconstruct, matmul=matmul)
+        if finished:
+            break
+        if len(columns) >= len(index):
+            raise ArithmeticError("exact_solution: the system is inconsistent but all columns were taken")
+        extra += 2
+    for pos, c in enumerate(columns):
+        x[c] += x_extra[pos]
+    sol_t, free = {}, [Fraction(0)] * problem.b.size
+    for bi, (_, _, s) in Bs.items():
+        nk = int(block_n[bi]) - int(s)
+        sol_t[bi] = _object_matrix(np.zeros((nk, nk), dtype=object), "exact_solution", Fraction)
+    for e, v in zip(index, x):
+        if e[0] == "free":
+            free[e[1]] = v
+        else:
+            sol_t[e[0]][e[1], e[2]] = sol_t[e[0]][e[2], e[1]] = v
+    certificates = [checkpd(sol_t[bi], device=device, minors=minors) for bi in sol_t if sol_t[bi].shape[0]]
+    success = bool(correct_slacks) and all(cert.pd for cert in certificates)
+    full = [undo_transform(sol_t[bi], Bs[bi][1], Bs[bi][2], matmul=matmul, device=device) for bi in sorted(sol_t)]
+    objective_value = problem.constant + sum((v * free[k] for k, v in enumerate(problem.b)), Fraction(0))
+    for (j, l), M in zip(((j, l) for j, cl in enumerate(problem.blocks) for l in range(len(cl))), full):
+        objective_value += sum((problem.C[j][l][a, b] * M[a, b] for a in range(M.shape[0]) for b in range(M.shape[0]) if M[a, b] != 0), Fraction(0))
+    return ExactSolution(success, [sol_t[bi] for bi in sorted(sol_t)] if transformed else full, free, objective_value, bool(correct_slacks), certificates, Bs)

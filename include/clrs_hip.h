@@ -453,7 +453,22 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   n == 0 or m == 0: nothing to lift, info = [0, steps, 0, 0, 0, 0] without touching a device (the rank of A is then not examined).  Every device buffer is
  *   released on every path.
  * clrs_modp_dixon_lift_multi_times: the milliseconds of the calling thread's last clrs_modp_dixon_lift_multi: in k_liftm_x, in k_zz_gemm and in k_liftm_r
- *   over all steps and chunks, and from the first upload to the last download (device events). */
+ *   over all steps and chunks, and from the first upload to the last download (device events).
+ * clrs_zz_lowrank_system: the rows of the rational linear system of the rounding chain from low-rank constraint matrices (the
+ *   reference's partial_linearsystem, src/interface.jl:1354-1535, cleared of denominators), host pointers, no context.  U is [ndu][n][T], W [ndw][n][T]: one
+ *   column per low-rank term, row-major planes of balanced base-2^24 digits, little-endian, digits in [-2^23, 2^23]; row i of the system owns the terms
+ *   rowptr[i] .. rowptr[i + 1] - 1 (rowptr has R + 1 entries, non-decreasing, from 0 to T); column c is the pair (col_a[c], col_b[c]), 0 <= a <= b < n.
+ *   C [ndc][R][nc] receives C[i, c] = 2^(a != b) sum_t U[a, t] W[b, t] in the unique digits of clrs_zz_gemm.  The digit index lies in the k-extent of the
+ *   fp64 MFMA (k_lrsys_tile: one workgroup per row and 16 x 16 tile of pairs that holds a selected column), int64 digit sums, one carry walk per entry.  info[0]:
+ *   entries that do not fit in ndc digits: non-zero gives CLRS_ERR_INVALID and leaves C untouched; info[1]: chunks of rows (the sums of a chunk,
+ *   8 (ndu + ndw - 1) nc bytes per row, stay below 256 MiB, or below clrs_config_set("lrsys_chunk_bytes", b); never less than one row per chunk; the result
+ *   does not depend on the chunks); info[2]: tile workgroups launched; info[3]: impossibilities as in clrs_zz_gemm: non-zero gives CLRS_ERR_HIP and leaves C
+ *   untouched.  CLRS_ERR_INVALID before any device call, C untouched: a negative size, ndu, ndw or ndc outside [1, 32767], U, W, C, n^2 or
+ *   (ndu + ndw - 1) nc of 2^31 elements or more, a null pointer (rowptr and info are always needed), a rowptr that does not start at 0, end at T or that
+ *   decreases, (most terms of a row) min(ndu, ndw) >= 2^14, a pair with a > b or an index outside [0, n), a digit outside [-2^23, 2^23].  R, nc or T equal to
+ *   0 gives zeros without touching a device; a row without terms is a row of zeros.  Every device buffer is released on every path.
+ * clrs_zz_lowrank_system_times: the milliseconds of the calling thread's last clrs_zz_lowrank_system: in k_lrsys_tile, in k_lrsys_carry, and from the first
+ *   upload to the last download (device events). */
 #define CLRS_MODP_MINORS_MAX_N 128
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
@@ -486,6 +501,9 @@ int clrs_zz_gemm_times(double *gemm_ms, double *combine_ms, double *whole_ms);
 int clrs_modp_dixon_lift_multi(int device, int n, int m, int p, int nd, const int32_t *A_digits, int nbl, const int32_t *B_limbs, int steps, int32_t *X,
                                int32_t *R_limbs, int32_t *info);
 int clrs_modp_dixon_lift_multi_times(double *x_ms, double *gemm_ms, double *r_ms, double *whole_ms);
+int clrs_zz_lowrank_system(int device, int n, int T, int R, const int32_t *rowptr, int ndu, const int32_t *U, int ndw, const int32_t *W, int nc,
+                           const int32_t *col_a, const int32_t *col_b, int ndc, int32_t *C, int32_t *info);
+int clrs_zz_lowrank_system_times(double *tile_ms, double *carry_ms, double *whole_ms);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 
