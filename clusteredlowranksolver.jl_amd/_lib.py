@@ -220,6 +220,8 @@ SYMBOLS = {
     "clrs_test_potrf": (C.c_int, [C.c_int, C.c_int, p_d, C.c_int]),
     "clrs_test_trsm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_d, C.c_int, p_d, C.c_int]),
     "clrs_test_stream": (C.c_int, [C.c_int, C.c_longlong, C.c_longlong, C.c_int, p_d]),
+    "clrs_test_min_eig": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_d, p_d]),
+    "clrs_mw_test_step_eig": (C.c_int, [C.c_void_p, p_d, p_d, p_d, p_d, p_d, p_i32]),
 }
 
 

@@ -1575,3 +1575,33 @@ extern "C" int clrs_test_trsm(int device, int trans, int n, int nrhs, const doub
     }
     return rc;
 }
+
+// ---- the three fp64 smallest-eigenvalue routines of the step length on matrices given to them ---------------------------------
+// A: `count` symmetric n x n matrices, column-major, both triangles, back to back; out[count]: their smallest eigenvalues.  One launch, one workgroup per
+// matrix.  form 0: wg_min_eig32 (2 <= n <= 64) and form 1: wg_min_eig (1 <= n <= 128), the routines of k_mwi_step (clrs_mw_ipm.hip.h); form 2:
+// ipm_min_eig, the second half of k_ipm_step (2 <= n <= 64).  Domain: entries of magnitude above about 2^-500 or zero -- below, the squares in x^T x
+// underflow and the Householder vectors lose their accuracy; the iteration never sees such matrices (W = L^-1 dM L^-T of iterates of ordinary size).
+int mw_test_min_eig_launch(int form, int n, int count, const double *dA, double *dOut);      // clrs_mw.hip (host side: clrs_mw_ipm_host.inc)
+extern "C" int clrs_test_min_eig(int device, int form, int n, int count, const double *A, double *out) {
+    if (!A || !out || count < 1) return fail(CLRS_ERR_INVALID, "clrs_test_min_eig: bad arguments");
+    if (form < 0 || form > 2) return fail(CLRS_ERR_INVALID, "clrs_test_min_eig: form is 0 (wg_min_eig32), 1 (wg_min_eig) or 2 (the fp64 loop's routine)");
+    if (form == 1 ? (n < 1 || n > 128) : (n < 2 || n > 64))
+        return fail(CLRS_ERR_INVALID, form == 1 ? "clrs_test_min_eig: form 1 takes 1 <= n <= 128" : "clrs_test_min_eig: forms 0 and 2 take 2 <= n <= 64");
+    if (hipSetDevice(device) != hipSuccess) return fail(CLRS_ERR_NO_DEVICE, "no device");
+    const size_t bytes = sizeof(double) * (size_t)n * n * count;
+    double *dA = nullptr, *dOut = nullptr;
+    int rc = 0;
+    auto ok = [&](hipError_t e, const char *what) { if (e != hipSuccess && !rc) rc = fail(CLRS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); return e == hipSuccess; };
+    if (ok(hipMalloc(&dA, bytes), "hipMalloc") && ok(hipMalloc(&dOut, sizeof(double) * count), "hipMalloc") &&
+        ok(hipMemcpy(dA, A, bytes, hipMemcpyHostToDevice), "hipMemcpy") && ok(hipMemset(dOut, 0, sizeof(double) * count), "hipMemset")) {
+        if (form == 2) {
+            const int n16 = (n + 15) & ~15, lda = n16 + 2;
+            hipLaunchKernelGGL(k_ipm_test_min_eig, dim3(count), dim3(256), sizeof(double) * (size_t)(lda * (n16 + 8) + 2 * n16 + 144), nullptr, dA, dOut, n);
+            ok(hipGetLastError(), "k_ipm_test_min_eig");
+        } else rc = mw_test_min_eig_launch(form, n, count, dA, dOut);
+        if (!rc && ok(hipDeviceSynchronize(), "hipDeviceSynchronize")) ok(hipMemcpy(out, dOut, sizeof(double) * count, hipMemcpyDeviceToHost), "hipMemcpy");
+    }
+    if (dA) (void)hipFree(dA);
+    if (dOut) (void)hipFree(dOut);
+    return rc;
+}

@@ -85,8 +85,20 @@ struct IpmBuf {
             q.eig[2 * q.NB + (i)] = (double)t_;                                                                 \
         }                                                                                                       \
     } while (0)
+// the same inside a device function the kernel calls: the kernel hands over where its stamps go (null: none)
+#define IPM_STAMPS_OF(q) (blockIdx.x == 0 ? (q).eig + 2 * (q).NB : (double *)nullptr)
+#define IPM_STAMP_AT(stamps, i)                                                                                 \
+    do {                                                                                                        \
+        if ((stamps) && threadIdx.x == 0) {                                                                     \
+            unsigned long long t_;                                                                              \
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                          \
+            (stamps)[i] = (double)t_;                                                                           \
+        }                                                                                                       \
+    } while (0)
 #else
 #define IPM_STAMP(i) do {} while (0)
+#define IPM_STAMPS_OF(q) ((double *)nullptr)
+#define IPM_STAMP_AT(stamps, i) do {} while (0)
 #endif
 
 __device__ __forceinline__ double block_reduce_sum(double v, double *red) {   // 256 threads, deterministic tree
@@ -662,57 +674,12 @@ __device__ __forceinline__ void ipm_householder_regs(const double *Ws, int lda, 
     if (lane == 0) ee[n - 2] = ev;
 }
 
-// ---- k_ipm_step: smallest eigenvalue of L^-1 dM L^-T, M in {X, Y} ---------------------------------------------------------------
-// grid = 2 NB: workgroup 2b handles (X, dX), 2b+1 handles (Y, dY).  Cholesky of M, two triangular solves, Householder
-// tridiagonalisation in LDS, Sturm-count multisection with one shift per thread (256-section per round).
-__global__ __launch_bounds__(256) void k_ipm_step(const IpmBuf q) {
-    extern __shared__ __attribute__((aligned(16))) double lds[];
-    __shared__ double red[4];
-    __shared__ int zc[2][4];
-    const int b = blockIdx.x >> 1, which = blockIdx.x & 1;
-    const IBlock k = q.blocks[b];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = k.n, n16 = (n + 15) & ~15, lda = n16 + 2;
-    // Ws carries 8 extra zero columns and vv / pp are 72 long: the Householder loops run in unguarded chunks of 8
-    double *Ls = lds, *Ws = Ls + lda * n16, *dinv = Ws + lda * (n16 + 8), *dd = dinv + n16, *ee = dd + n16, *vv = ee + n16, *pp = vv + 72;
-    const double *Mg = (which ? q.Y : q.X) + k.xyoff, *dMg = (which ? q.dY : q.dX) + k.xyoff;
-    const int i16 = tid & 15, j16 = tid >> 4;
-    if (n == 1) {
-        if (tid == 0) q.eig[b * 2 + which] = dMg[0] / Mg[0];
-        return;
-    }
-    IPM_STAMP(0);
-    // L = chol(M)
-    for (int j0 = 0; j0 < n16; j0 += 16)
-        for (int i0 = 0; i0 < n16; i0 += 16) {
-            const int i = i0 + i16, j = j0 + j16;
-            Ls[i + j * lda] = (i < n && j < n) ? ((i >= j) ? Mg[i + (long long)j * n] : 0.0) : ((i == j) ? 1.0 : 0.0);
-        }
-    ipm_load(Ws, lda, dMg, n, n16, tid);
-    for (int e = tid; e < 8 * lda; e += 256) Ws[n16 * lda + e] = 0.0;
-    __syncthreads();
-    IPM_STAMP(1);
-    const bool bad = lds_potrf(Ls, lda, dinv, n, wave, 4, lane);
-    if (bad && lane == 0) atomicMin(q.info + 1, 1000000 + b);          // Cholesky failed in the step length computation
-    __syncthreads();
-    IPM_STAMP(2);
-    // W = L^-1 dM L^-T: solve on the columns, then on the rows
-    lds_trsm<false>(Ls, lda, dinv, Ws, 1, lda, n, n, wave, 4, lane);
-    __syncthreads();
-    lds_trsm<false>(Ls, lda, dinv, Ws, lda, 1, n, n, wave, 4, lane);
-    __syncthreads();
-    IPM_STAMP(3);
-    // symmetrise
-    for (int j0 = 0; j0 < n; j0 += 16)
-        for (int i0 = 0; i0 < n; i0 += 16) {
-            const int i = i0 + i16, j = j0 + j16;
-            if (i < n && j < n && i > j) {
-                const double v = 0.5 * (Ws[i + j * lda] + Ws[j + i * lda]);
-                Ws[i + j * lda] = v;
-                Ws[j + i * lda] = v;
-            }
-        }
-    __syncthreads();
-    IPM_STAMP(4);
+// Smallest eigenvalue of the symmetric n x n matrix in Ws (LDS, both triangles, leading dimension lda, 2 <= n <= 64; destroyed), by the 256 threads of
+// the workgroup: the second half of k_ipm_step, a function of its own so that clrs_test_min_eig (form 2) runs the same code on matrices given to it.
+// Ws carries 8 zero columns behind column n16 - 1 (n16 = n rounded up to 16, lda >= n16 even); dd, ee: n16 doubles each; vv, pp: 72 each; red: 4; zc: 2 x 4.
+// The same value in every thread.  (stamps: diagnostic builds, else unused.)
+__device__ __forceinline__ double ipm_min_eig(double *Ws, int lda, int n, double *dd, double *ee, double *vv, double *pp, double *red, int (*zc)[4], double *stamps) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     // Householder tridiagonalisation inside ONE wave (n <= 64): lane i owns row c+1+i of the trailing matrix, the vector v and
     // w go through LDS as broadcasts, the norms and dot products through wave butterflies -- no workgroup barriers in the
     // n-2 dependent steps.  Both triangles of the trailing matrix are kept.
@@ -771,7 +738,7 @@ __global__ __launch_bounds__(256) void k_ipm_step(const IpmBuf q) {
         }
     }
     __syncthreads();
-    IPM_STAMP(5);
+    IPM_STAMP_AT(stamps, 5);
     if (!in_regs) {
         if (tid < n) dd[tid] = Ws[tid + tid * lda];
         if (tid == 0) ee[n - 2] = Ws[(n - 1) + (n - 2) * lda];
@@ -852,8 +819,81 @@ __global__ __launch_bounds__(256) void k_ipm_step(const IpmBuf q) {
     }
     lo = ldexp(lo, sexp);
     hi = ldexp(hi, sexp);
+    return 0.5 * (lo + hi);
+}
+
+// ---- k_ipm_step: smallest eigenvalue of L^-1 dM L^-T, M in {X, Y} ---------------------------------------------------------------
+// grid = 2 NB: workgroup 2b handles (X, dX), 2b+1 handles (Y, dY).  Cholesky of M, two triangular solves, Householder
+// tridiagonalisation in LDS, Sturm-count multisection with one shift per thread (256-section per round).
+__global__ __launch_bounds__(256) void k_ipm_step(const IpmBuf q) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ double red[4];
+    __shared__ int zc[2][4];
+    const int b = blockIdx.x >> 1, which = blockIdx.x & 1;
+    const IBlock k = q.blocks[b];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = k.n, n16 = (n + 15) & ~15, lda = n16 + 2;
+    // Ws carries 8 extra zero columns and vv / pp are 72 long: the Householder loops run in unguarded chunks of 8
+    double *Ls = lds, *Ws = Ls + lda * n16, *dinv = Ws + lda * (n16 + 8), *dd = dinv + n16, *ee = dd + n16, *vv = ee + n16, *pp = vv + 72;
+    const double *Mg = (which ? q.Y : q.X) + k.xyoff, *dMg = (which ? q.dY : q.dX) + k.xyoff;
+    const int i16 = tid & 15, j16 = tid >> 4;
+    if (n == 1) {
+        if (tid == 0) q.eig[b * 2 + which] = dMg[0] / Mg[0];
+        return;
+    }
+    IPM_STAMP(0);
+    // L = chol(M)
+    for (int j0 = 0; j0 < n16; j0 += 16)
+        for (int i0 = 0; i0 < n16; i0 += 16) {
+            const int i = i0 + i16, j = j0 + j16;
+            Ls[i + j * lda] = (i < n && j < n) ? ((i >= j) ? Mg[i + (long long)j * n] : 0.0) : ((i == j) ? 1.0 : 0.0);
+        }
+    ipm_load(Ws, lda, dMg, n, n16, tid);
+    for (int e = tid; e < 8 * lda; e += 256) Ws[n16 * lda + e] = 0.0;
+    __syncthreads();
+    IPM_STAMP(1);
+    const bool bad = lds_potrf(Ls, lda, dinv, n, wave, 4, lane);
+    if (bad && lane == 0) atomicMin(q.info + 1, 1000000 + b);          // Cholesky failed in the step length computation
+    __syncthreads();
+    IPM_STAMP(2);
+    // W = L^-1 dM L^-T: solve on the columns, then on the rows
+    lds_trsm<false>(Ls, lda, dinv, Ws, 1, lda, n, n, wave, 4, lane);
+    __syncthreads();
+    lds_trsm<false>(Ls, lda, dinv, Ws, lda, 1, n, n, wave, 4, lane);
+    __syncthreads();
+    IPM_STAMP(3);
+    // symmetrise
+    for (int j0 = 0; j0 < n; j0 += 16)
+        for (int i0 = 0; i0 < n; i0 += 16) {
+            const int i = i0 + i16, j = j0 + j16;
+            if (i < n && j < n && i > j) {
+                const double v = 0.5 * (Ws[i + j * lda] + Ws[j + i * lda]);
+                Ws[i + j * lda] = v;
+                Ws[j + i * lda] = v;
+            }
+        }
+    __syncthreads();
+    IPM_STAMP(4);
+    const double ev = ipm_min_eig(Ws, lda, n, dd, ee, vv, pp, red, zc, IPM_STAMPS_OF(q));
     IPM_STAMP(6);
-    if (tid == 0) q.eig[b * 2 + which] = 0.5 * (lo + hi);
+    if (tid == 0) q.eig[b * 2 + which] = ev;
+}
+
+// test hook (clrs_test_min_eig, form 2): workgroup b runs ipm_min_eig on the b-th of the symmetric n x n matrices in A (column-major, both triangles,
+// back to back), staged in LDS exactly as k_ipm_step leaves its W: leading dimension n16 + 2, zero padded to n16 rows and n16 + 8 columns.
+__global__ __launch_bounds__(256) void k_ipm_test_min_eig(const double *A, double *out, int n) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    __shared__ double red[4];
+    __shared__ int zc[2][4];
+    const int tid = threadIdx.x, n16 = (n + 15) & ~15, lda = n16 + 2;
+    double *Ws = lds, *dd = Ws + lda * (n16 + 8), *ee = dd + n16, *vv = ee + n16, *pp = vv + 72;
+    const double *Ag = A + (long long)blockIdx.x * n * n;
+    for (int e = tid; e < lda * (n16 + 8); e += 256) {
+        const int i = e % lda, j = e / lda;
+        Ws[e] = (i < n && j < n) ? Ag[i + (long long)j * n] : 0.0;
+    }
+    __syncthreads();
+    const double ev = ipm_min_eig(Ws, lda, n, dd, ee, vv, pp, red, zc, nullptr);
+    if (tid == 0) out[blockIdx.x] = ev;
 }
 
 // ---- k_ipm_update: iterate update + objective / complementarity dots ------------------------------------------------------

@@ -422,6 +422,24 @@ static int mw_ipm_tail(clrs_mw_ctx *c, int word_value = 0, bool with_next = fals
     st->tail_pending = false;
     return 0;
 }
+// both step lengths in one launch (after the Cholesky launch of this iteration: the inverse factors of X, and of Y where they ride along); with every
+// inverse factor in memory the congruences are split over column panels (zs workgroups each).  Enqueue only; the caller checks hipGetLastError.
+static int mw_ipm_launch_step(clrs_mw_ctx *c, hipStream_t M) {
+    const MwDev &q = c->d;
+    MwIpm *st = c->ipm;
+    const MwIpmDev &p = st->d;
+    const int ip = st->y_with_x ? 2 : st->step_inv ? 1 : 0, wl = st->step_w_lds ? 1 : 0;
+    if (ip == 2 && st->z_tiled) {                         // large blocks: the two products of each congruence as tiled launches, then the eigenvalues
+        const int nt = ((int)st->maxn_inv + MWI_BT - 1) / MWI_BT;
+        MW_DISPATCH(c, {
+            hipLaunchKernelGGL(k_mwi_bmm<KK>, dim3(nt * nt, q.NB, 2), dim3(MW_NT), st->sm_bmm, M, q, p, 4, 0);
+            hipLaunchKernelGGL(k_mwi_bmm<KK>, dim3(nt * nt, q.NB, 2), dim3(MW_NT), st->sm_bmm, M, q, p, 5, 0);
+            hipLaunchKernelGGL((k_mwi_step<KK, DD>), dim3(q.NB, 2, 1), dim3(MW_NT), st->sm_step, M, q, p, wl, 3, st->iter, 0);
+        });
+    } else
+    MW_DISPATCH(c, hipLaunchKernelGGL((k_mwi_step<KK, DD>), dim3(q.NB, 2, ip == 2 ? st->zs_step : 1), dim3(MW_NT), st->sm_step, M, q, p, wl, ip, st->iter, 0));
+    return 0;
+}
 static int mw_ipm_enqueue_body(clrs_mw_ctx *c) {
     const MwDev &q = c->d;
     MwIpm *st = c->ipm;
@@ -599,17 +617,7 @@ static int mw_ipm_enqueue_body(clrs_mw_ctx *c) {
     c->d.aff_mu = nullptr;
     if (rc) return rc;
     if ((rc = mw_ipm_rhs(c, M, 1))) return rc;
-    const int ip = st->y_with_x ? 2 : st->step_inv ? 1 : 0, wl = st->step_w_lds ? 1 : 0;
-    // both step lengths in one launch; with every inverse factor in memory the congruences are split over column panels (zs workgroups each)
-    if (ip == 2 && st->z_tiled) {                         // large blocks: the two products of each congruence as tiled launches, then the eigenvalues
-        const int nt = ((int)st->maxn_inv + MWI_BT - 1) / MWI_BT;
-        MW_DISPATCH(c, {
-            hipLaunchKernelGGL(k_mwi_bmm<KK>, dim3(nt * nt, q.NB, 2), dim3(MW_NT), st->sm_bmm, M, q, p, 4, 0);
-            hipLaunchKernelGGL(k_mwi_bmm<KK>, dim3(nt * nt, q.NB, 2), dim3(MW_NT), st->sm_bmm, M, q, p, 5, 0);
-            hipLaunchKernelGGL((k_mwi_step<KK, DD>), dim3(q.NB, 2, 1), dim3(MW_NT), st->sm_step, M, q, p, wl, 3, st->iter, 0);
-        });
-    } else
-    MW_DISPATCH(c, hipLaunchKernelGGL((k_mwi_step<KK, DD>), dim3(q.NB, 2, ip == 2 ? st->zs_step : 1), dim3(MW_NT), st->sm_step, M, q, p, wl, ip, st->iter, 0));
+    if ((rc = mw_ipm_launch_step(c, M))) return rc;
     if ((rc = mw_ipm_exchange(c, M, 3))) return rc;
     MW_DISPATCH(c, {
         if (q.world > 1) hipLaunchKernelGGL((k_mwi_scalar<KK, DD>), dim3(1), dim3(1), 0, M, q, p, 3, st->iter);
@@ -781,5 +789,71 @@ extern "C" int clrs_mw_ipm_objectives(clrs_mw_ctx *c, double *out) {
         out[K + l] = h[(size_t)l * MSC_COUNT + MSC_POBJ];
         out[2 * K + l] = h[(size_t)l * MSC_COUNT + MSC_GAP];
     }
+    return 0;
+}
+
+// ---- test hooks of the step length -------------------------------------------------------------------------------------------------------
+// clrs_test_min_eig, forms 0 and 1 (the C entry point and its argument checks: clrs_hip.hip): workgroup b copies the b-th matrix into LDS as k_mwi_step holds
+// its W (full storage, leading dimension n) and calls the routine; work space of 3 n + 2 MW_NT doubles behind it, as in k_mwi_step.
+__global__ __launch_bounds__(MW_NT) void k_mw_test_min_eig(const double *A, double *out, int n, int form) {
+    using namespace mwk;
+    lds_d *W = MW_LDS, *work = W + n * n;
+    const int tid = threadIdx.x;
+    const double *Ag = A + (long)blockIdx.x * n * n;
+    for (int e = tid; e < n * n; e += MW_NT) W[e] = Ag[e];
+    __syncthreads();
+    const double ev = form == 0 ? wg_min_eig32(W, n, work, tid) : wg_min_eig(W, n, work, tid);
+    if (tid == 0) out[blockIdx.x] = ev;
+}
+int mw_test_min_eig_launch(int form, int n, int count, const double *dA, double *dOut) {
+    const size_t sm = sizeof(double) * ((size_t)n * n + 3 * (size_t)n + 2 * MW_NT);
+    int rc;
+    if ((rc = mw_set_lds(k_mw_test_min_eig, sm))) return rc;
+    hipLaunchKernelGGL(k_mw_test_min_eig, dim3(count), dim3(MW_NT), sm, nullptr, dA, dOut, n, form);
+    MWCHECK(hipGetLastError());
+    return 0;
+}
+
+// The step-length stage of one iteration on matrices given to it: X, Y, dX, dY (planar limbs, K x xy_len each) go into the iteration's buffers, then the
+// Cholesky launch of an iteration (chol X, and chol(Y)^-1 where it rides along) and mw_ipm_launch_step run with the plan the context chose, as the first
+// iteration of a solve would run them (limbs of the factor stage: mw_ipm_reset_kf).  eig[2 NB]: what the step kernel left in its eigenvalue buffer
+// ((X, dX) of every block, then (Y, dY)); info[8] = {inv_path, W in LDS, tiled products, column panels, limbs of the factors, failure flag, 0, 0}.
+// The iterate is overwritten: clrs_mw_ipm_init or clrs_mw_ipm_set before the next solve.  Unsharded contexts.
+extern "C" int clrs_mw_test_step_eig(clrs_mw_ctx *c, const double *X, const double *Y, const double *dX, const double *dY, double *eig, int32_t *info) {
+    if (!c || !c->ipm || !c->ipm->ready) return mw_fail(CLRS_ERR_STATE, "clrs_mw_ipm_create first");
+    if (!X || !Y || !dX || !dY || !eig || !info) return mw_fail(CLRS_ERR_INVALID, "null argument");
+    if (c->d.world > 1 || c->d.gathered) return mw_fail(CLRS_ERR_STATE, "clrs_mw_test_step_eig on a sharded context");
+    MWCHECK(hipSetDevice(c->device));
+    const MwDev &q = c->d;
+    MwIpm *st = c->ipm;
+    const MwIpmDev &p = st->d;
+    const size_t bytes = sizeof(double) * (size_t)q.xylen * c->K;
+    int rc;
+    if ((rc = mw_ipm_drain(c))) return rc;
+    MWCHECK(hipMemcpy(p.X, X, bytes, hipMemcpyHostToDevice));
+    MWCHECK(hipMemcpy(p.Y, Y, bytes, hipMemcpyHostToDevice));
+    MWCHECK(hipMemcpy(p.dX, dX, bytes, hipMemcpyHostToDevice));
+    MWCHECK(hipMemcpy(p.dY, dY, bytes, hipMemcpyHostToDevice));
+    if ((rc = mw_ipm_arm(c))) return rc;                                       // status words, flags (the failure flag, the counter of finished workgroups)
+    MWCHECK(hipMemsetAsync(p.wcnt, 0, sizeof(int) * 2 * q.NB, c->stream));     // the panel counters
+    MWCHECK(hipMemsetAsync(p.eig, 0, sizeof(double) * 2 * q.NB, c->stream));
+    mw_ipm_reset_kf(c);
+    c->d.kf = st->kf_now;
+    rc = mw_cholesky_blocks_dev2(c, p.X, p.Xc, st->y_with_x ? p.Y : nullptr, p.Yi, p.yfail);
+    if (!rc) rc = mw_ipm_launch_step(c, c->stream);
+    const int kf_used = c->d.kf;
+    c->d.kf = c->kf_entry;
+    if (rc) return rc;
+    MWCHECK(hipGetLastError());
+    MWCHECK(hipStreamSynchronize(c->stream));
+    int flags[8];
+    MWCHECK(hipMemcpy(eig, p.eig, sizeof(double) * 2 * q.NB, hipMemcpyDeviceToHost));
+    MWCHECK(hipMemcpy(flags, p.flags, sizeof(flags), hipMemcpyDeviceToHost));
+    info[0] = st->y_with_x ? 2 : st->step_inv ? 1 : 0;
+    if (info[0] == 2 && st->z_tiled) info[0] = 3;
+    info[1] = st->step_w_lds ? 1 : 0; info[2] = st->z_tiled ? 1 : 0; info[3] = st->zs_step; info[4] = kf_used; info[5] = flags[2]; info[6] = info[7] = 0;
+    // the launch ended with the step lengths of these matrices in the scalar slots and possibly an error code in the flags: re-armed for what follows
+    if ((rc = mw_ipm_arm(c))) return rc;
+    MWCHECK(hipStreamSynchronize(c->stream));
     return 0;
 }

@@ -339,6 +339,24 @@ class MwSchurContext:
     def set_stream(self, hip_stream: int):
         _lib.check(self.L.clrs_mw_set_stream(self.h, C.c_void_p(hip_stream)))
 
+    # -- test hooks ------------------------------------------------------------------------------
+    def ipm_create(self):
+        """clrs_mw_ipm_create_ex with the objective data of the FlatSDP (what `solvesdp_mw` does first): the iteration's buffers and its plan."""
+        f = self.flat
+        keep = self._ipm_keep = [self._data("C"), self._data("c"), self._data("b") if f.n_free else np.zeros((self.data_limbs, 1))]
+        data = _lib.IpmData(_dp(keep[0]), _dp(keep[1]), _dp(keep[2]), int(f.maximize), 0, float(f.constant))
+        _lib.check(self.L.clrs_mw_ipm_create_ex(self.h, C.byref(data), self.data_limbs))
+
+    def test_step_eig(self, X, Y, dX, dY):
+        """clrs_mw_test_step_eig (after `ipm_create`): the step-length stage of an iteration on the given planar-limb matrices.  Returns (eig, info):
+        eig (2, n_blocks) -- row 0 of (X, dX), row 1 of (Y, dY) -- and the eight plan / status words as a dict."""
+        f = self.flat
+        a = [self._planar(m, f.xy_len) for m in (X, Y, dX, dY)]
+        eig, info = np.zeros(2 * f.n_blocks), np.zeros(8, dtype=np.int32)
+        _lib.check(self.L.clrs_mw_test_step_eig(self.h, _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3]), _dp(eig), info.ctypes.data_as(_lib.p_i32)))
+        names = ("ip", "w_in_lds", "z_tiled", "zs_step", "kf", "fail")
+        return eig.reshape(2, f.n_blocks), {k: int(v) for k, v in zip(names, info)}
+
 
 class LocalGroup:
     """clrs_mw_local_group: the in-process stand-in for the RCCL communicators (`world` contexts on one device, one thread each)."""
@@ -354,6 +372,17 @@ class LocalGroup:
         if getattr(self, "h", None):
             self.L.clrs_mw_local_group_destroy(self.h)
             self.h = None
+
+
+def min_eig_hook(form: int, A, device: int = 0) -> np.ndarray:
+    """clrs_test_min_eig: the smallest eigenvalue of every symmetric matrix of the batch `A` (count, n, n) by one of the three fp64 routines of the step
+    length -- form 0 / 1: the multi-word step kernel's routine for n <= 64 / for larger blocks, form 2: the fp64 loop's.  One launch."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    if A.ndim != 3 or A.shape[1] != A.shape[2]:
+        raise ValueError(f"expected a batch of square matrices (count, n, n), got {A.shape}")
+    out = np.zeros(A.shape[0])
+    _lib.check(_lib.load().clrs_test_min_eig(int(device), int(form), int(A.shape[1]), int(A.shape[0]), _dp(A), _dp(out)))      # (symmetric: row-major = column-major)
+    return out
 
 
 def rank_reveal(G, n, ncand, tau, limbs: int, device: int = 0):

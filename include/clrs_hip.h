@@ -619,6 +619,21 @@ int clrs_test_gemm(int device, int ta, int tb, int M, int N, int K, double alpha
  * matrix (returns 0 or 1 on a non-positive pivot), and B <- L^-1 B / L^-T B. */
 int clrs_test_potrf(int device, int n, double *A, int lda);
 int clrs_test_trsm(int device, int trans, int n, int nrhs, const double *L, int ldl, double *B, int ldb);
+/* Test hooks of the step length (src/solver.jl:1620-1693).
+ * The three fp64 smallest-eigenvalue routines on matrices given to them: A holds `count` symmetric n x n matrices (column-major, both
+ * triangles, back to back), out[count] receives their smallest eigenvalues; one launch, one workgroup per matrix.  form 0: the routine of the
+ * multi-word step kernel for n <= 64 (2 <= n <= 64); form 1: its routine for larger blocks (1 <= n <= 128); form 2: the routine of the fp64
+ * loop's step kernel (2 <= n <= 64).  Other sizes: CLRS_ERR_INVALID.  Domain: entries above about 2^-500 in magnitude, or zero (below, the
+ * squares in x^T x underflow). */
+int clrs_test_min_eig(int device, int form, int n, int count, const double *A, double *out);
+/* The step-length stage of one multi-word iteration on matrices given to it (after clrs_mw_ipm_create; unsharded contexts): X, Y, dX, dY
+ * (planar limbs, limbs x xy_len each) are uploaded into the iteration's buffers, the iteration's Cholesky launch and its step-length launches
+ * run with the plan the context chose, and eig[2 * n_blocks] receives what they leave per block: lambda_min(L^-1 dM L^-T) - 1e-5 (dM / M
+ * for 1 x 1 blocks, 0 for a block whose M is not positive definite), (X, dX) of every block first, then (Y, dY).  info[8] = {form of the
+ * congruence (0: substitutions, 1: Y factored inside the launch, 2: inverse factors, 3: inverse factors through tiled products), W in LDS,
+ * tiled products, column panels per congruence, limbs of the factors, failure flag, 0, 0}.  The iterate is overwritten: clrs_mw_ipm_init or
+ * clrs_mw_ipm_set before the next solve. */
+int clrs_mw_test_step_eig(clrs_mw_ctx *ctx, const double *X, const double *Y, const double *dX, const double *dY, double *eig, int32_t *info);
 
 /* Measurement hook: average duration (us, HIP events, `reps` back-to-back launches) of a pure streaming kernel that reads
  * `read_bytes` (two streams) and writes `write_bytes` (one stream, non-temporal) of freshly allocated device memory: the rate a
