@@ -169,6 +169,8 @@ SYMBOLS = {
     "clrs_modp_dixon_lift_multi_times": (C.c_int, [p_d, p_d, p_d, p_d]),
     "clrs_zz_lowrank_system": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_i32, C.c_int, p_i32, C.c_int, p_i32, C.c_int, p_i32, p_i32, C.c_int, p_i32, p_i32]),
     "clrs_zz_lowrank_system_times": (C.c_int, [p_d, p_d, p_d]),
+    "clrs_zz_lll": (C.c_int, [C.c_int, C.c_int, p_i32, p_i32, p_i32, C.c_int, p_i32, p_i32, C.c_double, C.c_double, C.c_int, C.c_int, p_i32]),
+    "clrs_zz_lll_times": (C.c_int, [p_d, p_d]),
     "clrs_mw_schur_solve": (C.c_int, [C.c_void_p, p_d, p_d, p_d, p_d]),
     "clrs_mw_cholesky_blocks_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "clrs_mw_sync_status_cholesky": (C.c_int, [C.c_void_p]),
@@ -234,9 +236,12 @@ def _hipcc(args):
 
 # translation units of libclrs_hip.so: (object, source, extra flags, predicate selecting the files it depends on)
 _UNITS = (
-    ("clrs_hip.o", "clrs_hip.hip", (), lambda f: not f.startswith(("clrs_mw", "clrs_modp"))),
+    ("clrs_hip.o", "clrs_hip.hip", (), lambda f: not f.startswith(("clrs_mw", "clrs_modp", "clrs_zz"))),
     # the elimination mod p, the p-adic lifting on it, the reconstruction and the leading minors mod many primes (clrs_modp_rref, clrs_modp_dixon_lift, clrs_modp_dixon_lift_multi, clrs_modp_dixon_reconstruct, clrs_modp_minors) and the exact integer matrix product (clrs_zz_gemm): a small unit of its own, no multi-word flags
     ("clrs_modp.o", "clrs_modp.hip", (), lambda f: f.startswith("clrs_modp")),
+    # the batched LLL reduction (clrs_zz_lll): exact integer rows steered by K-limb floating point, so no contraction here either; it reads the digit arithmetic
+    # of the exact product and the multi-word arithmetic
+    ("clrs_zz_lll.o", "clrs_zz_lll.hip", ("-ffp-contract=off",), lambda f: f.startswith("clrs_zz_lll") or f in ("clrs_modp_zz_arith.h", "clrs_mw_arith.h")),
     # the multi-word (extended precision) path: error-free transformations must not be contracted into FMAs
     ("clrs_mw.o", "clrs_mw.hip", ("-ffp-contract=off", "-DMW_SPLIT_UNITS"), lambda f: f.startswith("clrs_mw")),
     # the device code of the larger limb counts, one unit each (explicit instantiations: clrs_mw_inst.h), compiled side by side

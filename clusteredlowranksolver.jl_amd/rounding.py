@@ -30,8 +30,13 @@ Between the kernel vectors and the projection stands `basis_transformations` (sr
 basis vectors]`, `Binv = inv(B)` over QQ, its rows normalised by the lcm of their denominators, and `transform` / `undo_transform` (src/rounding.jl:1191-1253),
 which multiply with it.  The inverse is an exact solve with a matrix of right-hand sides: Dixon's lifting with both products of a step as fp64 MFMA GEMMs on
 the device (clrs_modp_dixon_lift_multi): `dixon_lift_multi`, `solve_dixon_multi`, `inverse_qq`, `complete_basis`,
-`basis_transformations`, `transform`, `undo_transform`.  Only the reference's unreduced branch is built: the HNF / LLL reduction of the kernel vectors
-(`reduce_kernelvectors`) is not on the device yet.
+`basis_transformations`, `transform`, `undo_transform`.
+
+The reference's reduced branch (`simplify_kernelvectors`, `reduction_step`, `basis_nullspace_remaining`, src/rounding.jl:860-1104: an LLL-reduced Z-basis of the
+saturated lattice of the kernel vectors and a unimodular basis change) is an LLL reduction of one embedded lattice per block, a batch on the device
+(clrs_zz_lll): `lll_batch`, `lll`, `reduce_kernel_vectors`, and `basis_transformations(..., reduce=reduce_kernel_vectors)`.  It is
+taken only when `reduce=` is given: without it the default settings still raise `NotImplementedError`.  Not built: number fields of degree above 1, the
+reference's `kernel_lll`, and its partial-column heuristic above `reduce_kernelvectors_cutoff`.
 
 The system the projection solves is assembled from an `ExactProblem` (the problem over QQ; `to_sdp` gives the numeric one) by `linear_system`
 (`partial_linearsystem`, src/interface.jl:1354-1535): per low-rank block one call of clrs_zz_lowrank_system, a row-wise Gram of long
@@ -54,7 +59,8 @@ __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vecto
            "solve_system_pseudoinverse", "project_to_affine_space", "to_digits24", "from_digits24", "dixon_reconstruct", "leading_minors_mod", "minor_bounds", "crt_tree",
            "PDCertificate", "checkpd", "is_valid_solution", "ints_to_planes", "planes_to_ints", "zz_matmul", "dixon_lift_multi", "DixonSolutionMatrix",
            "solve_dixon_multi", "inverse_qq", "complete_basis", "basis_transformations", "transform", "undo_transform", "lowrank_system", "ExactLowRank", "ExactBlock",
-           "ExactProblem", "ExactSolution", "system_index", "linear_system", "select_columns", "vectorize_solution", "get_rational_system", "exact_solution"]
+           "ExactProblem", "ExactSolution", "system_index", "linear_system", "select_columns", "vectorize_solution", "get_rational_system", "exact_solution",
+           "ReductionError", "lll_first_rung", "lll_batch", "lll", "kernel_lattice", "reduce_kernel_vectors"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -70,7 +76,8 @@ class RoundingSettings:
     pseudo: bool = True                     # solve through the pseudoinverse of a few more columns than rows (src/rounding.jl:23, 213)
     pseudo_columnfactor: float = 1.05       # that many columns per row; at least 1 (src/rounding.jl:60-62)
     extracolumns_linindep: bool = False     # take the extra columns linearly independent of each other instead of at random
-    reduce_kernelvectors: bool = True       # HNF / LLL reduction of the kernel vectors (src/rounding.jl:860-1060): not built, basis_transformations refuses it
+    reduce_kernelvectors: bool = True       # LLL reduction of the kernel vectors (src/rounding.jl:860-1060): basis_transformations takes it with `reduce=`, and refuses it without
+    unimodular_transform: bool = True       # with the reduction: the whole basis change unimodular (src/rounding.jl:960-963); False: only the kernel vectors are replaced
     normalize_transformation: bool = True   # rows of Binv times the lcm of their denominators, columns of B divided by it (src/rounding.jl:844-850)
     approximation_decimals: int = 40        # the numeric solution is cut to this many decimals before the projection (roundx, src/rounding.jl:515)
     redundancyfactor: int = 10              # select_columns takes about this many columns per constraint; negative: all (src/rounding.jl:95-153)
@@ -1583,60 +1590,299 @@ def undo_transform(Mt, Binv, s: int, matmul=None, device: int = 0) -> np.ndarray
     return transform(padded, Bf.T, 0, matmul=matmul, device=device)
 
 
-def basis_transformations(kernels, settings: Optional[RoundingSettings] = None, device: int = 0, maxprimes: int = 3, batch=None, lift=None, check: bool = True,
-                          reconstruct=None, matmul=None) -> dict:
-    """The reference's `basis_transformations` over QQ (src/rounding.jl:750-858), its unreduced branch (src/rounding.jl:967-971, 1017-1050).  `kernels` maps a
-    block key to `(N, vectors)`: the size of the block and its s rational kernel vectors, each of N entries (what `vectors_to_fractions(BlockKernel)`
-    returns); they become the first s columns of B.  Per key, in the order of `kernels`: `B = [V | E]` with the standard basis vectors E of
-    `complete_basis`, `Binv = inverse_qq(B)`, and, with `settings.normalize_transformation`, row i of Binv multiplied by the least common multiple of its
-    denominators and column i of B divided by it (src/rounding.jl:844-850).  A block without kernel vectors gives identities and s = 0.  Returns
-    `{key: (B^T, Binv, s)}`, object arrays (N, N) of `Fraction`s, like the reference.
-    The completion is tested against the inverse: an e_i that was not taken must lie in the span of V and the e_j taken before it, i.e. column i of Binv is
-    zero in the rows of the e_j taken with j > i; otherwise the prime of `complete_basis` divided a deciding minor and the next prime is taken (at most
-    `maxprimes` times, then `ArithmeticError`).
-    With `settings.reduce_kernelvectors` true (the default, as in the reference) this raises `NotImplementedError`: the HNF / LLL reduction of the kernel
-    vectors (`reduction_step`, src/rounding.jl:860-1060) is not on the device yet; neither are number fields of degree above 1.  Pass
-    `RoundingSettings(reduce_kernelvectors=False)`.
-    `batch` goes to `complete_basis`; `lift`, `check`, `reconstruct`, `matmul` go to `inverse_qq`."""
+# ---- LLL reduction of a batch of lattices; the reduced, unimodular basis change (src/rounding.jl:860-1104; clrs_zz_lll) ------------------
+LLL_LIMBS = (2, 4, 6)                # the rungs of the ladder: the fp64 words of the Gram-Schmidt data clrs_zz_lll is instantiated for
+LLL_MAX_ROWS, LLL_MAX_COLS, LLL_MAX_DIGITS = 128, 256, 20
+
+
+class ReductionError(ArithmeticError):
+    """`lll_batch` could not reduce a lattice: status 1 or 2 on the last rung of the ladder, or entries beyond the digits clrs_zz_lll takes; or
+    `reduce_kernel_vectors` could not verify a block on the last rung."""
+
+
+def lll_first_rung(bits: int, d: int) -> int:
+    """The rung (fp64 words of the Gram-Schmidt data) a lattice of `d` rows with entries of at most `bits` bits starts on: the least of 2, 4, 6 words with
+    53 words >= 2 bits + ceil(1.6 d) + 10 (2 bits for the cancellation in r_kk = G_kk - sum mu_kj r_kj of a size-reduced row,
+    1.6 d for the growth of errors along the Cholesky row at (delta, eta) = (0.99, 0.51), 10 to spare), else 6."""
+    need = 2 * int(bits) + -(-8 * int(d) // 5) + 10
+    return next((K for K in LLL_LIMBS if 53 * K >= need), LLL_LIMBS[-1])
+
+
+def _lll_call_device(rows, cols, cols_gram, nd, digits, delta, eta, limbs, max_swaps, device=0):
+    """one call of clrs_zz_lll: `digits` the packed planes (int32, flat); returns (out (flat, zeros where nothing was written), info (nb, 8))"""
+    rows, cols, cols_gram = (np.ascontiguousarray(a, np.int32) for a in (rows, cols, cols_gram))
+    digits = np.ascontiguousarray(digits, np.int32).reshape(-1)
+    out, info = np.zeros(max(digits.size, 1), np.int32), np.zeros((max(rows.size, 1), 8), np.int32)
+    ptr = lambda a: a.ctypes.data_as(_lib.p_i32)
+    _lib.check(_lib.load().clrs_zz_lll(int(device), int(rows.size), ptr(rows), ptr(cols), ptr(cols_gram), int(nd), ptr(digits) if digits.size else ptr(out), ptr(out),
+                                       float(delta), float(eta), int(limbs), int(max_swaps), ptr(info)))
+    return out[:digits.size], info[:rows.size]
+
+
+def lll_batch(lattices, delta: float = 0.99, eta: float = 0.51, transform: bool = False, limbs: Optional[int] = None, device: int = 0, cols_gram=None,
+              max_swaps: Optional[int] = None, call=None):
+    """LLL-reduce a batch of integer lattices on the device (clrs_zz_lll, one workgroup per lattice).  `lattices`: matrices of Python integers (anything
+    `np.asarray` takes), each with at most 128 independent rows and 256 columns.  Returns the reduced bases as object arrays, in order; with `transform`
+    pairs `(out, U)` with `U` unimodular and `U A == out` (an identity is appended to the rows and kept out of the dot products).  `cols_gram`: per lattice
+    the number of leading columns the dot products run over (default: all).  Every row operation is exact, so `out` spans the lattice of the input
+    whatever the floating point does; `(delta, eta)` are what the floating-point Gram-Schmidt data aim at.
+    Per lattice: the digits `nd` come from the bit length of its entries plus 40 bits of headroom, and on status 3 (an entry left its digits) the lattice is
+    repeated with two more; the first rung is `lll_first_rung(bits, d)` (or `limbs`), and on status 1 or 2 the lattice alone is repeated on the next rung
+    from its original input; past the last rung, or past 20 digits, `ReductionError`.  `max_swaps` defaults to twice the potential bound
+    d (d - 1) log2(max row norm) / log2(1 / delta), clipped to int32.  Lattices that share (rung, digits) go in one device call, which takes ONE cap: the
+    largest of its members'.  A lattice in a batch may so be given more exchanges than it would get alone, never fewer: a lattice that ends with status 0
+    gives the digits and counters of its single call, and only where a cap is reached (status 1) can the batch differ from the single calls.  The counters are kept in
+    `lll_batch.last_info`: per lattice a dict with `status`, `swaps`, `passes`, `launches`, `limbs`, `nd` and `rungs`, the list of every
+    (limbs, nd, status) tried.  `call` replaces the device call (the tests' host build)."""
+    from math import log2
+    call = _lll_call_device if call is None else call
+    if limbs is not None and int(limbs) not in LLL_LIMBS:
+        raise ValueError(f"lll_batch: limbs must be one of {LLL_LIMBS}, got {limbs}")
+    mats, grams, jobs = [], [], []
+    for idx, A in enumerate(lattices):
+        a = _integer_matrix(A, "lll_batch")
+        a = np.array([int(v) for v in a.flat], dtype=object).reshape(a.shape)
+        d, c = a.shape
+        g = c if cols_gram is None else int(cols_gram[idx])
+        if d > LLL_MAX_ROWS or c + (d if transform else 0) > LLL_MAX_COLS or not 0 <= g <= c or (d and g < 1):
+            raise ValueError(f"lll_batch: lattice {idx}: at most {LLL_MAX_ROWS} rows and {LLL_MAX_COLS} columns (the identity of `transform` included) and "
+                             f"1 <= cols_gram <= cols, got {d} x {c} and cols_gram = {g}")
+        if transform:
+            wide = np.zeros((d, c + d), dtype=object)
+            wide[:, :c] = a
+            for i in range(d):
+                wide[i, c + i] = 1
+            a = wide
+        mats.append(a)
+        grams.append(g)
+        bits = max((abs(int(v)).bit_length() for v in a.flat), default=0)
+        norm2 = max((sum(int(v) * int(v) for v in a[i, :g]) for i in range(d)), default=1)
+        bound = 2.0 * d * (d - 1) * max(0.5 * log2(max(norm2, 2)), 1.0) / log2(1.0 / delta) if delta < 1 else float(2 ** 31 - 1)
+        jobs.append({"rung": LLL_LIMBS.index(int(limbs) if limbs is not None else lll_first_rung(bits, d)), "nd": (bits + 40) // DIGIT_BITS + 1,
+                     "max_swaps": int(min(max(bound, 16.0), 2 ** 31 - 1)) if max_swaps is None else int(max_swaps), "rungs": [], "out": None, "info": None})
+    pending = list(range(len(mats)))
+    while pending:
+        groups = {}
+        for idx in pending:
+            if jobs[idx]["nd"] > LLL_MAX_DIGITS:
+                lll_batch.last_info = [dict(j["info"] or {}, rungs=j["rungs"]) for j in jobs]
+                raise ReductionError(f"lll_batch: lattice {idx} needs {jobs[idx]['nd']} digits of {DIGIT_BITS} bits, clrs_zz_lll takes {LLL_MAX_DIGITS}")
+            groups.setdefault((jobs[idx]["rung"], jobs[idx]["nd"]), []).append(idx)
+        pending = []
+        for (rung, nd), members in sorted(groups.items()):
+            K = LLL_LIMBS[rung]
+            planes = [ints_to_planes(mats[i], nd) if mats[i].size else np.zeros((nd,) + mats[i].shape, np.int32) for i in members]
+            digits = np.concatenate([p.reshape(-1) for p in planes]) if planes else np.zeros(0, np.int32)
+            out, info = call([mats[i].shape[0] for i in members], [mats[i].shape[1] for i in members], [grams[i] for i in members], nd, digits, delta, eta, K,
+                             max(jobs[i]["max_swaps"] for i in members), device=device)
+            off = 0
+            for pos, i in enumerate(members):
+                count, job = planes[pos].size, jobs[i]
+                status = int(info[pos][0])
+                job["rungs"].append((K, nd, status))
+                job["info"] = {"status": status, "swaps": int(info[pos][1]), "passes": int(info[pos][2]), "launches": int(info[pos][3]), "limbs": K, "nd": nd}
+                if status == 0:
+                    job["out"] = planes_to_ints(np.asarray(out[off:off + count]).reshape(planes[pos].shape)) if count else mats[i].copy()
+                elif status == 3:
+                    job["nd"] += 2
+                    pending.append(i)
+                elif status in (1, 2) and rung + 1 < len(LLL_LIMBS):
+                    job["rung"] += 1
+                    pending.append(i)
+                else:
+                    lll_batch.last_info = [dict(j["info"] or {}, rungs=j["rungs"]) for j in jobs]
+                    raise ReductionError(f"lll_batch: lattice {i}: status {status} on the last rung ({K} words, {nd} digits); tried {job['rungs']}")
+                off += count
+    lll_batch.last_info = [dict(j["info"] or {}, rungs=j["rungs"]) for j in jobs]
+    if not transform:
+        return [j["out"] for j in jobs]
+    return [(j["out"][:, :j["out"].shape[1] - j["out"].shape[0]], j["out"][:, j["out"].shape[1] - j["out"].shape[0]:]) for j in jobs]
+
+
+lll_batch.last_info = None
+
+
+def lll(A, delta: float = 0.99, eta: float = 0.51, transform: bool = False, limbs: Optional[int] = None, device: int = 0, **kw):
+    """`lll_batch` for one lattice: the reduced basis of the rows of `A`, or `(out, U)` with `transform`."""
+    return lll_batch([A], delta=delta, eta=eta, transform=transform, limbs=limbs, device=device, **kw)[0]
+
+
+def kernel_lattice(N: int, s: int, M, R: int, q_extra: int = 0):
+    """The lattice whose reduction gives the unimodular basis change of a block: the N rows of `[lambda M^T | I_N]`, an object
+    matrix N x (N - s + N), with `M` ((N - s) x N, integers of rank N - s whose integer kernel is the lattice L wanted) and lambda = 2^(24 q), q the least
+    with 24 q >= ceil((N - 1) / 2) + ceil(log2 R) + 2 (`R` an integer: L holds s independent vectors of norm <= R), plus `q_extra`.  Returns (rows, q)."""
+    N, s, R = int(N), int(s), max(int(R), 1)
+    M = _integer_matrix(M, "kernel_lattice")
+    if M.shape != (N - s, N):
+        raise ValueError(f"kernel_lattice: M must be ({N - s}, {N}), got {M.shape}")
+    need = -(-(N - 1) // 2) + (R - 1).bit_length() + 2
+    q = -(-need // DIGIT_BITS) + int(q_extra)
+    rows = np.zeros((N, N - s + N), dtype=object)
+    for i in range(N):
+        for r in range(N - s):
+            rows[i, r] = int(M[r, i]) << (DIGIT_BITS * q)
+        rows[i, N - s + i] = 1
+    return rows, q
+
+
+def reduce_kernel_vectors(blocks, settings: Optional[RoundingSettings] = None, device: int = 0, matmul=None, lll=None):
+    """The reduction of the kernel vectors of every block in ONE `lll_batch` call (the reference's `reduction_step`, src/rounding.jl:1062-1104, without an
+    HNF).  `blocks`: a list of `(N, s, M, R)` as `kernel_lattice` takes them, 0 < s < N.  Returns per block the integer matrix `U` (N x N, an object array):
+    unimodular by construction, its first s rows an LLL-reduced Z-basis of `L = {u in Z^N : M u = 0}`.  What the rest of the chain relies on is verified
+    exactly: the left part `lambda M u` of the first s reduced rows is zero and that of the others is not, and `M U^T[:, :s] == 0` as one product
+    (`matmul(A, B, device=...)`, default Python integers).  A block that fails is repeated with lambda 2^24 times as large, then on the next rung of the
+    ladder, and is a `ReductionError` past the last.  `lll` replaces `lll_batch` (same keywords).  `settings` is the second argument every `reduce=` hook is
+    called with; this one reads nothing from it (delta and eta are `lll_batch`'s defaults, FLINT's)."""
+    reduce_batch = lll_batch if lll is None else lll
+    blocks = [(int(N), int(s), _integer_matrix(M, "reduce_kernel_vectors"), int(R)) for N, s, M, R in blocks]
+    for N, s, M, R in blocks:
+        if not 0 < s < N or N > LLL_MAX_ROWS:
+            raise ValueError(f"reduce_kernel_vectors: 0 < s < N <= {LLL_MAX_ROWS} is needed, got N = {N}, s = {s}")
+    out = [None] * len(blocks)
+    attempts = [(0, None)] + [(1, None)] + [(1, K) for K in LLL_LIMBS[1:]]            # (more of lambda, rung): each block walks this list on its own
+    step = [0] * len(blocks)
+    todo = list(range(len(blocks)))
+    infos = [None] * len(blocks)
+    while todo:
+        ready = {}
+        for b in todo:
+            ready.setdefault(attempts[step[b]][1], []).append(b)
+        todo = []
+        for K, members in ready.items():
+            lattices = [kernel_lattice(*blocks[b], q_extra=attempts[step[b]][0])[0] for b in members]
+            reduced = reduce_batch(lattices, limbs=K, device=device)
+            last = getattr(reduce_batch, "last_info", None)
+            for pos, (b, red) in enumerate(zip(members, reduced)):
+                N, s, M, _ = blocks[b]
+                infos[b] = last[pos] if last else None
+                left, U = red[:, :N - s], red[:, N - s:]
+                ok = all(int(v) == 0 for v in left[:s].flat) and all(any(int(v) != 0 for v in left[i]) for i in range(s, N))
+                if ok:
+                    prod = _matmul_matrix(matmul, np.array([int(v) for v in M.flat], dtype=object).reshape(M.shape), np.ascontiguousarray(U[:s].T), device)
+                    ok = all(int(v) == 0 for v in np.asarray(prod, dtype=object).flat)
+                if ok:
+                    out[b] = U
+                    continue
+                step[b] += 1
+                while step[b] < len(attempts) and attempts[step[b]][1] is not None and infos[b] and attempts[step[b]][1] <= infos[b].get("limbs", 0):
+                    step[b] += 1                                                        # (a rung the ladder of lll_batch has already passed)
+                if step[b] >= len(attempts):
+                    raise ReductionError(f"reduce_kernel_vectors: block {b} (N = {N}, s = {s}) failed its exact verification on every rung")
+                todo.append(b)
+    reduce_kernel_vectors.last_info = infos
+    return out
+
+
+reduce_kernel_vectors.last_info = None
+
+
+def _unreduced_basis(key, N, vectors, settings, device, maxprimes, batch, lift, check, reconstruct, matmul):
+    """B = [V | E] with the greedy completion E and Binv = inverse_qq(B), not normalised (the loop over primes of `basis_transformations`)"""
+    s = len(vectors)
+    B = _object_matrix(np.zeros((N, N), dtype=object), "basis_transformations", Fraction)
+    for c, v in enumerate(vectors):
+        if len(v) != N:
+            raise ValueError(f"basis_transformations: block {key!r}: vector {c} has {len(v)} entries for a block of size {N}")
+        B[:, c] = [Fraction(x) for x in v]
+    below = None
+    for _ in range(int(maxprimes)):
+        extra = complete_basis(B[:, :s], maxprimes=maxprimes, device=device, batch=batch, below=below)
+        B[:, s:] = Fraction(0)
+        for c, i in enumerate(extra):
+            B[i, s + c] = Fraction(1)
+        Binv = np.asarray(inverse_qq(B, maxprimes=maxprimes, device=device, lift=lift, check=check, reconstruct=reconstruct, matmul=matmul))
+        taken = set(extra)
+        if all(Binv[s + c, i] == 0 for i in range(N) if i not in taken for c, j in enumerate(extra) if j > i):
+            return B, Binv
+        below = extra.p
+    raise ArithmeticError(f"basis_transformations: block {key!r}: no prime gave the greedy completion of the kernel vectors")
+
+
+def _normalized(B, Binv):
+    """row i of Binv times the least common multiple of its denominators, column i of B divided by it (src/rounding.jl:844-850), in place"""
     from math import gcd
+    for i in range(B.shape[0]):
+        l = 1
+        for v in Binv[i]:
+            l = l * v.denominator // gcd(l, v.denominator)
+        Binv[i] = [v * l for v in Binv[i]]
+        B[:, i] = [v / l for v in B[:, i]]
+
+
+def _kernel_block(N, vectors, Binv0):
+    """(N, s, M, R) of a block for `reduce_kernel_vectors`: M = the rows s .. N - 1 of inv([V | E]), which annihilate V, each cleared of denominators and of
+    its content; R = an integer bound on the norms of the vectors times the lcm of their denominators"""
+    from math import gcd, isqrt
+    s = len(vectors)
+    M = _rows_cleared_of_denominators([[Fraction(v) for v in Binv0[r]] for r in range(s, N)])
+    for r in range(M.shape[0]):
+        g = 0
+        for v in M[r]:
+            g = gcd(g, int(v))
+        if g > 1:
+            M[r] = [int(v) // g for v in M[r]]
+    R2 = 1
+    for v in vectors:
+        cleared = _rows_cleared_of_denominators([[Fraction(x) for x in v]])[0]
+        R2 = max(R2, sum(int(x) * int(x) for x in cleared))
+    return N, s, M, isqrt(R2) + 1
+
+
+def basis_transformations(kernels, settings: Optional[RoundingSettings] = None, device: int = 0, maxprimes: int = 3, batch=None, lift=None, check: bool = True,
+                          reconstruct=None, matmul=None, reduce=None, verbose: bool = False) -> dict:
+    """The reference's `basis_transformations` over QQ (src/rounding.jl:750-858).  `kernels` maps a block key to `(N, vectors)`: the size of the block and
+    its s rational kernel vectors, each of N entries (what `vectors_to_fractions(BlockKernel)` returns).  Returns `{key: (B^T, Binv, s)}`, object arrays
+    (N, N) of `Fraction`s, like the reference, in the order of `kernels`.
+
+    The unreduced branch (`settings.reduce_kernelvectors` false; src/rounding.jl:967-971, 1017-1050): the vectors become the first s columns of B,
+    `B = [V | E]` with the standard basis vectors E of `complete_basis`, `Binv = inverse_qq(B)`, and, with `settings.normalize_transformation`, row i of
+    Binv multiplied by the least common multiple of its denominators and column i of B divided by it (src/rounding.jl:844-850).  A block without kernel
+    vectors gives identities and s = 0.  The completion is tested against the inverse: an e_i that was not taken must lie in the span of V and the e_j taken
+    before it, i.e. column i of Binv is zero in the rows of the e_j taken with j > i; otherwise the prime of `complete_basis` divided a deciding minor and
+    the next prime is taken (at most `maxprimes` times, then `ArithmeticError`).
+
+    The reduced branch (`settings.reduce_kernelvectors` true, the default as in the reference, AND `reduce=` given, e.g. `reduce=reduce_kernel_vectors`;
+    src/rounding.jl:860-1104): blocks with s = 0 or s = N give identities; for the others the unreduced `[V | E]` and its inverse
+    give the integer matrix M whose kernel is the saturated lattice of the vectors, ONE call `reduce(blocks, settings, device=..., matmul=...)` for all
+    blocks returns the matrices U, and with `settings.unimodular_transform` `B = U^T`, `Binv = inverse_qq(B)`, an integer matrix (`ArithmeticError` if
+    not); without it the first s rows of U replace the vectors and the unreduced branch runs on them.  `verbose`: prints the largest entry of B after the
+    reduction, as the reference does.  With `settings.reduce_kernelvectors` true and `reduce=None` this raises `NotImplementedError`: pass `reduce=`, or
+    `RoundingSettings(reduce_kernelvectors=False)`.  Number fields of degree above 1 are not built.
+    `batch` goes to `complete_basis`; `lift`, `check`, `reconstruct`, `matmul` go to `inverse_qq`."""
     settings = RoundingSettings() if settings is None else settings
-    if settings.reduce_kernelvectors:
+    if settings.reduce_kernelvectors and reduce is None:
         raise NotImplementedError("basis_transformations: settings.reduce_kernelvectors is true, but the HNF / LLL reduction of the kernel vectors is not on "
                                   "the device yet (nor are number fields of degree above 1); pass RoundingSettings(reduce_kernelvectors=False)")
+    hooks = (settings, device, maxprimes, batch, lift, check, reconstruct, matmul)
+    kernels = {key: (int(N), [list(v) for v in vectors]) for key, (N, vectors) in kernels.items()}
+    reduced = {}
+    if settings.reduce_kernelvectors:
+        keys = [key for key, (N, vectors) in kernels.items() if 0 < len(vectors) < N]
+        blocks = [_kernel_block(kernels[key][0], kernels[key][1], _unreduced_basis(key, *kernels[key], *hooks)[1]) for key in keys]
+        reduced = dict(zip(keys, reduce(blocks, settings, device=device, matmul=matmul))) if keys else {}
     out = {}
     for key, (N, vectors) in kernels.items():
-        N, vectors = int(N), list(vectors)
         s = len(vectors)
-        B = _object_matrix(np.zeros((N, N), dtype=object), "basis_transformations", Fraction)
-        if s == 0:
+        if s == 0 or (settings.reduce_kernelvectors and s == N):
+            B = _object_matrix(np.zeros((N, N), dtype=object), "basis_transformations", Fraction)
             for i in range(N):
                 B[i, i] = Fraction(1)
-            out[key] = (B.T.copy(), B.copy(), 0)
+            out[key] = (B.T.copy(), B.copy(), s)
             continue
-        for c, v in enumerate(vectors):
-            if len(v) != N:
-                raise ValueError(f"basis_transformations: block {key!r}: vector {c} has {len(v)} entries for a block of size {N}")
-            B[:, c] = [Fraction(x) for x in v]
-        below = None
-        for _ in range(int(maxprimes)):
-            extra = complete_basis(B[:, :s], maxprimes=maxprimes, device=device, batch=batch, below=below)
-            B[:, s:] = Fraction(0)
-            for c, i in enumerate(extra):
-                B[i, s + c] = Fraction(1)
+        if key in reduced and settings.unimodular_transform:
+            U = np.asarray(reduced[key], dtype=object)
+            B = _object_matrix(U.T, "basis_transformations", Fraction)
             Binv = np.asarray(inverse_qq(B, maxprimes=maxprimes, device=device, lift=lift, check=check, reconstruct=reconstruct, matmul=matmul))
-            taken = set(extra)
-            if all(Binv[s + c, i] == 0 for i in range(N) if i not in taken for c, j in enumerate(extra) if j > i):
-                break
-            below = extra.p
+            if any(v.denominator != 1 for v in Binv.flat):
+                raise ArithmeticError(f"basis_transformations: block {key!r}: the inverse of the reduced basis change is not an integer matrix")
         else:
-            raise ArithmeticError(f"basis_transformations: block {key!r}: no prime gave the greedy completion of the kernel vectors")
-        if settings.normalize_transformation:
-            for i in range(N):
-                l = 1
-                for v in Binv[i]:
-                    l = l * v.denominator // gcd(l, v.denominator)
-                Binv[i] = [v * l for v in Binv[i]]
-                B[:, i] = [v / l for v in B[:, i]]
+            if key in reduced:
+                vectors = [[Fraction(int(x)) for x in row] for row in np.asarray(reduced[key], dtype=object)[:s]]
+            B, Binv = _unreduced_basis(key, N, vectors, *hooks)
+            if settings.normalize_transformation:
+                _normalized(B, Binv)
+        if verbose and key in reduced:
+            print(f"    After reduction, the maximum number of the basis transformation matrix is {max(abs(v) for v in B.flat)}")          # (maximum(abs.(B)), :972)
         out[key] = (B.T.copy(), Binv.copy(), s)
     return out
 
@@ -2054,7 +2300,7 @@ def _lift_by_columns(lift):
 
 
 def exact_solution(problem, result, settings: Optional[RoundingSettings] = None, limbs: Optional[int] = None, transformed: bool = False, rng=None,
-                   device: int = 0, batch=None, lift=None, reconstruct=None, matmul=None, minors=None, round_batch=None, assemble=None) -> ExactSolution:
+                   device: int = 0, batch=None, lift=None, reconstruct=None, matmul=None, minors=None, round_batch=None, assemble=None, reduce=None, verbose: bool = False) -> ExactSolution:
     """The reference's `exact_solution` over QQ (src/rounding.jl:1366-1409, 155-179) for an `ExactProblem` and a numeric solution `result` of
     `problem.to_sdp(...)` (a `SolveResult` of `solvesdp_mw`, or anything with `X`, `Y` (fp64 or planar limbs) and `y`):
 
@@ -2064,7 +2310,8 @@ def exact_solution(problem, result, settings: Optional[RoundingSettings] = None,
       `ArithmeticError` when all columns were already taken;  5. the positive-definiteness part of `is_valid_solution(..., check_slacks=False)`: `checkpd`
       of every transformed block, the certificates kept;  6. `undo_transform`, unless `transformed`.
 
-    With the default `settings.reduce_kernelvectors` `basis_transformations` raises its `NotImplementedError`, which passes through.  The hooks replace the
+    With the default `settings.reduce_kernelvectors` and `reduce=None` `basis_transformations` raises its `NotImplementedError`, which passes through;
+    `reduce=reduce_kernel_vectors` (or a stand-in) takes the reference's reduced, unimodular basis change (`verbose` goes there too).  The hooks replace the
     device calls of the steps: `round_batch` (`kernel_vectors`), `batch` (`rref_mod_p`), `lift` (the one-column hook of `solve_dixon`; the inverse of
     `basis_transformations` then takes it column by column), `reconstruct`, `matmul`, `minors` (`checkpd`), `assemble` (`linear_system`).  `rng`: the generator of `select_columns` and `project_to_affine_space`."""
     settings = RoundingSettings() if settings is None else settings
@@ -2072,7 +2319,7 @@ def exact_solution(problem, result, settings: Optional[RoundingSettings] = None,
     block_n = problem.block_n
     kernels = kernel_vectors(block_n, result, result, limbs=limbs, settings=settings, device=device, rationalize=True, round_batch=round_batch)
     Bs = basis_transformations({bi: (int(n), vectors_to_fractions(k)) for bi, (n, k) in enumerate(zip(block_n, kernels))}, settings, device=device, batch=batch,
-                               lift=None if lift is None else _lift_by_columns(lift), reconstruct=reconstruct, matmul=matmul)
+                               lift=None if lift is None else _lift_by_columns(lift), reconstruct=reconstruct, matmul=matmul, reduce=reduce, verbose=verbose)
     Y = _exact_blocks(result.Y, block_n, limbs)
     y = [sum((Fraction(float(v)) for v in np.atleast_2d(np.asarray(getattr(result, "y", np.zeros(0)), dtype=np.float64))[:, k]), Fraction(0))
          for k in range(problem.b.size)]

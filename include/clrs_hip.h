@@ -468,7 +468,25 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   decreases, (most terms of a row) min(ndu, ndw) >= 2^14, a pair with a > b or an index outside [0, n), a digit outside [-2^23, 2^23].  R, nc or T equal to
  *   0 gives zeros without touching a device; a row without terms is a row of zeros.  Every device buffer is released on every path.
  * clrs_zz_lowrank_system_times: the milliseconds of the calling thread's last clrs_zz_lowrank_system: in k_lrsys_tile, in k_lrsys_carry, and from the first
- *   upload to the last download (device events). */
+ *   upload to the last download (device events).
+ * clrs_zz_lll: LLL reduction of a batch of nb independent integer lattices (the reduction of the kernel vectors of the rounding chain,
+ *   the reference's simplify_kernelvectors / reduction_step, src/rounding.jl:860-1104), host pointers, no context.  Lattice b is given by rows[b] <= 128
+ *   independent rows of cols[b] <= 256 columns in nd <= 20 planes of balanced base-2^24 digits, [nd][rows[b]][cols[b]] row-major, little-endian, digits in
+ *   [-2^23, 2^23], the lattices packed one after the other in in_digits; out_digits has the same layout and receives the reduced rows of the lattices that
+ *   end with status 0 (nothing else of it is written).  Dot products run over the first cols_gram[b] columns only, row operations act on all columns (an
+ *   identity appended behind cols_gram columns comes back as the transformation).  One workgroup of 256 threads per lattice.  The rows change by exact
+ *   integer operations only (b_k <- b_k - X b_j with an integer X, and exchanges); the Gram-Schmidt data that choose them are floating point of `limbs` fp64
+ *   words (2, 4 or 6), size reduction to |mu| <= eta and Lovasz's test with delta.  info is [nb][8]: info[b][0] the status -- 0 reduced; 1 a cap was reached
+ *   (max_swaps exchanges, or 64 size-reduction passes at one index); 2 the arithmetic gave up (a diagonal r_kk that is not positive and finite, a non-finite
+ *   value, a pass of quotients that did not shrink the row of mu): more limbs may help, the rows may be dependent; 3 an entry left its nd digits --
+ *   info[b][1] exchanges, info[b][2] size-reduction passes, info[b][3] launches, info[b][4] the index reached.  A launch takes at most 1024 exchanges per
+ *   lattice, or clrs_config_set("lll_launch_swaps", n), then the host launches again; the result does not depend on n.  CLRS_ERR_INVALID before any device
+ *   call, outputs untouched: a negative size, more than 128 rows or 256 columns, cols_gram outside [0, cols] (or 0 for a lattice with rows), nd outside
+ *   [1, 20], limbs other than 2, 4, 6, delta outside (1/4, 1], eta outside [1/2, sqrt(delta)), max_swaps < 0, planes of 2^31 elements or more, a null
+ *   pointer, a digit outside [-2^23, 2^23].  nb == 0 touches nothing; a batch whose lattices all have 0 rows gives status 0 without touching a device.
+ *   Every device buffer is released on every path.
+ * clrs_zz_lll_times: the milliseconds of the calling thread's last clrs_zz_lll: in k_zz_lll over all launches, and from the first upload to the last
+ *   download (device events). */
 #define CLRS_MODP_MINORS_MAX_N 128
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
@@ -504,6 +522,9 @@ int clrs_modp_dixon_lift_multi_times(double *x_ms, double *gemm_ms, double *r_ms
 int clrs_zz_lowrank_system(int device, int n, int T, int R, const int32_t *rowptr, int ndu, const int32_t *U, int ndw, const int32_t *W, int nc,
                            const int32_t *col_a, const int32_t *col_b, int ndc, int32_t *C, int32_t *info);
 int clrs_zz_lowrank_system_times(double *tile_ms, double *carry_ms, double *whole_ms);
+int clrs_zz_lll(int device, int nb, const int32_t *rows, const int32_t *cols, const int32_t *cols_gram, int nd, const int32_t *in_digits, int32_t *out_digits,
+                double delta, double eta, int limbs, int max_swaps, int32_t *info);
+int clrs_zz_lll_times(double *kernel_ms, double *whole_ms);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 

@@ -860,6 +860,28 @@ function solve_dixon(A::Nemo.ZZMatrix, b::Nemo.ZZMatrix; maxprimes::Integer=3, d
     error("The system is rank-deficient")
 end
 
+"""
+    lll(A::AbstractMatrix{<:Integer}; delta=0.99, eta=0.51, limbs=6, max_swaps=typemax(Int32), device=0)
+
+An LLL-reduced basis of the lattice spanned by the (independent) rows of `A`, at most 128 rows and 256 columns, on the device (`clrs_zz_lll`, DESIGN.md
+section 22): what the reference's `reduction_step` (src/rounding.jl:1062-1104) asks of FLINT's `lll`.  Every row operation is exact; the Gram-Schmidt
+data that steer them are floating point of `limbs` fp64 words (2, 4 or 6).  Returns a `Matrix{BigInt}`; throws when the reduction ends with a status other
+than 0 (1: a cap was reached, 2: the arithmetic gave up -- take more limbs, 3: an entry left its digits).
+"""
+function lll(A::AbstractMatrix{<:Integer}; delta::Real=0.99, eta::Real=0.51, limbs::Integer=6, max_swaps::Integer=typemax(Int32), device::Integer=0)
+    d, c = size(A)
+    (d == 0 || c == 0) && return Matrix{BigInt}(undef, d, c)
+    vals = BigInt[BigInt(A[i, j]) for i in 1:d for j in 1:c]               # row-major
+    nd = digits_needed(maximum(abs, vals) << 40)                            # 40 bits of headroom for the row operations
+    digits = balanced_digits(vals, nd)                                      # planar: digit l of entry e at digits[e, l]
+    out = zeros(Int32, d * c, nd); info = zeros(Int32, 8)
+    check(ccall((:clrs_zz_lll, libclrs[]), Cint,
+                (Cint, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Cint, Ptr{Int32}, Ptr{Int32}, Cdouble, Cdouble, Cint, Cint, Ptr{Int32}),
+                device, 1, Int32[d], Int32[c], Int32[c], nd, digits, out, Float64(delta), Float64(eta), limbs, max_swaps, info))
+    info[1] == 0 || error("lll: the reduction ended with status $(info[1]) after $(info[2]) exchanges")
+    return BigInt[from_balanced_digits(out, (i - 1) * c + j) for i in 1:d, j in 1:c]
+end
+
 # `ClusteredLowRankHIP.Optimizer`: the MOI optimizer type lives in the package extension (ext/ClusteredLowRankHIPMOIExt.jl, loaded with
 # MathOptInterface), which registers it here; JuMP takes any callable that returns an optimizer: `GenericModel{BigFloat}(ClusteredLowRankHIP.Optimizer)`
 const OPTIMIZER_TYPE = Ref{Any}(nothing)
