@@ -171,6 +171,10 @@ SYMBOLS = {
     "clrs_zz_lowrank_system_times": (C.c_int, [p_d, p_d, p_d]),
     "clrs_zz_lll": (C.c_int, [C.c_int, C.c_int, p_i32, p_i32, p_i32, C.c_int, p_i32, p_i32, C.c_double, C.c_double, C.c_int, C.c_int, p_i32]),
     "clrs_zz_lll_times": (C.c_int, [p_d, p_d]),
+    "clrs_mw_field_round": (C.c_int, [C.c_int, C.c_int, C.c_int, p_d, C.c_int, p_d, C.c_int, C.c_int, C.c_double, C.c_int, p_i32, p_i32, p_i32, p_d, p_d, p_i32]),
+    "clrs_mw_field_round_times": (C.c_int, [p_d, p_d]),
+    "clrs_mw_kernel_vectors_field": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i32, p_d, p_d, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, p_d, C.c_int,
+                                               C.c_int, p_i32, p_i32, p_i32, p_i32, p_d, p_d, p_d, p_d, p_i32, p_i32, p_i32, p_d, p_d, p_i32, p_d]),
     "clrs_mw_schur_solve": (C.c_int, [C.c_void_p, p_d, p_d, p_d, p_d]),
     "clrs_mw_cholesky_blocks_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "clrs_mw_sync_status_cholesky": (C.c_int, [C.c_void_p]),
@@ -243,12 +247,15 @@ _UNITS = (
     # of the exact product and the multi-word arithmetic
     ("clrs_zz_lll.o", "clrs_zz_lll.hip", ("-ffp-contract=off",), lambda f: f.startswith("clrs_zz_lll") or f in ("clrs_modp_zz_arith.h", "clrs_mw_arith.h")),
     # the multi-word (extended precision) path: error-free transformations must not be contracted into FMAs
-    ("clrs_mw.o", "clrs_mw.hip", ("-ffp-contract=off", "-DMW_SPLIT_UNITS"), lambda f: f.startswith("clrs_mw")),
+    # the rounding to a number field by integer relations (clrs_mw_field_round): one lane per number; it reads the arithmetic of the LLL unit
+    ("clrs_mw_field_round.o", "clrs_mw_field_round.hip", ("-ffp-contract=off",),
+     lambda f: f.startswith("clrs_mw_field_round") or f in ("clrs_zz_lll_arith.h", "clrs_modp_zz_arith.h", "clrs_mw_arith.h")),
+    ("clrs_mw.o", "clrs_mw.hip", ("-ffp-contract=off", "-DMW_SPLIT_UNITS"), lambda f: f.startswith("clrs_mw") and not f.startswith("clrs_mw_field_round")),
     # the device code of the larger limb counts, one unit each (explicit instantiations: clrs_mw_inst.h), compiled side by side
     *((f"clrs_mw_k{k}.o", "clrs_mw_inst.hip", ("-ffp-contract=off", f"-DMW_INST_K={k}"),
-       lambda f: f.startswith("clrs_mw") and f not in ("clrs_mw.hip", "clrs_mw_ipm_host.inc", "clrs_mw_tables.h")) for k in (4, 5, 6)),
+       lambda f: f.startswith("clrs_mw") and not f.startswith("clrs_mw_field_round") and f not in ("clrs_mw.hip", "clrs_mw_ipm_host.inc", "clrs_mw_tables.h")) for k in (4, 5, 6)),
     *((f"clrs_mw_k{k}p{part}.o", "clrs_mw_inst.hip", ("-ffp-contract=off", f"-DMW_INST_K={k}", f"-DMW_INST_PART={part}"),
-       lambda f: f.startswith("clrs_mw") and f not in ("clrs_mw.hip", "clrs_mw_ipm_host.inc", "clrs_mw_tables.h")) for k in (8, 10) for part in (1, 2, 3, 4)),
+       lambda f: f.startswith("clrs_mw") and not f.startswith("clrs_mw_field_round") and f not in ("clrs_mw.hip", "clrs_mw_ipm_host.inc", "clrs_mw_tables.h")) for k in (8, 10) for part in (1, 2, 3, 4)),
 )
 _COMMON = ("--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value")
 

@@ -78,6 +78,7 @@ int g_cfg_zz_gemm_chunk_bytes = 0;     // clrs_zz_gemm: the (lo, hi) buffer of a
 int g_cfg_liftm_chunk_bytes = 0;       // clrs_modp_dixon_lift_multi: the buffers of a chunk of columns stay below this many bytes; 0: the 256 MiB of clrs_modp_liftm.hip.h (a small value makes a call take several chunks: for the tests)
 int g_cfg_lrsys_chunk_bytes = 0;       // clrs_zz_lowrank_system: the int64 sums of a chunk of rows stay below this many bytes; 0: the 256 MiB of clrs_modp_lrsys.hip.h (a small value makes a call take several chunks: for the tests)
 int g_cfg_lll_launch_swaps = 0;        // clrs_zz_lll: a launch of k_zz_lll takes at most this many exchanges per lattice, then the host launches again; 0: the 1024 of clrs_zz_lll.hip (a small value cuts a reduction into many launches: for the tests)
+int g_cfg_field_round_launch_rungs = 0;  // clrs_mw_field_round: a launch of k_mw_field_round advances a number by at most this many rungs, then the host launches again; 0: the 16 of clrs_mw_field_round_arith.h (the result does not depend on it)
 int g_cfg_mw_zi_narrow = 1;          // multi-word interior-point iteration: k_mwi_Zi in workgroups of 256 threads (one wave per SIMD) with panels of half the width where the launch keeps a compute unit per workgroup (clrs_mw_zi_panels.h) -- 0: always 512 threads; read when the context is created
 int g_cfg_mw_xinv_product = 1;        // multi-word interior-point iteration: X^-1 = Xi^T Xi formed once per iteration on the side stream (k_mwi_Xv) and applied by k_mwi_Zi as ONE product -- 0: Xi^T (Xi M), two triangular products per launch; read when the context is created
 int g_cfg_mw_chain_hop = 1;           // multi-word interior-point iteration: the "last workgroup continues" hand-offs of k_mwi_Zi and k_mwi_step (MwIpmDev::hop) -- 0: release fences (mwk::wg_last_block), 1: write-through stores, a drain and one lane's acquire, 2: write-through stores and loads, no fence; read when the iteration is created
@@ -1389,6 +1390,7 @@ extern "C" int clrs_config_set(const char *key, int value) {
     if (!std::strcmp(key, "liftm_chunk_bytes")) { g_cfg_liftm_chunk_bytes = value < 0 ? 0 : value; return 0; }
     if (!std::strcmp(key, "lrsys_chunk_bytes")) { g_cfg_lrsys_chunk_bytes = value < 0 ? 0 : value; return 0; }
     if (!std::strcmp(key, "lll_launch_swaps")) { g_cfg_lll_launch_swaps = value < 0 ? 0 : value; return 0; }
+    if (!std::strcmp(key, "field_round_launch_rungs")) { g_cfg_field_round_launch_rungs = value < 0 ? 0 : value; return 0; }
     if (!std::strcmp(key, "mw_xinv_product")) { g_cfg_mw_xinv_product = value; return 0; }
     if (!std::strcmp(key, "mw_chain_hop")) { g_cfg_mw_chain_hop = value; return 0; }
     if (!std::strcmp(key, "mw_skip_xfb")) { g_cfg_mw_skip_xfb = value; return 0; }

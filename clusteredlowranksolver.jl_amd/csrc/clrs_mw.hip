@@ -1741,16 +1741,52 @@ struct MwKvRational {
     double *Vq, *resid_max;
 };
 
-// both entries: clrs_mw_kernel_vectors (rat == nullptr) and clrs_mw_kernel_vectors_rational
+// the arguments and outputs of the rounding to a number field (clrs_mw_field_round.hip); rel, status, rung, err, info and Vq are pools over
+// the plane like V: only the positions of the vectors' entries are written
+struct MwKvField {
+    int deg;
+    const double *gpow;
+    int bits;
+    double errbound;
+    int nd;
+    int32_t *rel, *status, *rung;
+    double *err, *Vq;
+    int32_t *info;
+    double *resid_max;
+};
+// clrs_mw_field_round.hip: the device part of clrs_mw_field_round on compact device pools
+int mw_field_round_on_device(int limbs, int deg, const double *gpow, int count, const double *d_v, int bits, double errbound, int nd, int32_t *d_rel,
+                             int32_t *d_status, int32_t *d_rung, double *d_err, double *d_vq, int32_t *d_info, double *kernel_ms);
+
+// the entries of the vectors, gathered into a compact pool [limbs][count] and spread back over the plane
+static __global__ void k_mw_kv_gather(const double *__restrict__ V, mwi64 plane, const mwi64 *__restrict__ idx, int count, int limbs, double *__restrict__ out) {
+    const mwi64 i = (mwi64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const mwi64 o = idx[i];
+    if (o < 0 || o >= plane) return;
+    for (int l = 0; l < limbs; l++) out[(mwi64)l * count + i] = V[(mwi64)l * plane + o];
+}
+static __global__ void k_mw_kv_spread(const double *__restrict__ in, const mwi64 *__restrict__ idx, int count, int limbs, double *__restrict__ Vq, mwi64 plane) {
+    const mwi64 i = (mwi64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const mwi64 o = idx[i];
+    if (o < 0 || o >= plane) return;
+    for (int l = 0; l < limbs; l++) Vq[(mwi64)l * plane + o] = in[(mwi64)l * count + i];
+}
+
+// the three entries: clrs_mw_kernel_vectors (rat == fld == nullptr), clrs_mw_kernel_vectors_rational (rat) and clrs_mw_kernel_vectors_field (fld)
 static int mw_kernel_vectors_run(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual,
                                  double dual_max, int32_t *branch, int32_t *perm, int32_t *rank, int32_t *count, double *V, double *resid_max, double *v_max,
-                                 double *pivot_resid, const MwKvRational *rat) {
+                                 double *pivot_resid, const MwKvRational *rat, const MwKvField *fld = nullptr) {
     if (limbs != 4 && limbs != 5 && limbs != 6 && limbs != 8 && limbs != 10) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: limbs must be 4, 5, 6, 8 or 10");
     if (nblk < 0 || plane < 0) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: negative block count or plane length");
     if (!(tau > 0.0)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: tau must be positive");
     if (nblk > 0 && (!n || !X || !Y || !branch || !perm || !rank || !count || !V || !resid_max || !v_max || !pivot_resid)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: null argument");
     if (rat && !(rat->errbound > 0.0)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: round_errbound must be positive");
     if (rat && nblk > 0 && (!rat->num || !rat->den || !rat->status || !rat->Vq || !rat->resid_max)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: null argument");
+    if (fld && !(fld->errbound > 0.0)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: round_errbound must be positive");
+    if (fld && (fld->deg < 2 || fld->deg > 4 || fld->bits < 1 || fld->nd < 1 || fld->nd > 20)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: the degree must lie in [2, 4], bits >= 1 and nd in [1, 20]");
+    if (fld && nblk > 0 && (!fld->gpow || !fld->rel || !fld->status || !fld->rung || !fld->err || !fld->Vq || !fld->info || !fld->resid_max)) return mw_fail(CLRS_ERR_INVALID, "kernel vectors: null argument");
     std::vector<MwRankMat> mats(nblk);
     std::vector<MwKvBlk> blks(nblk);
     i64 glen = 0, xlen = 0;
@@ -1793,6 +1829,12 @@ static int mw_kernel_vectors_run(int device, int limbs, int nblk, const int32_t 
     double *d_num = nullptr, *d_den = nullptr, *d_Vq = nullptr, *d_rmax2 = nullptr, *d_vmax2 = nullptr;
     int *d_status = nullptr;
     mwi64 *d_idx = nullptr;
+    if (fld) {
+        MWCHECK(bufs.get(&d_Vq, pool)); MWCHECK(bufs.get(&d_rmax2, (size_t)xlen)); MWCHECK(bufs.get(&d_vmax2, (size_t)xlen));
+        MWCHECK(hipMemcpy(d_Vq, fld->Vq, pool * sizeof(double), hipMemcpyHostToDevice));
+        MWCHECK(hipMemset(d_rmax2, 0, std::max<size_t>(xlen, 1) * sizeof(double)));
+        MWCHECK(hipMemset(d_vmax2, 0, std::max<size_t>(xlen, 1) * sizeof(double)));
+    }
     if (rat) {
         MWCHECK(bufs.get(&d_num, (size_t)plane)); MWCHECK(bufs.get(&d_den, (size_t)plane)); MWCHECK(bufs.get(&d_status, (size_t)plane)); MWCHECK(bufs.get(&d_Vq, pool));
         MWCHECK(bufs.get(&d_rmax2, (size_t)xlen)); MWCHECK(bufs.get(&d_vmax2, (size_t)xlen));
@@ -1820,7 +1862,7 @@ static int mw_kernel_vectors_run(int device, int limbs, int nblk, const int32_t 
         blks[b].rank = r;
         blks[b].count = count[b] = blks[b].branch == MW_KV_DUAL ? r : nb - r;
         if (count[b] == 0) continue;
-        if (rat) for (i64 e = 0; e < (i64)nb * count[b]; e++) idx.push_back(blks[b].off + e);
+        if (rat || fld) for (i64 e = 0; e < (i64)nb * count[b]; e++) idx.push_back(blks[b].off + e);
         const int t = (int)jobs.size();
         jobs.push_back(MwGemmJob{nb, count[b], nb, 0, 0, 1, 0, nb, nb, nb, blks[b].off, blks[b].off, blks[b].off});
         for (int tj = 0; tj < (count[b] + MW_GEMM_T - 1) / MW_GEMM_T; tj++)
@@ -1860,6 +1902,50 @@ static int mw_kernel_vectors_run(int device, int limbs, int nblk, const int32_t 
             hipLaunchKernelGGL(k_mw_kv_colmax, dim3((unsigned)nblk), dim3(MW_NT), 0, nullptr, d_blks, d_R, d_Vq, d_rmax2, d_vmax2);
             MWCHECK(hipGetLastError());
         }
+        if (fld) {
+            // every entry of every vector rounded to the field (one lane each, on a compact pool), the elements spread back into Vq, then the second check as above
+            const int m = (int)idx.size(), D = fld->deg + 1;
+            double *d_vc = nullptr, *d_vqc = nullptr, *d_errc = nullptr;
+            int32_t *d_relc = nullptr, *d_statc = nullptr, *d_rungc = nullptr, *d_infoc = nullptr;
+            MWCHECK(bufs.get(&d_idx, idx.size())); MWCHECK(bufs.get(&d_vc, (size_t)limbs * m)); MWCHECK(bufs.get(&d_vqc, (size_t)limbs * m));
+            MWCHECK(bufs.get(&d_errc, (size_t)m)); MWCHECK(bufs.get(&d_relc, (size_t)fld->nd * D * m)); MWCHECK(bufs.get(&d_statc, (size_t)m));
+            MWCHECK(bufs.get(&d_rungc, (size_t)m)); MWCHECK(bufs.get(&d_infoc, (size_t)2 * m));
+            MWCHECK(hipMemcpy(d_idx, idx.data(), idx.size() * sizeof(mwi64), hipMemcpyHostToDevice));
+            const unsigned ggrid = (unsigned)((idx.size() + MW_NT - 1) / MW_NT);
+            hipLaunchKernelGGL(k_mw_kv_gather, dim3(ggrid), dim3(MW_NT), 0, nullptr, d_V, (mwi64)plane, d_idx, m, limbs, d_vc);
+            MWCHECK(hipGetLastError());
+            double kernel_ms = 0.0;
+            rc = mw_field_round_on_device(limbs, fld->deg, fld->gpow, m, d_vc, fld->bits, fld->errbound, fld->nd, d_relc, d_statc, d_rungc, d_errc, d_vqc, d_infoc, &kernel_ms);
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_mw_kv_spread, dim3(ggrid), dim3(MW_NT), 0, nullptr, d_vqc, d_idx, m, limbs, d_Vq, (mwi64)plane);
+#define MW_KV_CASE(Kc)                                                                                                                                            \
+    case Kc:                                                                                                                                                      \
+        hipLaunchKernelGGL(k_mw_gemm<Kc>, dim3(grid), dim3(MW_NT), MW_GEMM_LDS(Kc), nullptr, d_jobs, d_tiles, d_Y, (mwi64)plane, d_Vq, (mwi64)plane, d_R,         \
+                           (mwi64)plane);                                                                                                                         \
+        break;
+            switch (limbs) { MW_KV_CASE(4) MW_KV_CASE(5) MW_KV_CASE(6) MW_KV_CASE(8) MW_KV_CASE(10) }
+#undef MW_KV_CASE
+            hipLaunchKernelGGL(k_mw_kv_colmax, dim3((unsigned)nblk), dim3(MW_NT), 0, nullptr, d_blks, d_R, d_Vq, d_rmax2, d_vmax2);
+            MWCHECK(hipGetLastError());
+            MWCHECK(hipStreamSynchronize(nullptr));
+            std::vector<int32_t> h_rel((size_t)fld->nd * D * m), h_stat((size_t)m), h_rung((size_t)m), h_info((size_t)2 * m);
+            std::vector<double> h_err((size_t)m);
+            MWCHECK(hipMemcpy(h_rel.data(), d_relc, h_rel.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            MWCHECK(hipMemcpy(h_stat.data(), d_statc, h_stat.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            MWCHECK(hipMemcpy(h_rung.data(), d_rungc, h_rung.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            MWCHECK(hipMemcpy(h_info.data(), d_infoc, h_info.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            MWCHECK(hipMemcpy(h_err.data(), d_errc, h_err.size() * sizeof(double), hipMemcpyDeviceToHost));
+            for (int i = 0; i < m; i++) {
+                const i64 o = idx[(size_t)i];
+                for (int r = 0; r < fld->nd * D; r++) fld->rel[(i64)r * plane + o] = h_rel[(size_t)r * m + i];
+                fld->status[o] = h_stat[(size_t)i];
+                fld->rung[o] = h_rung[(size_t)i];
+                fld->err[o] = h_err[(size_t)i];
+                fld->info[o] = h_info[(size_t)i];
+                fld->info[(i64)plane + o] = h_info[(size_t)m + i];
+            }
+            MWCHECK(hipMemcpy(fld->Vq, d_Vq, pool * sizeof(double), hipMemcpyDeviceToHost));
+        }
         MWCHECK(hipStreamSynchronize(nullptr));
         MWCHECK(hipMemcpy(V, d_V, pool * sizeof(double), hipMemcpyDeviceToHost));
         if (rat) {
@@ -1870,6 +1956,7 @@ static int mw_kernel_vectors_run(int device, int limbs, int nblk, const int32_t 
         }
     }
     if (rat) MWCHECK(hipMemcpy(rat->resid_max, d_rmax2, (size_t)xlen * sizeof(double), hipMemcpyDeviceToHost));
+    if (fld) MWCHECK(hipMemcpy(fld->resid_max, d_rmax2, (size_t)xlen * sizeof(double), hipMemcpyDeviceToHost));
     MWCHECK(hipMemcpy(resid_max, d_rmax, (size_t)xlen * sizeof(double), hipMemcpyDeviceToHost));
     MWCHECK(hipMemcpy(v_max, d_vmax, (size_t)xlen * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
@@ -1887,6 +1974,14 @@ extern "C" int clrs_mw_kernel_vectors_rational(int device, int limbs, int nblk, 
                                                int32_t *status, double *Vq, double *round_resid_max) {
     const MwKvRational rat{round_errbound, num, den, status, Vq, round_resid_max};
     return mw_kernel_vectors_run(device, limbs, nblk, n, X, Y, plane, tau, use_dual, dual_max, branch, perm, rank, count, V, resid_max, v_max, pivot_resid, &rat);
+}
+
+extern "C" int clrs_mw_kernel_vectors_field(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual,
+                                            double dual_max, double round_errbound, int deg, const double *gpow, int bits, int nd, int32_t *branch, int32_t *perm,
+                                            int32_t *rank, int32_t *count, double *V, double *resid_max, double *v_max, double *pivot_resid, int32_t *rel,
+                                            int32_t *status, int32_t *rung, double *err, double *Vq, int32_t *info, double *round_resid_max) {
+    const MwKvField fld{deg, gpow, bits, round_errbound, nd, rel, status, rung, err, Vq, info, round_resid_max};
+    return mw_kernel_vectors_run(device, limbs, nblk, n, X, Y, plane, tau, use_dual, dual_max, branch, perm, rank, count, V, resid_max, v_max, pivot_resid, nullptr, &fld);
 }
 
 // ---- rounding to rationals (clrs_mw_rational.hip.h): no context, host pointers.  The device pool is compact (plane = count), so nothing behind the first

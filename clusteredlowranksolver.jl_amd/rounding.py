@@ -35,8 +35,13 @@ the device (clrs_modp_dixon_lift_multi): `dixon_lift_multi
 The reference's reduced branch (`simplify_kernelvectors`, `reduction_step`, `basis_nullspace_remaining`, src/rounding.jl:860-1104: an LLL-reduced Z-basis of the
 saturated lattice of the kernel vectors and a unimodular basis change) is an LLL reduction of one embedded lattice per block, a batch on the device
 (clrs_zz_lll): `lll_batch`, `lll`, `reduce_kernel_vectors`, and `basis_transformations(..., reduce=reduce_kernel_vectors)`.  It is
-taken only when `reduce=` is given: without it the default settings still raise `NotImplementedError`.  Not built: number fields of degree above 1, the
-reference's `kernel_lll`, and its partial-column heuristic above `reduce_kernelvectors_cutoff`.
+taken only when `reduce=` is given: without it the default settings still raise `NotImplementedError`.  Not built: the reference's `kernel_lll` and its
+partial-column heuristic above `reduce_kernelvectors_cutoff`.
+
+Over a number field QQ(g) of degree 2 .. 4 the entries of the kernel vectors are rounded by integer relations on the device (src/rounding.jl:481-534: roundx(x, g, deg)
+-> clindep -> lindep; clrs_mw_field_round): `NumberField`, `round_to_field`, `field_relations_lll` (the same contract through clrs_zz_lll: the
+rescue, degrees 5 .. 8), `kernel_vectors(..., rationalize=True, field=...)`, `vectors_to_field`.  The steps after the rounding -- basis change, system and PD check
+over the field -- are not built.
 
 The system the projection solves is assembled from an `ExactProblem` (the problem over QQ; `to_sdp` gives the numeric one) by `linear_system`
 (`partial_linearsystem`, src/interface.jl:1354-1535): per low-rank block one call of clrs_zz_lowrank_system, a row-wise Gram of long
@@ -60,7 +65,8 @@ __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vecto
            "PDCertificate", "checkpd", "is_valid_solution", "ints_to_planes", "planes_to_ints", "zz_matmul", "dixon_lift_multi", "DixonSolutionMatrix",
            "solve_dixon_multi", "inverse_qq", "complete_basis", "basis_transformations", "transform", "undo_transform", "lowrank_system", "ExactLowRank", "ExactBlock",
            "ExactProblem", "ExactSolution", "system_index", "linear_system", "select_columns", "vectorize_solution", "get_rational_system", "exact_solution",
-           "ReductionError", "lll_first_rung", "lll_batch", "lll", "kernel_lattice", "reduce_kernel_vectors"]
+           "ReductionError", "lll_first_rung", "lll_batch", "lll", "kernel_lattice", "reduce_kernel_vectors", "NumberField", "FieldRounding", "round_to_field",
+           "field_relations_lll", "kernel_vectors_field_batch", "vectors_to_field"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -73,6 +79,7 @@ class RoundingSettings:
     kernel_errbound: float = 1e-10          # pivots / residuals below this are zero
     kernel_round_errbound: float = 1e-15    # the dual block is used while max |X_b| <= 1 / sqrt(this)
     kernel_use_dual: bool = True
+    kernel_bits: int = 1000                 # the relation of an entry with the powers of the field's generator is searched up to this many bits (src/rounding.jl:7); not read over QQ
     pseudo: bool = True                     # solve through the pseudoinverse of a few more columns than rows (src/rounding.jl:23, 213)
     pseudo_columnfactor: float = 1.05       # that many columns per row; at least 1 (src/rounding.jl:60-62)
     extracolumns_linindep: bool = False     # take the extra columns linearly independent of each other instead of at random
@@ -112,6 +119,8 @@ class BlockKernel:
     round_status: Optional[np.ndarray] = None
     vectors_rounded: Optional[np.ndarray] = None
     round_resid_max: Optional[np.ndarray] = None
+    coeffs: Optional[np.ndarray] = None          # with `field=` of degree deg >= 2: (n, count, deg) `Fraction`s, entry = sum_k coeffs[.., k] g^k (num / den stay None)
+    round_rung: Optional[np.ndarray] = None      # with `field=`: (n, count), the bits of the rung an entry was accepted at
 
     @property
     def max_num(self) -> int:
@@ -217,7 +226,7 @@ def _planes(a, limbs, length, what):
 
 
 def kernel_vectors(sdp_or_block_n, dualsol, primalsol=None, limbs: Optional[int] = None, settings: Optional[RoundingSettings] = None, device: int = 0,
-                   check_dimensions: bool = False, batch=None, rationalize: bool = False, round_batch=None) -> List[BlockKernel]:
+                   check_dimensions: bool = False, batch=None, rationalize: bool = False, round_batch=None, field=None) -> List[BlockKernel]:
     """The kernel vectors of every PSD block of a solution: `dualsol.X` are the dual blocks, `primalsol.Y` the primal blocks (a `SolveResult` of
     `solvesdp_mw`, or anything with those attributes, fp64 or planar limbs; `primalsol=None`: both from `dualsol`).  `sdp_or_block_n`: the problem (a
     `ClusteredLowRankSDP` or `FlatSDP`) or the block sizes in block order.  `limbs`: 4, 5, 6, 8 or 10 (default: the planes of the solution, 5 for fp64).
@@ -227,10 +236,14 @@ def kernel_vectors(sdp_or_block_n, dualsol, primalsol=None, limbs: Optional[int]
     `rationalize`: also round every entry to the rationals with `settings.kernel_round_errbound` (the same device call: `round_batch`, default
     `kernel_vectors_rational_batch`) and fill `num`, `den`, `round_status`, `vectors_rounded`, `round_resid_max` of every block.  Raises `KernelVectorError`
     "clindep failed to find a relation" (src/rounding.jl:508) where an entry has no relation, and "wrong vector detected" where max |Y_b vq| of a rounded
-    vector is above `kernel_errbound` (src/rounding.jl:630-639)."""
+    vector is above `kernel_errbound` (src/rounding.jl:630-639).
+    `field`: a `NumberField`; of degree >= 2 (with `rationalize`) every entry is rounded to it by an integer relation searched up to `settings.kernel_bits`
+    bits (`round_batch`, default `kernel_vectors_field_batch`): `coeffs`, `round_status`, `round_rung`, `vectors_rounded`,
+    `round_resid_max` are filled, `num` / `den` stay None, and the same two errors are raised.  None, or degree 1: the path over QQ, untouched."""
     settings = RoundingSettings() if settings is None else settings
     batch = kernel_vectors_batch if batch is None else batch
-    round_batch = kernel_vectors_rational_batch if round_batch is None else round_batch
+    over_field = field is not None and field.degree >= 2
+    round_batch = (kernel_vectors_field_batch if over_field else kernel_vectors_rational_batch) if round_batch is None else round_batch
     if hasattr(sdp_or_block_n, "block_n"):
         block_n = sdp_or_block_n.block_n
     elif hasattr(sdp_or_block_n, "blocks"):
@@ -251,7 +264,10 @@ def kernel_vectors(sdp_or_block_n, dualsol, primalsol=None, limbs: Optional[int]
     off = np.concatenate([[0], np.cumsum(block_n.astype(np.int64) ** 2)])
     X, Y = _planes(dualsol.X, limbs, int(off[-1]), "X"), _planes(primalsol.Y, limbs, int(off[-1]), "Y")
     tau, dual_max = float(settings.kernel_errbound), 1.0 / float(np.sqrt(settings.kernel_round_errbound))
-    if rationalize:
+    if rationalize and over_field:
+        out = round_batch(block_n, X, Y, limbs, tau, bool(settings.kernel_use_dual), dual_max, float(settings.kernel_round_errbound), field=field,
+                          bits=int(settings.kernel_bits), device=device)
+    elif rationalize:
         out = round_batch(block_n, X, Y, limbs, tau, bool(settings.kernel_use_dual), dual_max, float(settings.kernel_round_errbound), device=device)
     else:
         out = batch(block_n, X, Y, limbs, tau, bool(settings.kernel_use_dual), dual_max, device=device)
@@ -1850,6 +1866,9 @@ def basis_transformations(kernels, settings: Optional[RoundingSettings] = None, 
     `RoundingSettings(reduce_kernelvectors=False)`.  Number fields of degree above 1 are not built.
     `batch` goes to `complete_basis`; `lift`, `check`, `reconstruct`, `matmul` go to `inverse_qq`."""
     settings = RoundingSettings() if settings is None else settings
+    if any(isinstance(x, tuple) for _, vectors in kernels.values() for v in vectors for x in v):
+        raise NotImplementedError("basis_transformations: the kernel vectors hold coefficient tuples over a number field (vectors_to_field); the basis change "
+                                  "over a field of degree above 1 -- the inverse of [V | E] over QQ(g) -- is not built yet, only the rounding of the vectors is")
     if settings.reduce_kernelvectors and reduce is None:
         raise NotImplementedError("basis_transformations: settings.reduce_kernelvectors is true, but the HNF / LLL reduction of the kernel vectors is not on "
                                   "the device yet (nor are number fields of degree above 1); pass RoundingSettings(reduce_kernelvectors=False)")
@@ -2356,3 +2375,295 @@ def exact_solution(problem, result, settings: Optional[RoundingSettings] = None,
     for (j, l), M in zip(((j, l) for j, cl in enumerate(problem.blocks) for l in range(len(cl))), full):
         objective_value += sum((problem.C[j][l][a, b] * M[a, b] for a in range(M.shape[0]) for b in range(M.shape[0]) if M[a, b] != 0), Fraction(0))
     return ExactSolution(success, [sol_t[bi] for bi in sorted(sol_t)] if transformed else full, free, objective_value, bool(correct_slacks), certificates, Bs)
+
+
+# ---- rounding to a number field of degree above 1: integer relations (src/rounding.jl:481-534, 623-628; clrs_mw_field_round) ----------------
+FIELD_KERNEL_DEGREES = (2, 3, 4)     # what k_mw_field_round is instantiated for
+FIELD_LLL_MAX_DEGREE = 8             # `field_relations_lll` goes further, through clrs_zz_lll
+FIELD_FOUND, FIELD_EXHAUSTED, FIELD_NOT_FINITE, FIELD_STEER, FIELD_OVERFLOW, FIELD_NO_FIELD = range(6)
+
+
+def field_top_bits(bits: int, limbs: int) -> int:
+    """the top rung of the ladder 1, 6, 11, ..: min(bits, 53 limbs - 16) rounded down onto it"""
+    return 1 + 5 * ((min(int(bits), 53 * int(limbs) - 16) - 1) // 5)
+
+
+class NumberField:
+    """QQ(g): `minpoly` the integer coefficients of a polynomial with root g, low to high; `g` an mpmath number (taken at `prec` bits, default the current
+    mpmath precision) or its limbs (a 1-d fp64 array, `prec` = 53 per limb).  Refuses a `g` with |minpoly(g)| above 2^(8 - prec) sum_k |c_k| |g|^k."""
+
+    def __init__(self, minpoly, g, prec: Optional[int] = None):
+        import mpmath as mp
+        self.minpoly = [int(c) for c in minpoly]
+        if len(self.minpoly) < 2 or self.minpoly[-1] == 0 or any(int(c) != c for c in minpoly):
+            raise ValueError("NumberField: minpoly must hold the integer coefficients of a polynomial of degree >= 1, low to high")
+        if isinstance(g, (np.ndarray, list, tuple)):
+            limbs = np.asarray(g, dtype=np.float64).reshape(-1)
+            self.prec = 53 * limbs.size if prec is None else int(prec)
+            with mp.workprec(64 * limbs.size + 1200):
+                self.g = mp.fsum(mp.mpf(float(x)) for x in limbs)
+        else:
+            self.prec = int(mp.mp.prec if prec is None else prec)
+            self.g = mp.mpf(g)
+        if self.residual() > mp.ldexp(1, 8 - self.prec):
+            raise ValueError(f"NumberField: |minpoly(g)| is {mp.nstr(self.residual(), 3)} of its terms, not below 2^{8 - self.prec}: g is no root at {self.prec} bits")
+
+    @property
+    def degree(self) -> int:
+        return len(self.minpoly) - 1
+
+    def residual(self):
+        """|minpoly(g)| / sum_k |c_k| |g|^k"""
+        import mpmath as mp
+        with mp.workprec(self.prec + 64):
+            terms = [c * self.g ** k for k, c in enumerate(self.minpoly)]
+            return abs(mp.fsum(terms)) / mp.fsum(abs(t) for t in terms)
+
+    def power_values(self, count: Optional[int] = None, prec: Optional[int] = None):
+        import mpmath as mp
+        with mp.workprec((self.prec if prec is None else prec) + 64):
+            return [self.g ** k for k in range(self.degree if count is None else count)]
+
+    def powers(self, limbs: int) -> np.ndarray:
+        """g^0 .. g^(degree - 1) as planar limbs (limbs, degree), what clrs_mw_field_round takes; refuses a g not known to the 53 limbs - 16 bits of the ladder"""
+        import mpmath as mp
+        from .mw import to_limbs
+        need = 53 * int(limbs) - 16
+        if self.prec < need or self.residual() > mp.ldexp(1, 8 - need):
+            raise ValueError(f"NumberField.powers: g is a root to {self.prec} bits, {limbs} limbs need {need}")
+        return np.ascontiguousarray(to_limbs(self.power_values(prec=64 * int(limbs) + 64), int(limbs)))
+
+
+@dataclasses.dataclass
+class FieldRounding:
+    """What `round_to_field` returns.  `coeffs` (count, deg) object: x_k = -a_{k+1} / a_0 as `Fraction`s where `status` is 0, else None; `rel` (count, deg + 1)
+    Python integers, the relation a (zeros unless status is 0 or 5); `status` (count,): 0 found, 1 ladder exhausted, 2 not finite, 3 steering failed or a cap
+    was hit, 4 an entry left its digits, 5 a_0 = 0; `rung`: the bits of the rung a number ended at; `err`: |sum a_i u_i| there; `vq` planar (limbs, count): the
+    element in limbs; `exchanges`, `rungs` (count,): the counters of the kernel; `path` (count,): 0 the kernel, 1 `field_relations_lll`."""
+    coeffs: np.ndarray
+    rel: np.ndarray
+    status: np.ndarray
+    rung: np.ndarray
+    err: np.ndarray
+    vq: np.ndarray
+    exchanges: np.ndarray
+    rungs: np.ndarray
+    path: np.ndarray
+
+
+def _field_round_call_device(limbs, deg, gpow, count, v, plane, bits, errbound, nd, device=0):
+    """one call of clrs_mw_field_round: returns (rel (nd, deg + 1, plane) int32, status, rung, err, vq (limbs, plane), info (2, plane))"""
+    D = deg + 1
+    rel, status, rung = np.zeros((nd, D, max(plane, 1)), np.int32), np.zeros(max(plane, 1), np.int32), np.zeros(max(plane, 1), np.int32)
+    err, vq, info = np.zeros(max(plane, 1)), np.zeros((limbs, max(plane, 1))), np.zeros((2, max(plane, 1)), np.int32)
+    pi, pd = (lambda a: a.ctypes.data_as(_lib.p_i32)), (lambda a: a.ctypes.data_as(_lib.p_d))
+    _lib.check(_lib.load().clrs_mw_field_round(int(device), int(limbs), int(deg), pd(gpow), int(count), pd(v), int(plane), int(bits), float(errbound), int(nd),
+                                               pi(rel), pi(status), pi(rung), pd(err), pd(vq), pi(info)))
+    return rel, status, rung, err, vq, info
+
+
+def _field_values(values, limbs, what):
+    a = np.asarray(values, dtype=np.float64)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    if a.ndim != 2 or a.shape[0] > limbs:
+        raise ValueError(f"{what}: values must be fp64 (count,) or planar (planes <= {limbs}, count), got {a.shape}")
+    v = np.zeros((limbs, max(a.shape[1], 1)))
+    v[:a.shape[0], :a.shape[1]] = a
+    return v, a.shape[1]
+
+
+def _field_coeffs(rel, status):
+    coeffs = np.empty((rel.shape[0], rel.shape[1] - 1), dtype=object)
+    for i in range(rel.shape[0]):
+        for k in range(rel.shape[1] - 1):
+            coeffs[i, k] = Fraction(-int(rel[i, k + 1]), int(rel[i, 0])) if status[i] == FIELD_FOUND else None
+    return coeffs
+
+
+def field_default_digits(bits: int, limbs: int) -> int:
+    """the digits per entry `round_to_field` gives the kernel: a reduced basis at p bits with one short relation has entries near p / 2 bits at worst (deg 2)"""
+    return min(LLL_MAX_DIGITS, field_top_bits(bits, limbs) // (2 * DIGIT_BITS) + 3)
+
+
+def field_relations_lll(values, field: NumberField, limbs: int, errbound: float = 1e-15, bits: int = 1000, device: int = 0, lll=None) -> FieldRounding:
+    """The contract of `round_to_field` through `lll_batch` (clrs_zz_lll): per rung p = 1, 6, 11, .. one batched call over the numbers still open, each on
+    the lattice [I | floor(2^p u)] from scratch; the first row is accepted on the host, in mpmath, when |sum a_i u_i| < errbound.  Degrees 2 .. 8; limited
+    by the 20 digits of `lll_batch` (status 4 where a lattice leaves them, 3 where it could not be reduced).  The rescue of `round_to_field` for statuses 3
+    and 4, its path for degrees 5 .. 8, and an independent device-side cross-check of k_mw_field_round.  `lll` replaces `lll_batch` (the tests' host build)."""
+    import mpmath as mp
+    from .mw import from_limbs, to_limbs
+    limbs, deg = int(limbs), field.degree
+    if limbs not in LIMBS:
+        raise ValueError(f"field_relations_lll: limbs must be one of {LIMBS}, got {limbs}")
+    if not 2 <= deg <= FIELD_LLL_MAX_DEGREE:
+        raise ValueError(f"field_relations_lll: the degree must lie in [2, {FIELD_LLL_MAX_DEGREE}], got {deg}")
+    if not errbound > 0 or bits < 1:
+        raise ValueError("field_relations_lll: errbound must be positive and bits at least 1")
+    lll = lll_batch if lll is None else lll
+    v, count = _field_values(values, limbs, "field_relations_lll")
+    D, P = deg + 1, field_top_bits(bits, limbs)
+    field.powers(limbs)                                                         # (refuses a g not known to the ladder's bits)
+    rel, status = np.zeros((count, D), dtype=object), np.full(count, -1, np.int32)
+    rung, err, vqs = np.zeros(count, np.int32), np.zeros(count), [mp.mpf(0)] * count
+    with mp.workprec(64 * limbs + 128):
+        gp = [mp.mpf(x) for x in from_limbs(field.powers(limbs))]
+        finite = np.all(np.isfinite(v[:, :count]), axis=0)
+        us = [[x] + gp if finite[i] else None for i, x in enumerate(from_limbs(v[:, :count]))]
+        status[~finite] = FIELD_NOT_FINITE
+        p = 1
+        while p <= P and np.any(status == -1):
+            opened = [i for i in range(count) if status[i] == -1]
+            lattices = []
+            for i in opened:
+                A = np.zeros((D, D + 1), dtype=object)
+                for r in range(D):
+                    A[r, r], A[r, D] = 1, int(mp.floor(mp.ldexp(us[i][r], p)))
+                lattices.append(A)
+            try:
+                outs = lll(lattices, device=device)
+            except ReductionError:
+                outs = []
+                for A in lattices:                                             # (one lattice failed: find out which)
+                    try:
+                        outs.append(lll([A], device=device)[0])
+                    except ReductionError as e:
+                        outs.append(FIELD_OVERFLOW if "digits" in str(e) else FIELD_STEER)
+            for i, out in zip(opened, outs):
+                rung[i] = p
+                if isinstance(out, int):
+                    status[i] = out
+                    continue
+                a = [int(x) for x in out[0, :D]]
+                e = abs(mp.fsum(x * u for x, u in zip(a, us[i])))
+                err[i] = float(e)
+                if e < errbound:
+                    rel[i] = a
+                    status[i] = FIELD_FOUND if a[0] != 0 else FIELD_NO_FIELD
+                    if a[0] != 0:
+                        vqs[i] = -mp.fsum(x * u for x, u in zip(a[1:], gp)) / a[0]
+            p += 5
+        status[status == -1] = FIELD_EXHAUSTED
+        vq = to_limbs(vqs, limbs) if count else np.zeros((limbs, 0))
+    zeros = np.zeros(count, np.int32)
+    return FieldRounding(_field_coeffs(rel, status), rel, status, rung, err, vq, zeros, zeros.copy(), np.ones(count, np.int32))
+
+
+def round_to_field(values, field: NumberField, limbs: int, errbound: float = 1e-15, bits: int = 1000, device: int = 0, relations=None, nd: Optional[int] = None,
+                   call=None) -> FieldRounding:
+    """Round numbers to QQ(g) on the device (clrs_mw_field_round, one lane per number): `values` planar (planes <= limbs, count) or fp64 (count,).  Per
+    number v the first rung p = 1, 6, 11, .. <= min(bits, 53 limbs - 16) at which the first row a of the LLL-reduced basis of [I | floor(2^p (v, 1, g, ..))]
+    has |a_0 v + a_1 + a_2 g + ..| < errbound, evaluated in `limbs` limbs from the numbers as given; then v ~ sum_k x_k g^k with x_k = -a_{k+1} / a_0.
+    Degrees 2 .. 4 run in the kernel; numbers it ends with status 3 or 4, and every number of a field of degree 5 .. 8, go to `relations` (default
+    `field_relations_lll`; False: nowhere).  `nd`: the base-2^24 digits per lattice entry (default `field_default_digits`); `call` replaces the device
+    call (the tests' host build)."""
+    limbs, deg = int(limbs), field.degree
+    if limbs not in LIMBS:
+        raise ValueError(f"round_to_field: limbs must be one of {LIMBS}, got {limbs}")
+    if deg < 2:
+        raise ValueError("round_to_field: a field of degree 1 is QQ: use rationalize")
+    relations = field_relations_lll if relations is None else relations
+    if deg not in FIELD_KERNEL_DEGREES:
+        if relations is False:
+            raise ValueError(f"round_to_field: the kernel takes degrees {FIELD_KERNEL_DEGREES}, got {deg}")
+        return relations(values, field, limbs, errbound=errbound, bits=bits, device=device)
+    v, count = _field_values(values, limbs, "round_to_field")
+    nd = field_default_digits(bits, limbs) if nd is None else int(nd)
+    gpow = field.powers(limbs)
+    call = _field_round_call_device if call is None else call
+    reld, status, rung, err, vq, info = call(limbs, deg, gpow, count, v, v.shape[1], int(bits), float(errbound), nd, device=device)
+    status, rung, err, vq = status[:count].copy(), rung[:count].copy(), err[:count].copy(), vq[:, :count].copy()
+    rel = planes_to_ints(reld[:, :, :count]).T.copy() if count else np.zeros((0, deg + 1), dtype=object)
+    out = FieldRounding(_field_coeffs(rel, status), rel, status, rung, err, vq, info[0, :count].copy(), info[1, :count].copy(), np.zeros(count, np.int32))
+    again = np.flatnonzero((status == FIELD_STEER) | (status == FIELD_OVERFLOW))
+    if again.size and relations is not False:
+        r = relations(v[:, again], field, limbs, errbound=errbound, bits=bits, device=device)
+        out.coeffs[again], out.rel[again], out.status[again], out.rung[again], out.err[again], out.path[again] = r.coeffs, r.rel, r.status, r.rung, r.err, 1
+        out.vq[:, again] = r.vq
+    return out
+
+
+def kernel_vectors_field_batch(block_n, X, Y, limbs: int, tau: float, use_dual: bool, dual_max: float, round_errbound: float, field: NumberField = None,
+                               bits: int = 1000, device: int = 0, batch=None, round=None, gemm=None):
+    """`kernel_vectors_batch`, then on the device the rounding of every entry of every vector to `field` (`round_to_field`) and the reference's second
+    check Y_b Vq_b of the rounded vectors (src/rounding.jl:630-639) by the kernel of clrs_mw_gemm.  Fills `coeffs` (n, count, deg), `round_status`,
+    `round_rung`, `vectors_rounded` and `round_resid_max` of every block; `num` / `den` stay None.  Without hooks this is ONE call,
+    clrs_mw_kernel_vectors_field; `batch`, `round`, `gemm` replace the three device calls it is made of (and make it three calls), which is also what runs
+    when an entry ends with status 3 or 4: `round_to_field` then sends it to `field_relations_lll`."""
+    from .mw import gemm_batch
+    if batch is None and round is None and gemm is None and field.degree in FIELD_KERNEL_DEGREES:
+        out = _kernel_vectors_field_call(block_n, X, Y, int(limbs), tau, use_dual, dual_max, float(round_errbound), field, int(bits), device)
+        if not any(np.any((k.round_status == FIELD_STEER) | (k.round_status == FIELD_OVERFLOW)) for k in out):
+            return out                                    # (else: the composed path below, whose `round_to_field` sends such entries to `field_relations_lll`)
+    batch = kernel_vectors_batch if batch is None else batch
+    round = round_to_field if round is None else round
+    gemm = gemm_batch if gemm is None else gemm
+    out = batch(block_n, X, Y, limbs, tau, use_dual, dual_max, device=device)
+    n = np.ascontiguousarray(block_n, np.int32).reshape(-1)
+    off = np.concatenate([[0], np.cumsum(n.astype(np.int64) ** 2)])
+    sizes = [int(n[b]) * k.count for b, k in enumerate(out)]
+    pool = np.concatenate([np.asarray(k.vectors).reshape(limbs, -1) for k in out], axis=1) if out else np.zeros((limbs, 0))
+    r = round(pool, field, limbs, errbound=float(round_errbound), bits=int(bits), device=device)
+    pos, jobs = 0, []
+    for b, (k, size) in enumerate(zip(out, sizes)):
+        nn, shape = int(n[b]), (int(n[b]), k.count)
+        k.coeffs = r.coeffs[pos:pos + size].reshape(shape + (field.degree,))
+        k.round_status, k.round_rung = r.status[pos:pos + size].reshape(shape), r.rung[pos:pos + size].reshape(shape)
+        k.vectors_rounded = np.ascontiguousarray(r.vq[:, pos:pos + size].reshape((limbs,) + shape))
+        k.round_resid_max = np.zeros(k.count)
+        if size:
+            jobs.append((b, (np.asarray(Y)[:, off[b]:off[b + 1]].reshape(limbs, nn, nn), k.vectors_rounded, None, False, False, 1, 0)))
+        pos += size
+    for (b, _), prod in zip(jobs, gemm([j for _, j in jobs], limbs, device=device)):
+        out[b].round_resid_max = np.max(np.abs(prod[0]), axis=0)
+    return out
+
+
+def _kernel_vectors_field_call(block_n, X, Y, limbs, tau, use_dual, dual_max, round_errbound, field, bits, device=0, nd=None):
+    """one call of clrs_mw_kernel_vectors_field: the elimination, the rounding of every entry to `field` and the second check, on the device"""
+    n = np.ascontiguousarray(block_n, np.int32).reshape(-1)
+    nb, deg = n.size, field.degree
+    off = np.concatenate([[0], np.cumsum(n.astype(np.int64) ** 2)])
+    xoff = np.concatenate([[0], np.cumsum(n.astype(np.int64))])
+    plane, xlen = int(off[-1]), int(xoff[-1])
+    nd = field_default_digits(bits, limbs) if nd is None else int(nd)
+    X, Y = (np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64) for a in (X, Y))
+    if X.shape != (limbs, plane) or Y.shape != (limbs, plane):
+        raise ValueError(f"kernel_vectors_field_batch: X and Y must be planar ({limbs}, {plane}), got {X.shape} and {Y.shape}")
+    p1 = max(plane, 1)
+    pool = lambda: np.zeros((limbs, p1))
+    Xp, Yp, V, Vq = pool(), pool(), pool(), pool()
+    Xp[:, :plane], Yp[:, :plane] = X, Y
+    branch, rank, count = (np.zeros(max(nb, 1), np.int32) for _ in range(3))
+    perm = np.zeros(max(xlen, 1), np.int32)
+    rmax, vmax, rmax2, piv = np.zeros(max(xlen, 1)), np.zeros(max(xlen, 1)), np.zeros(max(xlen, 1)), np.zeros((limbs, max(xlen, 1)))
+    rel, status, rung = np.zeros((nd, deg + 1, p1), np.int32), np.zeros(p1, np.int32), np.zeros(p1, np.int32)
+    err, info, gpow = np.zeros(p1), np.zeros((2, p1), np.int32), field.powers(limbs)
+    pi, pd = (lambda a: a.ctypes.data_as(_lib.p_i32)), (lambda a: a.ctypes.data_as(_lib.p_d))
+    _lib.check(_lib.load().clrs_mw_kernel_vectors_field(int(device), limbs, nb, pi(n), pd(Xp), pd(Yp), plane if plane else 0, float(tau), int(bool(use_dual)),
+                                                        float(dual_max), float(round_errbound), deg, pd(gpow), int(bits), nd, pi(branch), pi(perm), pi(rank),
+                                                        pi(count), pd(V), pd(rmax), pd(vmax), pd(piv), pi(rel), pi(status), pi(rung), pd(err), pd(Vq), pi(info),
+                                                        pd(rmax2)))
+    out = []
+    for b in range(nb):
+        nn, r, c = int(n[b]), int(rank[b]), int(count[b])
+        seg = slice(int(off[b]), int(off[b]) + nn * c)
+        cols = lambda a: np.ascontiguousarray(np.moveaxis(a[..., seg].reshape(a.shape[:-1] + (c, nn)), -1, -2))
+        k = BlockKernel("dual" if branch[b] else "primal", r, c, perm[xoff[b]:xoff[b + 1]].copy(), cols(V), rmax[xoff[b]:xoff[b] + c].copy(),
+                        vmax[xoff[b]:xoff[b] + c].copy(), piv[:, xoff[b]:xoff[b] + nn - r].copy())
+        k.round_status, k.round_rung, k.vectors_rounded = cols(status), cols(rung), cols(Vq)
+        ints = planes_to_ints(rel[:, :, seg]).T if nn * c else np.zeros((0, deg + 1), dtype=object)           # (entry, deg + 1), entries vector by vector
+        k.coeffs = np.ascontiguousarray(np.transpose(_field_coeffs(ints, status[seg]).reshape(c, nn, deg), (1, 0, 2)))
+        k.round_resid_max = rmax2[xoff[b]:xoff[b] + c].copy()
+        out.append(k)
+    return out
+
+
+def vectors_to_field(block: BlockKernel):
+    """The rounded vectors of a block (after `kernel_vectors(rationalize=True, field=...)`): per vector a list of coefficient tuples (x_0, .., x_{deg-1}) of
+    `Fraction`s, entry = sum_k x_k g^k."""
+    if block.coeffs is None:
+        raise ValueError("vectors_to_field: the block was not rounded to a field (kernel_vectors(..., rationalize=True, field=...))")
+    if np.any(np.asarray(block.round_status) != 0):
+        raise KernelVectorError(f"{CLINDEP_MESSAGE}: the block has entries without a relation")
+    c = block.coeffs
+    return [[tuple(c[i, v]) for i in range(c.shape[0])] for v in range(c.shape[1])]

@@ -486,7 +486,32 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   pointer, a digit outside [-2^23, 2^23].  nb == 0 touches nothing; a batch whose lattices all have 0 rows gives status 0 without touching a device.
  *   Every device buffer is released on every path.
  * clrs_zz_lll_times: the milliseconds of the calling thread's last clrs_zz_lll: in k_zz_lll over all launches, and from the first upload to the last
- *   download (device events). */
+ *   download (device events).
+ * clrs_mw_field_round: round `count` multi-word numbers to the number field QQ(g) of degree deg = 2 .. 4 by integer relations (the
+ *   reference's roundx(x, g, deg) -> clindep -> lindep per entry of a kernel vector, src/rounding.jl:481-534), host pointers, no context: the degree-d
+ *   counterpart of clrs_mw_rationalize.  gpow is planar [limbs][deg], limb l of g^k at gpow[l * deg + k]; v planar [limbs][plane].  Per number the first
+ *   rung p = 1, 6, 11, .. <= min(bits, 53 limbs - 16) at which the first row a of an LLL-reduced basis ((delta, eta) = (0.99, 0.51)) of the lattice
+ *   [I | floor(2^p (v, 1, g, .., g^(deg-1)))] has |a_0 v + a_1 + a_2 g + .. + a_deg g^(deg-1)| < errbound, that quantity evaluated in `limbs` limbs from the
+ *   numbers as given.  The lattice of a rung is the reduced basis of the rung before with its last column carried five bits further (exact integers of nd
+ *   balanced base-2^24 digits; one lane per number, the state in a lane-strided workspace).  rel is [nd][deg + 1][plane] int32: digit s of a_k of number i
+ *   at rel[(s * (deg + 1) + k) * plane + i]; status [plane]: 0 found; 1 no rung gave a relation; 2 a limb of v is NaN or Inf; 3 the Gram-Schmidt data were
+ *   unusable or a cap was hit (64 size-reduction passes per visit, 4096 exchanges per rung); 4 an entry left its nd digits, or |v| >= 2^22; 5 the accepted
+ *   relation has a_0 = 0 (the powers of g are dependent to this accuracy).  rung [plane]: the bits of the rung the number ended at; err [plane]: the
+ *   residual there (0 for statuses 2, 3, 4); vq planar [limbs][plane]: -(a_1 + a_2 g + ..) / a_0 for status 0, else 0; info [2][plane]: exchanges, rungs
+ *   visited.  rel is 0 unless the status is 0 or 5.  Entry i < count of every plane is written and nothing behind them.  A launch advances a number by at
+ *   most 16 rungs, or clrs_config_set("field_round_launch_rungs", n), then the host launches again; the result does not depend on n.  CLRS_ERR_INVALID before
+ *   any device call, outputs untouched: limbs other than 4, 5, 6, 8, 10, deg outside [2, 4], count < 0, plane < count, errbound not positive, bits < 1, nd
+ *   outside [1, 20], a null pointer with count > 0, a power of g that is not finite or not below 2^22.  count == 0 touches nothing.  Every device buffer is
+ *   released on every path.
+ * clrs_mw_kernel_vectors_field: clrs_mw_kernel_vectors with the same arguments and the same outputs, bit for bit, followed on the device by
+ *   clrs_mw_field_round (deg, gpow, bits, nd, errbound = round_errbound) of every entry of every vector and by the reference's second check Y_b Vq_b
+ *   (src/rounding.jl:630-639) by the kernel of clrs_mw_gemm: the shape of clrs_mw_kernel_vectors_rational, whose scaffold it shares.  rel [nd][deg + 1][plane],
+ *   status, rung, err [plane], info [2][plane] and Vq [limbs][plane] are pools over the plane like V: the entries of the vectors (block b: n_b x count_b from
+ *   its offset, column-major) are written, everything else comes back as it went.  round_resid_max [sum n]: per vector max_i |head (Y_b Vq_b)[i, v]|.
+ *   CLRS_ERR_INVALID as for clrs_mw_kernel_vectors, and for round_errbound not positive, deg outside [2, 4], bits < 1, nd outside [1, 20], a null output,
+ *   a power of g that is not finite or not below 2^22.
+ * clrs_mw_field_round_times: the milliseconds of the calling thread's last clrs_mw_field_round: in k_mw_field_round over all launches, and from the first
+ *   upload to the last download (device events). */
 #define CLRS_MODP_MINORS_MAX_N 128
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
@@ -525,6 +550,13 @@ int clrs_zz_lowrank_system_times(double *tile_ms, double *carry_ms, double *whol
 int clrs_zz_lll(int device, int nb, const int32_t *rows, const int32_t *cols, const int32_t *cols_gram, int nd, const int32_t *in_digits, int32_t *out_digits,
                 double delta, double eta, int limbs, int max_swaps, int32_t *info);
 int clrs_zz_lll_times(double *kernel_ms, double *whole_ms);
+int clrs_mw_field_round(int device, int limbs, int deg, const double *gpow, int count, const double *v, int plane, int bits, double errbound, int nd,
+                        int32_t *rel, int32_t *status, int32_t *rung, double *err, double *vq, int32_t *info);
+int clrs_mw_field_round_times(double *kernel_ms, double *whole_ms);
+int clrs_mw_kernel_vectors_field(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual,
+                                 double dual_max, double round_errbound, int deg, const double *gpow, int bits, int nd, int32_t *branch, int32_t *perm,
+                                 int32_t *rank, int32_t *count, double *V, double *resid_max, double *v_max, double *pivot_resid, int32_t *rel, int32_t *status,
+                                 int32_t *rung, double *err, double *Vq, int32_t *info, double *round_resid_max);
 /* the solve stage of compute_search_direction! (src/solver.jl:1527-1582) */
 int clrs_mw_schur_solve(clrs_mw_ctx *ctx, const double *rhs_x, const double *rhs_y, double *dx, double *dy);
 

@@ -720,6 +720,40 @@ function rationalize(v::AbstractVector{BigFloat}; prec::Integer=precision(BigFlo
 end
 
 """
+    round_to_field(v::AbstractVector{BigFloat}, g::BigFloat, deg::Integer; prec=precision(BigFloat), bits=1000, errbound=1e-15, nd=0, device=0)
+
+The reference's `roundx(x, g, deg)` (src/rounding.jl:519-534) for `deg` = 2 .. 4 on the device (`clrs_mw_field_round`, DESIGN.md section 23), at
+`limbs_for(prec)` words per number: per number the first rung p = 1, 6, 11, .. <= min(bits, 53 limbs - 16) at which the first row `a` of an LLL-reduced
+basis of `[I | floor(2^p (v, 1, g, .., g^(deg-1)))]` has `|a[1] v + a[2] + a[3] g + ..| < errbound`.  Returns `(coeffs, status, rung)`: `coeffs[i]` the
+`deg` rationals `-a[k+1] // a[1]` (zeros unless `status[i] == 0`); `status[i]` 0 found, 1 ladder exhausted, 2 not finite, 3 steering failed or a cap was
+hit, 4 an entry left its `nd` digits, 5 `a[1] == 0`; `rung[i]` the bits of the rung the number ended at.  `nd = 0` takes the default digit count.
+"""
+function round_to_field(v::AbstractVector{BigFloat}, g::BigFloat, deg::Integer; prec::Integer=precision(BigFloat), bits::Integer=1000, errbound::Real=1e-15,
+                        nd::Integer=0, device::Integer=0)
+    K = limbs_for(prec)
+    K >= 4 || error("round_to_field: prec = $prec selects $K limbs; the multi-word kernels need at least 4 (prec >= 158)")
+    2 <= deg <= 4 || error("round_to_field: the degree must lie in 2:4, got $deg")
+    cnt = length(v); plane = max(cnt, 1); D = deg + 1
+    top = 1 + 5 * div(min(bits, 53 * K - 16) - 1, 5)
+    ndig = nd > 0 ? Int(nd) : min(20, div(top, 48) + 3)
+    vw = zeros(Float64, plane, K); vq = zeros(Float64, plane, K); gw = zeros(Float64, deg, K)
+    for i in 1:cnt
+        isfinite(v[i]) ? limbs_of!(vw, i, v[i], K) : (vw[i, 1] = Float64(v[i]))
+    end
+    for k in 1:deg
+        limbs_of!(gw, k, g^(k - 1), K)
+    end
+    rel = zeros(Int32, plane, D, ndig); status = zeros(Int32, plane); rung = zeros(Int32, plane); err = zeros(Float64, plane); info = zeros(Int32, plane, 2)
+    check(ccall((:clrs_mw_field_round, libclrs[]), Cint,
+                (Cint, Cint, Cint, Ptr{Float64}, Cint, Ptr{Float64}, Cint, Cint, Cdouble, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{Int32}),
+                device, K, deg, gw, cnt, vw, plane, bits, Float64(errbound), ndig, rel, status, rung, err, vq, info))
+    a(i, k) = sum(BigInt(rel[i, k, s]) << (24 * (s - 1)) for s in 1:ndig)
+    coeffs = [status[i] == 0 ? [-a(i, k + 1) // a(i, 1) for k in 1:deg] : [big(0) // big(1) for k in 1:deg] for i in 1:cnt]
+    return coeffs, status[1:cnt], rung[1:cnt]
+end
+
+"""
     find_pivots_modular(A::AbstractMatrix{<:Integer}, p::Integer; device=0)
     find_pivots_modular(A::AbstractMatrix{<:Integer}; maxprimes=3, device=0)
 
