@@ -344,6 +344,7 @@ extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int
 #include "clrs_modp_lift.hip.h"      // clrs_modp_dixon_lift: the inverse mod p by the elimination above, then the p-adic lifting loop
 #include "clrs_modp_rec.hip.h"       // clrs_modp_dixon_reconstruct: Horner and the half-extended Euclid per entry of the lifted solution
 #include "clrs_modp_minors.hip.h"    // clrs_modp_minors: the leading principal minors of a symmetric integer matrix mod many primes, one workgroup per prime
+#include "clrs_modp_minors_field.hip.h"   // clrs_modp_minors_field, clrs_modp_field_frobenius: the same minors for a matrix over a number field, D residue matrices per prime
 #include "clrs_modp_tile.hip.h"      // the 64 x 64 fp64 MFMA tile loop of the two exact products below
 #include "clrs_modp_zz_gemm.hip.h"   // clrs_zz_gemm: the exact product of integer matrices given in digit planes, one fp64 MFMA GEMM of one-digit matrices
 #include "clrs_modp_liftm.hip.h"     // clrs_modp_dixon_lift_multi: the lifting with a matrix of right-hand sides, both products of a step as fp64 MFMA GEMMs

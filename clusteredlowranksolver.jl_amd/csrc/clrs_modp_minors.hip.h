@@ -179,81 +179,37 @@ extern "C" int clrs_modp_minors_times(double *residues_ms, double *ldl_ms, doubl
     return 0;
 }
 
-extern "C" int clrs_modp_minors(int device, int n, int nd, const int32_t *digits, int nprimes, const int32_t *primes, int32_t *minors, int32_t *breakdown,
-                                int32_t *info) {
-    if (n < 1 || n > CLRS_MODP_MINORS_MAX_N) return modp_fail(CLRS_ERR_INVALID, "modp_minors: n must lie in [1, 128]");
-    if (nd < 1 || nd > MINORS_MAX_DIGITS) return modp_fail(CLRS_ERR_INVALID, "modp_minors: nd must lie in [1, 32767]");
-    if (nprimes < 1 || nprimes > MINORS_MAX_PRIMES) return modp_fail(CLRS_ERR_INVALID, "modp_minors: nprimes must lie in [1, 65535]");
-    if (!digits || !primes || !minors || !breakdown || !info) return modp_fail(CLRS_ERR_INVALID, "modp_minors: null argument");
+// What clrs_modp_minors and clrs_modp_minors_field (clrs_modp_minors_field.hip.h) refuse alike, before any device call: `who` heads the message.
+// digits: `planes` row-major n x n planes of balanced digits, each symmetric
+static int minors_check_digits(const std::string &who, int n, size_t planes, const int32_t *digits) {
     const size_t plane = (size_t)n * n;
-    for (size_t o = 0; o < (size_t)nd * plane; o++)
-        if (digits[o] < -(1 << 23) || digits[o] > (1 << 23)) return modp_fail(CLRS_ERR_INVALID, "modp_minors: a digit outside [-2^23, 2^23]");
-    for (int l = 0; l < nd; l++)
+    for (size_t o = 0; o < planes * plane; o++)
+        if (digits[o] < -(1 << 23) || digits[o] > (1 << 23)) return modp_fail(CLRS_ERR_INVALID, who + ": a digit outside [-2^23, 2^23]");
+    for (size_t l = 0; l < planes; l++)
         for (int i = 0; i < n; i++)
             for (int j = 0; j < i; j++)
                 if (digits[l * plane + (size_t)i * n + j] != digits[l * plane + (size_t)j * n + i])
-                    return modp_fail(CLRS_ERR_INVALID, "modp_minors: the digit planes are not symmetric");
-    {
-        std::vector<int32_t> sorted(primes, primes + nprimes);
-        std::sort(sorted.begin(), sorted.end());
-        for (int q = 0; q < nprimes; q++) {
-            const int v = sorted[q];
-            if (!modp_prime_ok(v)) return modp_fail(CLRS_ERR_INVALID, "modp_minors: every modulus must be a prime with 2 <= p < 2^23");
-            if (q > 0 && sorted[q - 1] == v) return modp_fail(CLRS_ERR_INVALID, "modp_minors: a repeated prime");
-        }
-    }
-    const size_t bound = modp_chunk_bound(g_cfg_modp_minors_chunk_bytes, MINORS_CHUNK_BYTES);
-    const int chunk = (int)std::min<size_t>((size_t)nprimes, std::max<size_t>(bound / (plane * sizeof(double)), 1));
-    const int npad = (n + 15) / 16 * 16;
-    const size_t lds = minors_lds_bytes(n);
+                    return modp_fail(CLRS_ERR_INVALID, who + ": the digit planes are not symmetric");
+    return 0;
+}
 
-    MODPCHECK(hipSetDevice(device));
-    if (lds > 48 * 1024) MODPCHECK(hipFuncSetAttribute((const void *)k_minors_ldl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    ModpBufs bufs;
-    int32_t *d_digits = nullptr, *d_primes = nullptr, *d_minors = nullptr, *d_break = nullptr;
-    double *d_R = nullptr;
-    int *d_err = nullptr;
-    MODPCHECK(bufs.get(&d_digits, (size_t)nd * plane)); MODPCHECK(bufs.get(&d_primes, (size_t)nprimes)); MODPCHECK(bufs.get(&d_R, (size_t)chunk * plane));
-    MODPCHECK(bufs.get(&d_minors, (size_t)nprimes * n)); MODPCHECK(bufs.get(&d_break, (size_t)nprimes)); MODPCHECK(bufs.get(&d_err, (size_t)1));
-    ModpEvents ev(5);
-    for (hipEvent_t &x : ev.e) MODPCHECK(hipEventCreate(&x));
-    MODPCHECK(hipEventRecord(ev.e[3], nullptr));
-    MODPCHECK(hipMemcpy(d_digits, digits, (size_t)nd * plane * sizeof(int32_t), hipMemcpyHostToDevice));
-    MODPCHECK(hipMemcpy(d_primes, primes, (size_t)nprimes * sizeof(int32_t), hipMemcpyHostToDevice));
-    MODPCHECK(hipMemset(d_minors, 0xff, (size_t)nprimes * n * sizeof(int32_t)));
-    MODPCHECK(hipMemset(d_break, 0, (size_t)nprimes * sizeof(int32_t)));
-    MODPCHECK(hipMemset(d_err, 0, sizeof(int)));
-    const int ne = n * (n + 1) / 2;
-    double ms[2] = {0.0, 0.0};
-    int launched = 0;
-    for (int q0 = 0; q0 < nprimes; q0 += chunk) {
-        const int pc = std::min(chunk, nprimes - q0);
-        MODPCHECK(hipEventRecord(ev.e[0], nullptr));
-        hipLaunchKernelGGL(k_minors_residues, dim3((unsigned)((ne + MINORS_WAVES - 1) / MINORS_WAVES), (unsigned)((pc + 64 * MINORS_RES_GROUPS - 1) / (64 * MINORS_RES_GROUPS))),
-                           dim3(MINORS_NT), 0, nullptr, d_digits, n, nd, d_primes + q0, pc, d_R);
-        MODPCHECK(hipGetLastError());
-        MODPCHECK(hipEventRecord(ev.e[1], nullptr));
-        hipLaunchKernelGGL(k_minors_ldl, dim3((unsigned)pc), dim3(MINORS_NT), lds, nullptr, d_R, n, npad, d_primes, q0, d_minors, d_break, d_err);
-        MODPCHECK(hipGetLastError());
-        MODPCHECK(hipEventRecord(ev.e[2], nullptr));
-        MODPCHECK(hipEventSynchronize(ev.e[2]));
-        float a = 0.f, b = 0.f;
-        MODPCHECK(hipEventElapsedTime(&a, ev.e[0], ev.e[1])); MODPCHECK(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
-        ms[0] += a; ms[1] += b;
-        launched += pc;
-    }
-    int err = 0;
-    std::vector<int32_t> h_minors((size_t)nprimes * n), h_break((size_t)nprimes);      // the caller's arrays are written only by a call that succeeds
-    MODPCHECK(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
-    MODPCHECK(hipMemcpy(h_minors.data(), d_minors, h_minors.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    MODPCHECK(hipMemcpy(h_break.data(), d_break, h_break.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    MODPCHECK(hipEventRecord(ev.e[4], nullptr));
-    MODPCHECK(hipEventSynchronize(ev.e[4]));
-    float total = 0.f;
-    MODPCHECK(hipEventElapsedTime(&total, ev.e[3], ev.e[4]));
-    g_minors_ms[0] = ms[0]; g_minors_ms[1] = ms[1]; g_minors_ms[2] = total;
-    int broke = 0;
+static int minors_check_primes(const std::string &who, int nprimes, const int32_t *primes) {
+    std::vector<int32_t> sorted(primes, primes + nprimes);
+    std::sort(sorted.begin(), sorted.end());
     for (int q = 0; q < nprimes; q++) {
+        const int v = sorted[q];
+        if (!modp_prime_ok(v)) return modp_fail(CLRS_ERR_INVALID, who + ": every modulus must be a prime with 2 <= p < 2^23");
+        if (q > 0 && sorted[q - 1] == v) return modp_fail(CLRS_ERR_INVALID, who + ": a repeated prime");
+    }
+    return 0;
+}
+
+// What k_minors_ldl left for `count` matrices (matrix q eliminated mod primes[q]): the counters into info, and, unless an impossibility was met (a
+// breakdown outside [0, n], a residue where none belongs: CLRS_ERR_HIP, the caller's arrays untouched), the rows into the caller's arrays.
+static int minors_deliver(const std::string &who, int n, int count, const int32_t *primes, const std::vector<int32_t> &h_minors, const std::vector<int32_t> &h_break,
+                          int err, size_t lds, int launched, int32_t *minors, int32_t *breakdown, int32_t *info) {
+    int broke = 0;
+    for (int q = 0; q < count; q++) {
         const int k = h_break[q];
         if (k != 0) broke++;
         if (k < 0 || k > n) err++;
@@ -263,8 +219,89 @@ extern "C" int clrs_modp_minors(int device, int n, int nd, const int32_t *digits
         }
     }
     info[0] = (int32_t)lds; info[1] = launched; info[2] = broke; info[3] = err;
-    if (err != 0) return modp_fail(CLRS_ERR_HIP, "modp_minors: " + std::to_string(err) + " pivots or minors that are no residues");
+    if (err != 0) return modp_fail(CLRS_ERR_HIP, who + ": " + std::to_string(err) + " pivots or minors that are no residues");
     std::copy(h_minors.begin(), h_minors.end(), minors);
     std::copy(h_break.begin(), h_break.end(), breakdown);
     return 0;
+}
+
+// The device half of clrs_modp_minors and clrs_modp_minors_field: `count` matrices of residues, matrix m eliminated mod mods[m] (a host array), `chunk`
+// of them resident at a time.  upload(bufs) allocates and fills what the residue launch reads; residues(m0, mc, d_mods, d_R) launches the kernel that
+// fills d_R with the matrices m0 .. m0 + mc - 1 (d_mods: the device copy of mods).  ms receives the times of clrs_modp_minors_times.
+template <class Upload, class Residues>
+static int minors_run(const std::string &who, int device, int n, int count, int chunk, const int32_t *mods, Upload upload, Residues residues, double *ms_out,
+                      int32_t *minors, int32_t *breakdown, int32_t *info) {
+    const size_t plane = (size_t)n * n;
+    const int npad = (n + 15) / 16 * 16;
+    const size_t lds = minors_lds_bytes(n);
+
+    MODPCHECK(hipSetDevice(device));
+    if (lds > 48 * 1024) MODPCHECK(hipFuncSetAttribute((const void *)k_minors_ldl, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ModpBufs bufs;
+    int32_t *d_mods = nullptr, *d_minors = nullptr, *d_break = nullptr;
+    double *d_R = nullptr;
+    int *d_err = nullptr;
+    MODPCHECK(bufs.get(&d_mods, (size_t)count)); MODPCHECK(bufs.get(&d_R, (size_t)chunk * plane));
+    MODPCHECK(bufs.get(&d_minors, (size_t)count * n)); MODPCHECK(bufs.get(&d_break, (size_t)count)); MODPCHECK(bufs.get(&d_err, (size_t)1));
+    ModpEvents ev(5);
+    for (hipEvent_t &x : ev.e) MODPCHECK(hipEventCreate(&x));
+    MODPCHECK(hipEventRecord(ev.e[3], nullptr));
+    if (int code = upload(bufs)) return code;
+    MODPCHECK(hipMemcpy(d_mods, mods, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice));
+    MODPCHECK(hipMemset(d_minors, 0xff, (size_t)count * n * sizeof(int32_t)));
+    MODPCHECK(hipMemset(d_break, 0, (size_t)count * sizeof(int32_t)));
+    MODPCHECK(hipMemset(d_err, 0, sizeof(int)));
+    double ms[2] = {0.0, 0.0};
+    int launched = 0;
+    for (int m0 = 0; m0 < count; m0 += chunk) {
+        const int mc = std::min(chunk, count - m0);
+        MODPCHECK(hipEventRecord(ev.e[0], nullptr));
+        residues(m0, mc, d_mods, d_R);
+        MODPCHECK(hipGetLastError());
+        MODPCHECK(hipEventRecord(ev.e[1], nullptr));
+        hipLaunchKernelGGL(k_minors_ldl, dim3((unsigned)mc), dim3(MINORS_NT), lds, nullptr, d_R, n, npad, d_mods, m0, d_minors, d_break, d_err);
+        MODPCHECK(hipGetLastError());
+        MODPCHECK(hipEventRecord(ev.e[2], nullptr));
+        MODPCHECK(hipEventSynchronize(ev.e[2]));
+        float a = 0.f, b = 0.f;
+        MODPCHECK(hipEventElapsedTime(&a, ev.e[0], ev.e[1])); MODPCHECK(hipEventElapsedTime(&b, ev.e[1], ev.e[2]));
+        ms[0] += a; ms[1] += b;
+        launched += mc;
+    }
+    int err = 0;
+    std::vector<int32_t> h_minors((size_t)count * n), h_break((size_t)count);          // the caller's arrays are written only by a call that succeeds
+    MODPCHECK(hipMemcpy(&err, d_err, sizeof(int), hipMemcpyDeviceToHost));
+    MODPCHECK(hipMemcpy(h_minors.data(), d_minors, h_minors.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    MODPCHECK(hipMemcpy(h_break.data(), d_break, h_break.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    MODPCHECK(hipEventRecord(ev.e[4], nullptr));
+    MODPCHECK(hipEventSynchronize(ev.e[4]));
+    float total = 0.f;
+    MODPCHECK(hipEventElapsedTime(&total, ev.e[3], ev.e[4]));
+    ms_out[0] = ms[0]; ms_out[1] = ms[1]; ms_out[2] = total;
+    return minors_deliver(who, n, count, mods, h_minors, h_break, err, lds, launched, minors, breakdown, info);
+}
+
+extern "C" int clrs_modp_minors(int device, int n, int nd, const int32_t *digits, int nprimes, const int32_t *primes, int32_t *minors, int32_t *breakdown,
+                                int32_t *info) {
+    if (n < 1 || n > CLRS_MODP_MINORS_MAX_N) return modp_fail(CLRS_ERR_INVALID, "modp_minors: n must lie in [1, 128]");
+    if (nd < 1 || nd > MINORS_MAX_DIGITS) return modp_fail(CLRS_ERR_INVALID, "modp_minors: nd must lie in [1, 32767]");
+    if (nprimes < 1 || nprimes > MINORS_MAX_PRIMES) return modp_fail(CLRS_ERR_INVALID, "modp_minors: nprimes must lie in [1, 65535]");
+    if (!digits || !primes || !minors || !breakdown || !info) return modp_fail(CLRS_ERR_INVALID, "modp_minors: null argument");
+    const size_t plane = (size_t)n * n;
+    if (int code = minors_check_digits("modp_minors", n, (size_t)nd, digits)) return code;
+    if (int code = minors_check_primes("modp_minors", nprimes, primes)) return code;
+    const size_t bound = modp_chunk_bound(g_cfg_modp_minors_chunk_bytes, MINORS_CHUNK_BYTES);
+    const int chunk = (int)std::min<size_t>((size_t)nprimes, std::max<size_t>(bound / (plane * sizeof(double)), 1));
+    const int ne = n * (n + 1) / 2;
+    int32_t *d_digits = nullptr;
+    auto upload = [&](ModpBufs &bufs) -> int {
+        MODPCHECK(bufs.get(&d_digits, (size_t)nd * plane));
+        MODPCHECK(hipMemcpy(d_digits, digits, (size_t)nd * plane * sizeof(int32_t), hipMemcpyHostToDevice));
+        return 0;
+    };
+    auto residues = [&](int q0, int pc, const int32_t *d_primes, double *d_R) {
+        hipLaunchKernelGGL(k_minors_residues, dim3((unsigned)((ne + MINORS_WAVES - 1) / MINORS_WAVES), (unsigned)((pc + 64 * MINORS_RES_GROUPS - 1) / (64 * MINORS_RES_GROUPS))),
+                           dim3(MINORS_NT), 0, nullptr, d_digits, n, nd, d_primes + q0, pc, d_R);
+    };
+    return minors_run("modp_minors", device, n, nprimes, chunk, primes, upload, residues, g_minors_ms, minors, breakdown, info);
 }

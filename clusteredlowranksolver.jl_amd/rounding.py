@@ -40,8 +40,10 @@ partial-column heuristic above `reduce_kernelvectors_cutoff`.
 
 Over a number field QQ(g) of degree 2 .. 4 the entries of the kernel vectors are rounded by integer relations on the device (src/rounding.jl:481-534: roundx(x, g, deg)
 -> clindep -> lindep; clrs_mw_field_round): `NumberField`, `round_to_field`, `field_relations_lll` (the same contract through clrs_zz_lll: the
-rescue, degrees 5 .. 8), `kernel_vectors(..., rationalize=True, field=...)`, `vectors_to_field`.  The steps after the rounding -- basis change, system and PD check
-over the field -- are not built.
+rescue, degrees 5 .. 8), `kernel_vectors(..., rationalize=True, field=...)`, `vectors_to_field`.  Of the steps after the rounding the positive-definiteness check is built
+(`checkpd_field`, exact: the leading minors as elements of Z[g] from their images at the roots of the minimal polynomial mod primes that split it,
+clrs_modp_minors_field; `split_primes`, `field_frobenius`, `leading_minors_field_mod`, `field_minor_bounds`, `FieldPDCertificate`,
+`is_valid_solution(..., field=...)`); the basis change and the system over the field are not.
 
 The system the projection solves is assembled from an `ExactProblem` (the problem over QQ; `to_sdp` gives the numeric one) by `linear_system`
 (`partial_linearsystem`, src/interface.jl:1354-1535): per low-rank block one call of clrs_zz_lowrank_system, a row-wise Gram of long
@@ -66,7 +68,8 @@ __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vecto
            "solve_dixon_multi", "inverse_qq", "complete_basis", "basis_transformations", "transform", "undo_transform", "lowrank_system", "ExactLowRank", "ExactBlock",
            "ExactProblem", "ExactSolution", "system_index", "linear_system", "select_columns", "vectorize_solution", "get_rational_system", "exact_solution",
            "ReductionError", "lll_first_rung", "lll_batch", "lll", "kernel_lattice", "reduce_kernel_vectors", "NumberField", "FieldRounding", "round_to_field",
-           "field_relations_lll", "kernel_vectors_field_batch", "vectors_to_field"]
+           "field_relations_lll", "kernel_vectors_field_batch", "vectors_to_field", "split_primes", "field_frobenius", "leading_minors_field_mod", "field_minor_bounds",
+           "FieldPDCertificate", "checkpd_field"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -1229,15 +1232,20 @@ def checkpd(A, device: int = 0, minors=None) -> PDCertificate:
     return PDCertificate(failed is None, exact, failed, scale, primes, discarded)
 
 
-def is_valid_solution(blocks, A=None, b=None, x=None, check_slacks: bool = True, device: int = 0, minors=None, matmul=None):
+def is_valid_solution(blocks, A=None, b=None, x=None, check_slacks: bool = True, device: int = 0, minors=None, matmul=None, field=None, primes=None):
     """The numeric part of the reference's `is_valid_solution` (src/rounding.jl:367-415): are the slacks zero, and is every block of the exact solution
     positive definite?  `blocks`: the symmetric blocks (`Fraction`s or integers), each through `checkpd` (`device`, `minors` go there).  With
     `check_slacks` the slacks `A x - b` (`A` (nrows, ncols), `b` (nrows,), `x` (ncols,)) are formed in `Fraction` arithmetic on the host, or, with
     `matmul(A, B, device=...)` (`zz_matmul`: on the device), as ONE integer product of the rows of [A b] cleared of denominators with `L x`, L the common
     denominator of x, divided by L and the row's multiplier entry by entry: the same `Fraction`s.  Returns
     `(success, failures)`: `failures` lists `("constraint", i, slack)` for every constraint i with a non-zero slack and `("block", j, failed_order)` for
-    every block j that is not positive definite."""
+    every block j that is not positive definite.
+
+    With `field` (a `NumberField`) the blocks are matrices of coefficient tuples over QQ(g) and go through `checkpd_field` (`minors`, `primes` go there); the
+    slack check over a field is not built, so `check_slacks` must be False then."""
     failures = []
+    if field is not None and check_slacks:
+        raise ValueError("is_valid_solution: the slack check over a number field is not built; pass check_slacks=False")
     if check_slacks:
         if A is None or b is None or x is None:
             raise ValueError("is_valid_solution: A, b and x are needed to check the slacks")
@@ -1259,7 +1267,7 @@ def is_valid_solution(blocks, A=None, b=None, x=None, check_slacks: bool = True,
             if slack != 0:
                 failures.append(("constraint", i, slack))
     for j, blk in enumerate(blocks):
-        cert = checkpd(blk, device=device, minors=minors)
+        cert = checkpd(blk, device=device, minors=minors) if field is None else checkpd_field(blk, field, device=device, minors=minors, primes=primes)
         if not cert.pd:
             failures.append(("block", j, cert.failed_order))
     return not failures, failures
@@ -2667,3 +2675,474 @@ def vectors_to_field(block: BlockKernel):
         raise KernelVectorError(f"{CLINDEP_MESSAGE}: the block has entries without a relation")
     c = block.coeffs
     return [[tuple(c[i, v]) for i in range(c.shape[0])] for v in range(c.shape[1])]
+
+
+# ---- the exact positive-definiteness check over a number field: leading minors in Z[g] from split primes (src/rounding.jl:417-472; clrs_modp_minors_field) ----
+FIELD_MINORS_DEGREES = (2, 3, 4)     # what k_minors_residues_field and k_field_frobenius are instantiated for
+FIELD_FROBENIUS_MAX_PRIMES = 1 << 20
+
+
+def _pmod_divmod(a, f, p):
+    """(quotient, remainder) of the polynomial a by f over F_p (coefficient lists low to high, trimmed; f != 0)"""
+    a = [int(v) % p for v in a]
+    df, inv = len(f) - 1, pow(f[-1], -1, p)
+    q = [0] * max(len(a) - df, 0)
+    while len(a) - 1 >= df:
+        c = a[-1] * inv % p
+        if c:
+            off = len(a) - 1 - df
+            q[off] = c
+            for j in range(df):
+                a[off + j] = (a[off + j] - c * f[j]) % p
+        a.pop()
+    while a and a[-1] == 0:
+        a.pop()
+    return q, a
+
+
+def _pmod_mul(a, b, f, p):
+    """a b mod (f, p)"""
+    if not a or not b:
+        return []
+    t = [0] * (len(a) + len(b) - 1)
+    for i, x in enumerate(a):
+        if x:
+            for j, y in enumerate(b):
+                t[i + j] += x * y
+    return _pmod_divmod(t, f, p)[1]
+
+
+def _pmod_pow(base, e: int, f, p):
+    """base^e mod (f, p) by square and multiply"""
+    r, b = _pmod_divmod([1], f, p)[1], _pmod_divmod(base, f, p)[1]
+    while e:
+        if e & 1:
+            r = _pmod_mul(r, b, f, p)
+        b = _pmod_mul(b, b, f, p)
+        e >>= 1
+    return r
+
+
+def _pmod_gcd(a, b, p):
+    """the monic greatest common divisor over F_p"""
+    a, b = [int(v) % p for v in a], [int(v) % p for v in b]
+    while a and a[-1] == 0:
+        a.pop()
+    while b and b[-1] == 0:
+        b.pop()
+    while b:
+        a, b = b, _pmod_divmod(a, b, p)[1]
+    inv = pow(a[-1], -1, p) if a else 0
+    return [v * inv % p for v in a]
+
+
+def _frobenius_host(minpoly, p: int) -> list:
+    """the coefficients of x^p mod (minpoly, p), `degree` of them, or -1 throughout where p divides the leading coefficient: what k_field_frobenius computes"""
+    d = len(minpoly) - 1
+    if minpoly[-1] % p == 0:
+        return [-1] * d
+    r = _pmod_pow([0, 1], p, [int(c) % p for c in minpoly], p)
+    return r + [0] * (d - len(r))
+
+
+def _split_roots(f, p: int) -> list:
+    """the roots, ascending, of a polynomial f over F_p that is a product of distinct linear factors: Cantor-Zassenhaus, gcd(f, (x + a)^((p - 1) / 2) - 1)
+    for a = 1, 2, .. (deterministic); by trial below 64"""
+    f = _pmod_gcd(f, [], p)                                          # monic
+    if len(f) <= 1:
+        return []
+    if len(f) == 2:
+        return [(-f[0]) % p]
+    if p < 64:
+        return [r for r in range(p) if sum(c * pow(r, j, p) for j, c in enumerate(f)) % p == 0]
+    for a in range(1, p):
+        h = _pmod_pow([a, 1], (p - 1) // 2, f, p)
+        h = [(h[0] - 1) % p] + h[1:] if h else [p - 1]
+        g = _pmod_gcd(f, h, p)
+        if 1 < len(g) < len(f):
+            return sorted(_split_roots(g, p) + _split_roots(_pmod_divmod(f, g, p)[0], p))
+    raise ArithmeticError(f"_split_roots: no splitting element mod {p}")
+
+
+def field_frobenius(minpoly, primes, device: int = 0) -> np.ndarray:
+    """x^p mod (f, p) for every prime of `primes` (in [2, 2^23), at most 2^20) on the device, one lane per prime (clrs_modp_field_frobenius): int32
+    (len(primes), degree), row q the coefficients low to high, -1 throughout where the prime divides the leading coefficient.  `minpoly`: the integer
+    coefficients of f, low to high, degree 2 .. 4, below 2^63 in size.  The `frobenius=` of `split_primes`."""
+    f = [int(c) for c in minpoly]
+    d = len(f) - 1
+    if d not in FIELD_MINORS_DEGREES or f[-1] == 0 or any(abs(c) >= 1 << 63 for c in f):
+        raise ValueError(f"field_frobenius: a polynomial of degree in {FIELD_MINORS_DEGREES} with coefficients below 2^63 is needed")
+    pr = np.ascontiguousarray([int(p) for p in primes], dtype=np.int64)
+    if pr.size < 1 or pr.size > FIELD_FROBENIUS_MAX_PRIMES or pr.min() < 2 or pr.max() >= MODP_PRIME_LIMIT:
+        raise ValueError(f"field_frobenius: between 1 and {FIELD_FROBENIUS_MAX_PRIMES} primes in [2, 2^23) are needed")
+    pr, fc, out = pr.astype(np.int32), np.array(f, dtype=np.int64), np.full((pr.size, d), -2, np.int32)
+    _lib.check(_lib.load().clrs_modp_field_frobenius(int(device), d, fc.ctypes.data_as(_lib.p_i64), pr.size, pr.ctypes.data_as(_lib.p_i32), out.ctypes.data_as(_lib.p_i32)))
+    return out
+
+
+def split_primes(field, count: int, start: Optional[int] = None, frobenius=None):
+    """The first `count` primes below `start` (default 2^23), descending, at which the minimal polynomial f of `field` (a `NumberField`, or the coefficient
+    list itself) splits into distinct linear factors, with their roots: `(primes, roots)`, roots[q] the `degree` roots of f mod primes[q], ascending.
+
+    p splits f completely iff p divides neither lc(f) nor disc(f) and x^p = x mod (f, p).  `frobenius(minpoly, primes)` -> rows of coefficients of x^p
+    decides that for a batch: None is the host's square and multiply on Python integers, prime by prime; `field_frobenius` is the device, 4096 primes
+    per call.  The roots of the primes that passed are found on the host (Cantor-Zassenhaus).  `ArithmeticError` when the primes run out."""
+    f = [int(c) for c in (field.minpoly if hasattr(field, "minpoly") else field)]
+    d = len(f) - 1
+    if d < 2 or f[-1] == 0:
+        raise ValueError("split_primes: a minimal polynomial of degree at least 2 is needed")
+    fprime = [j * c for j, c in enumerate(f)][1:]
+    want = [0, 1] + [0] * (d - 2)
+    sched = _primes_descending()
+    at = 0 if start is None else int(np.count_nonzero(sched >= int(start)))
+    step = 1 if frobenius is None else 4096
+    primes, roots = [], []
+    while len(primes) < int(count):
+        cand = [int(p) for p in sched[at:at + step]]
+        if not cand:
+            raise ArithmeticError("split_primes: the primes below 2^23 are exhausted")
+        at += len(cand)
+        rows = [_frobenius_host(f, p) for p in cand] if frobenius is None else np.asarray(frobenius(f, cand))
+        for p, row in zip(cand, rows):
+            if [int(v) for v in row] != want or f[-1] % p == 0 or len(_pmod_gcd(f, fprime, p)) != 1:
+                continue
+            primes.append(p)
+            roots.append(_split_roots(f, p))
+            if len(roots[-1]) != d:
+                raise ArithmeticError(f"split_primes: {p} passed the test and has {len(roots[-1])} roots")
+            if len(primes) == int(count):
+                break
+    return primes, roots
+
+
+def _field_coeff_matrices(coeff_matrices, what):
+    """-> object array (d, n, n) of Python integers, every matrix symmetric"""
+    mats = [_symmetric_integer_matrix(M, what) for M in coeff_matrices]
+    if len(mats) < 2 or any(m.shape != mats[0].shape for m in mats):
+        raise ValueError(f"{what}: at least two coefficient matrices of one shape are needed")
+    out = np.empty((len(mats),) + mats[0].shape, dtype=object)
+    for j, m in enumerate(mats):
+        out[j] = m
+    return out
+
+
+def leading_minors_field_mod(coeff_matrices, primes, roots, device: int = 0):
+    """The leading principal minors of M = sum_j M_j g^j evaluated at g = roots[q][i] mod primes[q], for every pair, on the device: one call of
+    clrs_modp_minors_field.  `coeff_matrices`: the d (2 .. 4) symmetric integer matrices M_0 .. M_(d-1) (n <= 128, Python integers of any size); `primes`
+    distinct, in [2, 2^23), at most 65535; `roots` (len(primes), d): distinct numbers in [0, p) per prime (for the minors of M in Z[g]: the roots of the
+    monic minimal polynomial of g mod p).  Returns `(minors, breakdown)`: int32 (len(primes), d, n) and (len(primes), d), per pair what
+    `leading_minors_mod` returns per prime.  The counters are kept in `leading_minors_field_mod.last_info`."""
+    a = _field_coeff_matrices(coeff_matrices, "leading_minors_field_mod")
+    d, n = a.shape[0], a.shape[1]
+    pr = np.ascontiguousarray([int(p) for p in primes], dtype=np.int64)
+    if d not in FIELD_MINORS_DEGREES:
+        raise ValueError(f"leading_minors_field_mod: the degree must be one of {FIELD_MINORS_DEGREES}, got {d}")
+    if n < 1 or n > MINORS_MAX_N:
+        raise ValueError(f"leading_minors_field_mod: n must lie in [1, {MINORS_MAX_N}], got {n}")
+    if pr.size < 1 or pr.size > MINORS_MAX_PRIMES or pr.min() < 2 or pr.max() >= MODP_PRIME_LIMIT:
+        raise ValueError(f"leading_minors_field_mod: between 1 and {MINORS_MAX_PRIMES} primes in [2, 2^23) are needed")
+    rt = np.ascontiguousarray(np.asarray([[int(r) for r in row] for row in roots], dtype=np.int64).reshape(pr.size, -1))
+    if rt.shape != (pr.size, d) or rt.min() < 0 or np.any(rt >= pr[:, None]):
+        raise ValueError(f"leading_minors_field_mod: roots must be ({pr.size}, {d}) with every root in [0, p)")
+    pr, rt = pr.astype(np.int32), rt.astype(np.int32)
+    digits = np.ascontiguousarray(np.swapaxes(to_balanced_digits(a), 0, 1))                 # (d, nd, n, n)
+    minors, breakdown, info = np.full((pr.size, d, n), -2, np.int32), np.full((pr.size, d), -2, np.int32), np.zeros(4, np.int32)
+    ptr = lambda v: v.ctypes.data_as(_lib.p_i32)
+    _lib.check(_lib.load().clrs_modp_minors_field(int(device), n, d, digits.shape[1], ptr(digits), pr.size, ptr(pr), ptr(rt), ptr(minors), ptr(breakdown), ptr(info)))
+    leading_minors_field_mod.last_info = [int(v) for v in info]
+    return minors, breakdown
+
+
+leading_minors_field_mod.last_info = None
+
+
+def _field_monic(field):
+    """(h, a): a = |lc(f)| and h the monic integer minimal polynomial of a g (h(y) = a^(d-1) f(y / a) up to sign), low to high"""
+    f = [int(c) for c in field.minpoly]
+    if f[-1] < 0:
+        f = [-c for c in f]
+    a, d = f[-1], len(f) - 1
+    return [c * a ** (d - 1 - j) for j, c in enumerate(f[:-1])] + [1], a
+
+
+def _root_bound(h) -> int:
+    """an integer rho >= |z| for every complex root z of the monic integer polynomial h: the smaller of Cauchy's 1 + max |h_j| and max(1, sum |h_j|), j < deg"""
+    low = [abs(c) for c in h[:-1]]
+    return min(1 + max(low), max(1, sum(low)))
+
+
+def _trace_matrix_inverse(h):
+    """T^-1 as `Fraction`s, T[a][b] = Tr(g^(a + b)) for a root g of the monic h: the power sums s_0 .. s_(2d-2) by Newton's identities"""
+    d = len(h) - 1
+    e = [1] + [(-1) ** k * h[d - k] for k in range(1, d + 1)]        # elementary symmetric polynomials of the roots
+    s = [d]
+    for k in range(1, 2 * d - 1):
+        s.append(sum((-1) ** (i - 1) * e[i] * s[k - i] for i in range(1, min(k, d + 1))) + ((-1) ** (k - 1) * k * e[k] if k <= d else 0))
+    T = [[Fraction(s[a + b]) for b in range(d)] + [Fraction(int(a == b)) for b in range(d)] for a in range(d)]
+    for c in range(d):
+        piv = next((r for r in range(c, d) if T[r][c] != 0), None)
+        if piv is None:
+            raise ArithmeticError("the minimal polynomial has a repeated root: its trace form is singular")
+        T[c], T[piv] = T[piv], T[c]
+        T[c] = [v / T[c][c] for v in T[c]]
+        for r in range(d):
+            if r != c and T[r][c] != 0:
+                T[r] = [v - T[r][c] * w for v, w in zip(T[r], T[c])]
+    return [row[d:] for row in T]
+
+
+def field_minor_bounds(coeff_matrices, field) -> list:
+    """Python integers `C_k`, k = 1 .. n, with |c_(k,j)| <= C_k for every coefficient of the k-th leading principal minor sum_j c_(k,j) h^j of
+    M = sum_j M_j h^j, h the generator `checkpd_field` normalises to (lc(f) g: g itself where the minimal polynomial of `field` is monic), M_j the symmetric
+    integer matrices `coeff_matrices`.  With rho >= every |conjugate of h| (`_root_bound`), E = sum_j |M_j| rho^j entry by entry and H_k =
+    minor_bounds(E)[k - 1] (Hadamard), every conjugate of the minor is at most H_k in size; t_b = Tr(minor h^b) is then at most d H_k rho^b, and the
+    coefficients are T^-1 t, T[a][b] = Tr(h^(a + b)): C_k = max_j ceil(H_k d sum_b |T^-1[j][b]| rho^b).  DESIGN.md section 24."""
+    a = _field_coeff_matrices(coeff_matrices, "field_minor_bounds")
+    h, _ = _field_monic(field)
+    d = len(h) - 1
+    if a.shape[0] != d:
+        raise ValueError(f"field_minor_bounds: {d} coefficient matrices are needed for a field of degree {d}, got {a.shape[0]}")
+    rho, n = _root_bound(h), a.shape[1]
+    E = np.array([sum(abs(int(a[j, r, c])) * rho ** j for j in range(d)) for r in range(n) for c in range(n)], dtype=object).reshape(n, n)
+    Tinv = _trace_matrix_inverse(h)
+    factor = max(sum((abs(Tinv[j][b]) * d * rho ** b for b in range(d)), Fraction(0)) for j in range(d))
+    return [-((-H * factor.numerator) // factor.denominator) for H in minor_bounds(E)]
+
+
+def _poly_at(coeffs, x):
+    acc = Fraction(0)
+    for c in reversed(coeffs):
+        acc = acc * x + c
+    return acc
+
+
+def _poly_range(coeffs, lo, hi):
+    """an interval that holds sum_j coeffs[j] x^j for every x in [lo, hi]: Horner in interval arithmetic on exact rationals"""
+    a = b = Fraction(0)
+    for c in reversed(coeffs):
+        prods = (a * lo, a * hi, b * lo, b * hi)
+        a, b = min(prods) + c, max(prods) + c
+    return a, b
+
+
+class _RealRoot:
+    """The real root of the monic integer polynomial h next to the rational `near`, held in an isolating interval [lo, hi] with dyadic endpoints: h changes
+    sign on it and h' has no zero on it (interval evaluation), so it holds exactly one root.  `refine(bits)` shrinks it below 2^-bits by quadratic interval
+    refinement (the interval is cut into N parts, the part the secant points at is kept when h changes sign on it and N is squared, else the interval is
+    bisected and N goes back to its root): every step is decided by exact signs of h."""
+
+    def __init__(self, h, near: Fraction, prec: int):
+        self.h = [int(c) for c in h]
+        dh = [j * c for j, c in enumerate(self.h)][1:]
+        scale = max(1, abs(near.numerator) // near.denominator + 1)
+        for k in sorted({max(prec - 16, 8), max(prec // 2, 8), 32, 16, 8}, reverse=True):
+            w = Fraction(scale, 1 << k)
+            lo, hi = near - w, near + w
+            flo, fhi = _poly_at(self.h, lo), _poly_at(self.h, hi)
+            if flo == 0 or fhi == 0:
+                raise ArithmeticError("the minimal polynomial has a rational root: it is reducible")
+            d0, d1 = _poly_range(dh, lo, hi)
+            if (flo < 0) != (fhi < 0) and (d0 > 0 or d1 < 0):
+                self.lo, self.hi, self.flo, self.fhi, self.N = lo, hi, flo, fhi, 4
+                return
+        raise ArithmeticError("the generator could not be isolated as a simple real root of the minimal polynomial")
+
+    def refine(self, bits: int) -> None:
+        tol = Fraction(1, 1 << bits)
+        while self.hi - self.lo > tol:
+            N, width = self.N, self.hi - self.lo
+            t = self.flo / (self.flo - self.fhi)                     # the secant's zero, as a share of the width, in (0, 1)
+            k = min(N - 1, (t.numerator * N) // t.denominator)
+            a = self.lo + width * k / N
+            b = a + width / N
+            fa, fb = _poly_at(self.h, a), _poly_at(self.h, b)
+            if fa == 0 or fb == 0:
+                raise ArithmeticError("the minimal polynomial has a rational root: it is reducible")
+            if (fa < 0) != (fb < 0):
+                self.lo, self.hi, self.flo, self.fhi, self.N = a, b, fa, fb, N * N
+                continue
+            m = (self.lo + self.hi) / 2
+            fm = _poly_at(self.h, m)
+            if fm == 0:
+                raise ArithmeticError("the minimal polynomial has a rational root: it is reducible")
+            if (fm < 0) != (self.flo < 0):
+                self.hi, self.fhi = m, fm
+            else:
+                self.lo, self.flo = m, fm
+            self.N = max(4, _isqrt(N))
+
+    def sign(self, coeffs, what: str) -> int:
+        """the sign of sum_j coeffs[j] eta^j at the root eta, rigorously: 0 only for the zero element.  A non-zero element x of Z[eta] has a norm of size at
+        least 1, and each of its d conjugates is at most B = sum_j |c_j| rho^j, so |x(eta)| >= B^(1-d): an interval of eta below 2^-bits decides the sign
+        once bits exceeds (d - 1) log2 B by the slope of the polynomial.  The precision doubles from 64 bits up to that cap; `ArithmeticError`
+        naming `what` when it is reached (a reducible `minpoly` can do that).  Never a guess."""
+        c = [int(v) for v in coeffs]
+        if not any(c):
+            return 0
+        d, rho = len(self.h) - 1, _root_bound(self.h)
+        B = sum(abs(v) * rho ** j for j, v in enumerate(c))
+        slope = sum(j * abs(v) * rho ** max(j - 1, 0) for j, v in enumerate(c))
+        cap = (d - 1) * B.bit_length() + slope.bit_length() + 8
+        bits = 64
+        while True:
+            self.refine(bits)
+            lo, hi = _poly_range(c, self.lo, self.hi)
+            if lo > 0:
+                return 1
+            if hi < 0:
+                return -1
+            if bits > cap:
+                raise ArithmeticError(f"checkpd_field: the sign of {what} is undecided at {bits} bits, beyond what a non-zero element of the field allows: is minpoly irreducible?")
+            bits *= 2
+
+
+@dataclasses.dataclass
+class FieldPDCertificate:
+    """What `checkpd_field` proves about a symmetric matrix A over QQ(g).  `pd`: A is positive definite at the embedding g -> the real root gamma that
+    `NumberField.g` approximates.  `minpoly`, `generator_scale`: the monic integer minimal polynomial of h = generator_scale g (generator_scale = |lc| of
+    the field's minimal polynomial, 1 where that is monic) in which everything below is expressed.  `scale`: the positive integer D with D A = sum_j M_j h^j,
+    M_j integer.  `minors`: the exact leading principal minors of D A, from order 1 up to where the walk stopped, each a list of d integers c_0 .. c_(d-1),
+    the minor being sum_j c_j h^j.  `failed_order`: None, or the order of the first minor that is <= 0 at gamma (`minors[-1]`); when a diagonal entry <= 0
+    decided on the host, `minors` is empty and `failed_order` is the 1-based index of that entry.  `primes`: every prime given to the device, in order, and
+    `roots` their roots of `minpoly`, row by row; `discarded`: `(prime, root, order)` for every pair that broke down (a zero pivot at that order: that
+    image of the minor is 0 mod the prime); the prime was left out of every minor behind the first of its breakdowns.  `interval`: rationals (lo, hi)
+    with lo < gamma < hi, holding no other root of the minimal polynomial, as narrow as the signs needed."""
+    pd: bool
+    minors: list
+    failed_order: Optional[int]
+    scale: int
+    primes: list
+    roots: list
+    discarded: list
+    interval: tuple
+    minpoly: list
+    generator_scale: int
+
+    def __bool__(self):
+        return self.pd
+
+
+def _mod_matrix_inverse(V, p: int):
+    """the inverse of a small square matrix over F_p (Gauss-Jordan); `ArithmeticError` when singular"""
+    d = len(V)
+    a = [[int(v) % p for v in row] + [int(i == j) for j in range(d)] for i, row in enumerate(V)]
+    for c in range(d):
+        piv = next((r for r in range(c, d) if a[r][c]), None)
+        if piv is None:
+            raise ArithmeticError(f"two equal roots mod {p}")
+        a[c], a[piv] = a[piv], a[c]
+        inv = pow(a[c][c], -1, p)
+        a[c] = [v * inv % p for v in a[c]]
+        for r in range(d):
+            if r != c and a[r][c]:
+                f = a[r][c]
+                a[r] = [(v - f * w) % p for v, w in zip(a[r], a[c])]
+    return [row[d:] for row in a]
+
+
+def checkpd_field(A, field, device: int = 0, minors=None, primes=None) -> FieldPDCertificate:
+    """Is the symmetric matrix `A` over QQ(g) positive definite at the real embedding g -> gamma of `field` (a `NumberField`; gamma the real root its `g`
+    approximates)?  `A`: (n, n) coefficient tuples (x_0 .. x_(d-1)) of `Fraction`s or integers, entry = sum_j x_j g^j (what `vectors_to_field` uses), n <=
+    128.  An exact answer with its proof, where the reference's checkpd_cholesky(A; FF, g) (src/rounding.jl:417-472) embeds A at Arb balls and doubles the
+    precision until 2^14 bits.  `ValueError` unless A is square and symmetric.
+
+    The block is cleared of denominators and, where the minimal polynomial is not monic, rewritten in h = |lc| g, so that its leading principal minors lie
+    in Z[h]; A is positive definite iff every one of them is positive at gamma.  An empty block is positive definite; a diagonal entry <= 0 at gamma
+    answers from the host.  Otherwise: primes at which the minimal polynomial splits (`primes(field, count, start)` -> `(primes, roots)`, default
+    `split_primes`, the host scan; `functools.partial(split_primes, frobenius=field_frobenius)` scans on the device), the minors of the d residue matrices
+    of every prime (`minors(coeff_matrices, primes, roots, device=...)`, default `leading_minors_field_mod`), the coefficients mod p by the inverse
+    Vandermonde matrix of the roots, lifted by `crt_tree` against `field_minor_bounds`, and the sign of each minor at gamma by interval arithmetic on an
+    isolating interval of gamma (`ArithmeticError` naming the order if a sign stays undecided at the precision a non-zero element allows).  The walk is
+    that of `checkpd`: a prime one of whose pairs breaks down at order k is usable up to and including k."""
+    from math import gcd
+    minors_fn = leading_minors_field_mod if minors is None else minors
+    primes_fn = split_primes if primes is None else primes
+    h, lc = _field_monic(field)
+    d = len(h) - 1
+    if d < 2:
+        raise ValueError("checkpd_field: a field of degree at least 2 is needed (checkpd is the check over QQ)")
+    neg, man, exp, _ = field.g._mpf_                                # the mpmath number exactly: (-1)^neg man 2^exp
+    root = _RealRoot(h, Fraction(-int(man) if neg else int(man)) * Fraction(2) ** int(exp) * lc, int(field.prec))
+    interval = lambda: (root.lo / lc, root.hi / lc)
+    empty = lambda pd, order, scale: FieldPDCertificate(pd, [], order, scale, [], [], [], interval(), h, lc)
+    try:
+        rows_in = [list(r) for r in A]
+    except TypeError:
+        raise ValueError("checkpd_field: the block must be an (n, n) array of coefficient tuples") from None
+    n = len(rows_in)
+    if n == 0:
+        return empty(True, None, 1)
+    if any(len(r) != n for r in rows_in):
+        raise ValueError(f"checkpd_field: the block must be square, got rows of {sorted({len(r) for r in rows_in})} entries for {n} rows")
+    try:
+        rows = [[[Fraction(x) for x in e] for e in r] for r in rows_in]
+    except TypeError:
+        rows = None
+    if rows is None or any(len(e) != d for r in rows for e in r):
+        raise ValueError(f"checkpd_field: every entry must be a tuple of {d} coefficients")
+    if any(rows[i][j] != rows[j][i] for i in range(n) for j in range(i)):
+        raise ValueError("checkpd_field: the block must be symmetric")
+    L = 1
+    for r in rows:
+        for e in r:
+            for x in e:
+                L = L * x.denominator // gcd(L, x.denominator)
+    scale = L * lc ** (d - 1)                                        # sum_j x_j g^j = sum_j x_j lc^-j h^j; times L lc^(d-1) every coefficient is an integer
+    M = np.empty((d, n, n), dtype=object)
+    for i in range(n):
+        for j in range(n):
+            for c in range(d):
+                M[c, i, j] = int(rows[i][j][c] * L) * lc ** (d - 1 - c)
+    for i in range(n):
+        if root.sign([M[c, i, i] for c in range(d)], f"diagonal entry {i + 1}") <= 0:
+            return empty(False, i + 1, scale)
+    if n > MINORS_MAX_N:
+        raise ValueError(f"checkpd_field: blocks of more than {MINORS_MAX_N} rows are not supported, got {n}")
+    bounds = field_minor_bounds(M, field)
+    plist, rlist, breaks, pair_breaks, coeffs = [], [], [], [], []   # per prime: roots, first breakdown, the breakdowns of its pairs, (d, n) coefficients mod p
+    exact, done = [], 0
+    while done < n:
+        need, have = 2 * max(max(bounds[done:]), 1), _product(p for p, k in zip(plist, breaks) if k == 0)
+        count = max(1, -(-(need.bit_length() - have.bit_length() + 2) // 22))      # every prime drawn exceeds 2^22 while they last
+        count = min(count, MINORS_MAX_PRIMES)
+        batch, batch_roots = primes_fn(field, count, plist[-1] if plist else None)
+        batch = [int(p) for p in batch]
+        batch_roots = [[int(r) * lc % p for r in rr] for p, rr in zip(batch, batch_roots)]            # the roots of h: lc times those of the field's polynomial
+        res, brk = minors_fn(M, batch, batch_roots, device=device)
+        res, brk = np.asarray(res).reshape(len(batch), d, n), np.asarray(brk).reshape(len(batch), d)
+        for q, p in enumerate(batch):
+            Vinv = np.array(_mod_matrix_inverse([[pow(r, j, p) for j in range(d)] for r in batch_roots[q]], p), dtype=np.int64)
+            img = np.where(res[q] < 0, 0, res[q]).astype(np.int64)                                  # (-1 behind a breakdown: never read, see `usable`)
+            coeffs.append((Vinv @ img) % p)                                                         # d products below 2^46 each
+            ks = [int(k) for k in brk[q]]
+            pair_breaks.append(ks)
+            breaks.append(min((k for k in ks if k), default=0))
+        plist += batch
+        rlist += batch_roots
+        groups, products, order = {}, {}, done + 1
+        while order <= n:
+            usable = tuple(q for q, k in enumerate(breaks) if k == 0 or k >= order)
+            if usable not in products:
+                products[usable] = _product(plist[q] for q in usable)
+            if not usable or products[usable] <= 2 * bounds[order - 1]:
+                break
+            groups.setdefault(usable, []).append(order)
+            order += 1
+        stop = False
+        for usable, orders in groups.items():                      # (insertion order: ascending orders)
+            residues = np.array([[int(coeffs[q][c, k - 1]) for k in orders for c in range(d)] for q in usable], dtype=np.int64)
+            values, _ = crt_tree(residues, [plist[q] for q in usable])
+            for t, k in enumerate(orders):
+                minor = [int(v) for v in values[t * d:(t + 1) * d]]
+                exact.append(minor)
+                done = k
+                if root.sign(minor, f"the minor of order {k}") <= 0:
+                    stop = True
+                    break
+            if stop:
+                break
+        if stop:
+            break
+    discarded = [(p, rr[i], ks[i]) for p, rr, ks in zip(plist, rlist, pair_breaks) for i in range(d) if ks[i] != 0]
+    failed = done if stop else None
+    return FieldPDCertificate(failed is None, exact, failed, scale, plist, rlist, discarded, interval(), h, lc)

@@ -430,6 +430,21 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   clrs_config_set("modp_minors_chunk_bytes", b): the primes are taken in chunks whose residues (8 n^2 bytes per prime) stay below b bytes (0, the default: 256 MiB).
  * clrs_modp_minors_times: the milliseconds of the calling thread's last clrs_modp_minors: in the residue kernel, in the L D L^T kernel, and from the first
  *   upload to the last download (device events).
+ * clrs_modp_minors_field: clrs_modp_minors for a symmetric matrix over a number field QQ(g), M = sum_j M_j g^j with integer M_j (the
+ *   device half of rounding.checkpd_field, where the reference's checkpd_cholesky(A; FF, g), src/rounding.jl:417-472, embeds at Arb balls), host pointers, no
+ *   context.  deg in [2, 4] is the degree of the (monic) minimal polynomial f of g.  digits is [deg][nd][n][n]: the planes of M_0 .. M_(deg-1) as
+ *   clrs_modp_minors takes them, every plane symmetric.  primes holds nprimes distinct primes in [2, 2^23) and roots ([nprimes][deg]) deg distinct numbers
+ *   in [0, p) per prime: the roots of f mod p (the function does not check that they are; any distinct points give the minors of M evaluated there).
+ *   minors is [nprimes][deg][n] and breakdown [nprimes][deg]: for the pair (prime q, root i) what clrs_modp_minors returns for the integer matrix
+ *   sum_j M_j roots[q][i]^j mod primes[q], with the same conventions.  info as clrs_modp_minors, counted per pair: [1] = nprimes deg workgroups.
+ *   CLRS_ERR_INVALID before any device call, nothing written: deg outside [2, 4], n outside [1, 128], nd outside [1, 32767], nprimes outside [1, 65535], a null
+ *   pointer, a digit outside [-2^23, 2^23], a plane that is not symmetric, a modulus that is no prime in [2, 2^23), a repeated prime, a root outside [0, p),
+ *   two equal roots of one prime.  The chunks of clrs_config_set("modp_minors_chunk_bytes", b) hold 8 n^2 deg bytes per prime.
+ * clrs_modp_minors_field_times: the milliseconds of the calling thread's last clrs_modp_minors_field, as clrs_modp_minors_times gives them.
+ * clrs_modp_field_frobenius: out ([nprimes][deg]) receives, per prime, the coefficients in [0, p) of x^p mod (f, p), f = sum_j minpoly[j] x^j of degree
+ *   deg in [2, 4] (minpoly[deg] != 0), one lane per prime; -1 throughout where p divides minpoly[deg].  A prime that divides neither the leading coefficient
+ *   nor the discriminant splits f into deg distinct linear factors iff the row is (0, 1, 0, ..).  nprimes in [1, 2^20]; the primes need not be distinct.
+ *   CLRS_ERR_INVALID before any device call: deg, nprimes out of range, a null pointer, minpoly[deg] = 0, a modulus that is no prime in [2, 2^23).
  * clrs_zz_gemm: C = A B over the integers (the exact matrix arithmetic around the steps above: Gram matrices, normal equations, the
  *   checks A x == b), host pointers, no context.  A is [nda][m][k], B [ndb][k][n], C [ndc][m][n]: row-major planes of balanced base-2^24 digits, little-endian.
  *   Input digits lie in [-2^23, 2^23]; C receives the unique representation with every digit ((v + 2^23) mod 2^24) - 2^23.  info[0]: entries of C that do not
@@ -539,6 +554,10 @@ int clrs_modp_dixon_reconstruct(int device, int n, int p, int steps, const int32
 int clrs_modp_dixon_reconstruct_times(double *horner_ms, double *euclid_ms);
 int clrs_modp_minors(int device, int n, int nd, const int32_t *digits, int nprimes, const int32_t *primes, int32_t *minors, int32_t *breakdown, int32_t *info);
 int clrs_modp_minors_times(double *residues_ms, double *ldl_ms, double *total_ms);
+int clrs_modp_minors_field(int device, int n, int deg, int nd, const int32_t *digits, int nprimes, const int32_t *primes, const int32_t *roots, int32_t *minors,
+                           int32_t *breakdown, int32_t *info);
+int clrs_modp_minors_field_times(double *residues_ms, double *ldl_ms, double *total_ms);
+int clrs_modp_field_frobenius(int device, int deg, const int64_t *minpoly, int nprimes, const int32_t *primes, int32_t *out);
 int clrs_zz_gemm(int device, int m, int k, int n, int nda, const int32_t *A, int ndb, const int32_t *B, int ndc, int32_t *C, int32_t *info);
 int clrs_zz_gemm_times(double *gemm_ms, double *combine_ms, double *whole_ms);
 int clrs_modp_dixon_lift_multi(int device, int n, int m, int p, int nd, const int32_t *A_digits, int nbl, const int32_t *B_limbs, int steps, int32_t *X,
