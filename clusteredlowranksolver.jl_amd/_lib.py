@@ -166,6 +166,8 @@ SYMBOLS = {
     "clrs_modp_minors_field": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_i32, C.c_int, p_i32, p_i32, p_i32, p_i32, p_i32]),
     "clrs_modp_minors_field_times": (C.c_int, [p_d, p_d, p_d]),
     "clrs_modp_field_frobenius": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, p_i32, p_i32]),
+    "clrs_modp_field_adjugate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_i32, C.c_int, p_i32, p_i32, p_i32, p_i32, p_i32, p_i32]),
+    "clrs_modp_field_adjugate_times": (C.c_int, [p_d, p_d, p_d]),
     "clrs_zz_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, p_i32, C.c_int, p_i32, C.c_int, p_i32, p_i32]),
     "clrs_zz_gemm_times": (C.c_int, [p_d, p_d, p_d]),
     "clrs_modp_dixon_lift_multi": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, p_i32, C.c_int, p_i32, C.c_int, p_i32, p_i32, p_i32]),
@@ -244,7 +246,7 @@ def _hipcc(args):
 # translation units of libclrs_hip.so: (object, source, extra flags, predicate selecting the files it depends on)
 _UNITS = (
     ("clrs_hip.o", "clrs_hip.hip", (), lambda f: not f.startswith(("clrs_mw", "clrs_modp", "clrs_zz"))),
-    # the elimination mod p, the p-adic lifting on it, the reconstruction and the leading minors mod many primes (clrs_modp_rref, clrs_modp_dixon_lift, clrs_modp_dixon_lift_multi, clrs_modp_dixon_reconstruct, clrs_modp_minors, clrs_modp_minors_field, clrs_modp_field_frobenius) and the exact integer matrix product (clrs_zz_gemm): a small unit of its own, no multi-word flags
+    # the elimination mod p, the p-adic lifting on it, the reconstruction and the leading minors mod many primes (clrs_modp_rref, clrs_modp_dixon_lift, clrs_modp_dixon_lift_multi, clrs_modp_dixon_reconstruct, clrs_modp_minors, clrs_modp_minors_field, clrs_modp_field_frobenius, clrs_modp_field_adjugate) and the exact integer matrix product (clrs_zz_gemm): a small unit of its own, no multi-word flags
     ("clrs_modp.o", "clrs_modp.hip", (), lambda f: f.startswith("clrs_modp")),
     # the batched LLL reduction (clrs_zz_lll): exact integer rows steered by K-limb floating point, so no contraction here either; it reads the digit arithmetic
     # of the exact product and the multi-word arithmetic

@@ -349,3 +349,4 @@ extern "C" int clrs_modp_rref(int device, int nrows, int ncols, int p, const int
 #include "clrs_modp_zz_gemm.hip.h"   // clrs_zz_gemm: the exact product of integer matrices given in digit planes, one fp64 MFMA GEMM of one-digit matrices
 #include "clrs_modp_liftm.hip.h"     // clrs_modp_dixon_lift_multi: the lifting with a matrix of right-hand sides, both products of a step as fp64 MFMA GEMMs
 #include "clrs_modp_lrsys.hip.h"     // clrs_zz_lowrank_system: the rows of the rational system from low-rank constraint matrices, the digit index in the MFMA's k-extent
+#include "clrs_modp_field_adjugate.hip.h"   // clrs_modp_field_adjugate: determinant and adjugate of a matrix over a number field mod split primes, one workgroup per (prime, root)

@@ -43,7 +43,10 @@ Over a number field QQ(g) of degree 2 .. 4 the entries of the kernel vectors are
 rescue, degrees 5 .. 8), `kernel_vectors(..., rationalize=True, field=...)`, `vectors_to_field`.  Of the steps after the rounding the positive-definiteness check is built
 (`checkpd_field`, exact: the leading minors as elements of Z[g] from their images at the roots of the minimal polynomial mod primes that split it,
 clrs_modp_minors_field; `split_primes`, `field_frobenius`, `leading_minors_field_mod`, `field_minor_bounds`, `FieldPDCertificate`,
-`is_valid_solution(..., field=...)`); the basis change and the system over the field are not.
+`is_valid_solution(..., field=...)`), and so is the basis change (`B = [V | E]` and its inverse over QQ(g), src/rounding.jl:834-836, 1017-1050: the determinant and
+the adjugate as elements of Z[g] from the inverses of the residue matrices at every (split prime, root) pair, clrs_modp_field_adjugate, DESIGN.md section 25;
+`inverse_field`, `FieldInverse`, `field_adjugate_mod`, `field_adjugate_bounds`, `field_matmul`, `complete_basis_field`, `transform_field`, `undo_transform_field`,
+`basis_transformations(..., field=...)`); the system over the field and the reduction of its kernel vectors are not.
 
 The system the projection solves is assembled from an `ExactProblem` (the problem over QQ; `to_sdp` gives the numeric one) by `linear_system`
 (`partial_linearsystem`, src/interface.jl:1354-1535): per low-rank block one call of clrs_zz_lowrank_system, a row-wise Gram of long
@@ -1853,7 +1856,7 @@ def _kernel_block(N, vectors, Binv0):
 
 
 def basis_transformations(kernels, settings: Optional[RoundingSettings] = None, device: int = 0, maxprimes: int = 3, batch=None, lift=None, check: bool = True,
-                          reconstruct=None, matmul=None, reduce=None, verbose: bool = False) -> dict:
+                          reconstruct=None, matmul=None, reduce=None, verbose: bool = False, field=None, adjugate=None, primes=None) -> dict:
     """The reference's `basis_transformations` over QQ (src/rounding.jl:750-858).  `kernels` maps a block key to `(N, vectors)`: the size of the block and
     its s rational kernel vectors, each of N entries (what `vectors_to_fractions(BlockKernel)` returns).  Returns `{key: (B^T, Binv, s)}`, object arrays
     (N, N) of `Fraction`s, like the reference, in the order of `kernels`.
@@ -1871,10 +1874,22 @@ def basis_transformations(kernels, settings: Optional[RoundingSettings] = None, 
     blocks returns the matrices U, and with `settings.unimodular_transform` `B = U^T`, `Binv = inverse_qq(B)`, an integer matrix (`ArithmeticError` if
     not); without it the first s rows of U replace the vectors and the unreduced branch runs on them.  `verbose`: prints the largest entry of B after the
     reduction, as the reference does.  With `settings.reduce_kernelvectors` true and `reduce=None` this raises `NotImplementedError`: pass `reduce=`, or
-    `RoundingSettings(reduce_kernelvectors=False)`.  Number fields of degree above 1 are not built.
-    `batch` goes to `complete_basis`; `lift`, `check`, `reconstruct`, `matmul` go to `inverse_qq`."""
+    `RoundingSettings(reduce_kernelvectors=False)`.
+    `batch` goes to `complete_basis`; `lift`, `check`, `reconstruct`, `matmul` go to `inverse_qq`.
+
+    Over a number field: when the vectors hold coefficient tuples (`vectors_to_field`) and `field` is a `NumberField` of degree
+    at least 2, the unreduced branch runs over QQ(g): `B = [V | E]` with E from `complete_basis_field` (`batch`, `primes`), `Binv =
+    inverse_field(B, field, adjugate=adjugate, primes=primes, matmul=matmul, check=check).inverse`, the completion tested against the inverse in the same
+    way (the next (prime, root) pair on failure), and no normalisation (the reference normalises at degree 1 only, src/rounding.jl:844).  The matrices
+    returned are object arrays of coefficient tuples.  The reduction of kernel vectors over number fields is not built: with
+    `settings.reduce_kernelvectors` true this raises `NotImplementedError`.  Without `field` tuples are refused as before."""
     settings = RoundingSettings() if settings is None else settings
     if any(isinstance(x, tuple) for _, vectors in kernels.values() for v in vectors for x in v):
+        if field is not None and getattr(field, "degree", 1) >= 2:
+            if settings.reduce_kernelvectors:
+                raise NotImplementedError("basis_transformations: the reduction of kernel vectors over number fields is not built; pass "
+                                          "RoundingSettings(reduce_kernelvectors=False)")
+            return _basis_transformations_field(kernels, field, device, maxprimes, batch, check, matmul, adjugate, primes)
         raise NotImplementedError("basis_transformations: the kernel vectors hold coefficient tuples over a number field (vectors_to_field); the basis change "
                                   "over a field of degree above 1 -- the inverse of [V | E] over QQ(g) -- is not built yet, only the rounding of the vectors is")
     if settings.reduce_kernelvectors and reduce is None:
@@ -3054,7 +3069,6 @@ def checkpd_field(A, field, device: int = 0, minors=None, primes=None) -> FieldP
     Vandermonde matrix of the roots, lifted by `crt_tree` against `field_minor_bounds`, and the sign of each minor at gamma by interval arithmetic on an
     isolating interval of gamma (`ArithmeticError` naming the order if a sign stays undecided at the precision a non-zero element allows).  The walk is
     that of `checkpd`: a prime one of whose pairs breaks down at order k is usable up to and including k."""
-    from math import gcd
     minors_fn = leading_minors_field_mod if minors is None else minors
     primes_fn = split_primes if primes is None else primes
     h, lc = _field_monic(field)
@@ -3082,17 +3096,11 @@ def checkpd_field(A, field, device: int = 0, minors=None, primes=None) -> FieldP
         raise ValueError(f"checkpd_field: every entry must be a tuple of {d} coefficients")
     if any(rows[i][j] != rows[j][i] for i in range(n) for j in range(i)):
         raise ValueError("checkpd_field: the block must be symmetric")
-    L = 1
-    for r in rows:
-        for e in r:
-            for x in e:
-                L = L * x.denominator // gcd(L, x.denominator)
-    scale = L * lc ** (d - 1)                                        # sum_j x_j g^j = sum_j x_j lc^-j h^j; times L lc^(d-1) every coefficient is an integer
-    M = np.empty((d, n, n), dtype=object)
+    Af = np.empty((n, n), dtype=object)
     for i in range(n):
         for j in range(n):
-            for c in range(d):
-                M[c, i, j] = int(rows[i][j][c] * L) * lc ** (d - 1 - c)
+            Af[i, j] = tuple(rows[i][j])
+    scale, M = _field_integer_form(Af, h, lc)
     for i in range(n):
         if root.sign([M[c, i, i] for c in range(d)], f"diagonal entry {i + 1}") <= 0:
             return empty(False, i + 1, scale)
@@ -3146,3 +3154,436 @@ def checkpd_field(A, field, device: int = 0, minors=None, primes=None) -> FieldP
     discarded = [(p, rr[i], ks[i]) for p, rr, ks in zip(plist, rlist, pair_breaks) for i in range(d) if ks[i] != 0]
     failed = done if stop else None
     return FieldPDCertificate(failed is None, exact, failed, scale, plist, rlist, discarded, interval(), h, lc)
+
+
+# ---- the basis change over a number field: adjugate and determinant in Z[h] from split primes (src/rounding.jl:834-836, 1017-1050; clrs_modp_field_adjugate) ----
+def _square_coeff_matrices(coeff_matrices, what):
+    """-> object array (d, n, n) of Python integers: d >= 2 square matrices of one shape, not necessarily symmetric"""
+    mats = [_integer_matrix(M, what) for M in coeff_matrices]
+    if len(mats) < 2 or any(m.shape != mats[0].shape for m in mats) or mats[0].shape[0] != mats[0].shape[1]:
+        raise ValueError(f"{what}: at least two square coefficient matrices of one shape are needed")
+    n = mats[0].shape[0]
+    out = np.empty((len(mats), n, n), dtype=object)
+    for j, m in enumerate(mats):
+        out[j].flat = [int(v) for v in m.flat]
+    return out
+
+
+def field_adjugate_mod(coeff_matrices, primes, roots, device: int = 0):
+    """The determinant and the adjugate of M = sum_j M_j g^j evaluated at g = roots[q][i] mod primes[q], for every pair, on the device: one call of
+    clrs_modp_field_adjugate.  `coeff_matrices`: the d (2 .. 4) square integer matrices M_0 .. M_(d-1) (n <= 128, Python integers of any size, not
+    necessarily symmetric); `primes` descending, in [2, 2^23), at most 65535; `roots` (len(primes), d): distinct numbers in [0, p) per prime (for the
+    images of det M and adj M in Z[g]: the roots of the monic minimal polynomial of g mod p).  Returns `(adj, det, breakdown)`: int32
+    (len(primes), d, n, n), (len(primes), d) and (len(primes), d).  Per pair: det M(r) mod p and adj M(r) = det M(r) M(r)^-1 mod p with breakdown 0; or,
+    where M(r) is singular mod p, det 0, adj -1 throughout and breakdown c + 1, c the first column that depends on the columns before it.  The counters
+    are kept in `field_adjugate_mod.last_info` (`[LDS bytes per workgroup, workgroups, singular pairs, 0]`)."""
+    a = _square_coeff_matrices(coeff_matrices, "field_adjugate_mod")
+    d, n = a.shape[0], a.shape[1]
+    pr = np.ascontiguousarray([int(p) for p in primes], dtype=np.int64)
+    if d not in FIELD_MINORS_DEGREES:
+        raise ValueError(f"field_adjugate_mod: the degree must be one of {FIELD_MINORS_DEGREES}, got {d}")
+    if n < 1 or n > MINORS_MAX_N:
+        raise ValueError(f"field_adjugate_mod: n must lie in [1, {MINORS_MAX_N}], got {n}")
+    if pr.size < 1 or pr.size > MINORS_MAX_PRIMES or pr.min() < 2 or pr.max() >= MODP_PRIME_LIMIT:
+        raise ValueError(f"field_adjugate_mod: between 1 and {MINORS_MAX_PRIMES} primes in [2, 2^23) are needed")
+    rt = np.ascontiguousarray(np.asarray([[int(r) for r in row] for row in roots], dtype=np.int64).reshape(pr.size, -1))
+    if rt.shape != (pr.size, d) or rt.min() < 0 or np.any(rt >= pr[:, None]):
+        raise ValueError(f"field_adjugate_mod: roots must be ({pr.size}, {d}) with every root in [0, p)")
+    pr, rt = pr.astype(np.int32), rt.astype(np.int32)
+    digits = np.ascontiguousarray(np.swapaxes(to_balanced_digits(a), 0, 1))                 # (d, nd, n, n)
+    adj, det = np.full((pr.size, d, n, n), -2, np.int32), np.full((pr.size, d), -2, np.int32)
+    breakdown, info = np.full((pr.size, d), -2, np.int32), np.zeros(4, np.int32)
+    ptr = lambda v: v.ctypes.data_as(_lib.p_i32)
+    _lib.check(_lib.load().clrs_modp_field_adjugate(int(device), n, d, digits.shape[1], ptr(digits), pr.size, ptr(pr), ptr(rt), ptr(adj), ptr(det), ptr(breakdown),
+                                                    ptr(info)))
+    field_adjugate_mod.last_info = [int(v) for v in info]
+    return adj, det, breakdown
+
+
+field_adjugate_mod.last_info = None
+
+
+def _field_hadamard(a, h):
+    """(H, factor) for the integer coefficient matrices `a` (d, n, n) of M = sum_j M_j h^j, h a root of the monic integer polynomial `h`: with rho >= every
+    |conjugate of h| and E = sum_j |M_j| rho^j entry by entry, H = prod_i max(1, ceil ||row i of E||_2) bounds every conjugate of every minor of M of
+    order n - 1 and n (Hadamard, rows of norm below 1 counted as 1 so that leaving a row out never raises the bound); `factor` (a `Fraction`) turns a
+    bound on the conjugates of an element of Z[h] into one on its coefficients, max_j d sum_b |T^-1[j][b]| rho^b (`field_minor_bounds`)."""
+    d, n = a.shape[0], a.shape[1]
+    rho = _root_bound(h)
+    H = 1
+    for i in range(n):
+        s = sum(sum(abs(int(a[j, i, c])) * rho ** j for j in range(d)) ** 2 for c in range(n))
+        r = _isqrt(s)
+        H *= max(1, r if r * r == s else r + 1)
+    Tinv = _trace_matrix_inverse(h)
+    factor = max(sum((abs(Tinv[j][b]) * d * rho ** b for b in range(d)), Fraction(0)) for j in range(d))
+    return H, factor
+
+
+def field_adjugate_bounds(coeff_matrices, field) -> int:
+    """A Python integer `C` with |c| <= C for every coefficient c in Z[h] of det M and of every entry of adj M, M = sum_j M_j h^j with the square integer
+    matrices `coeff_matrices` and h the generator `inverse_field` normalises to (lc(f) g: g itself where the minimal polynomial of `field` is monic):
+    C = ceil(H factor) with `(H, factor)` of `_field_hadamard`.  DESIGN.md section 25."""
+    a = _square_coeff_matrices(coeff_matrices, "field_adjugate_bounds")
+    h, _ = _field_monic(field)
+    if a.shape[0] != len(h) - 1:
+        raise ValueError(f"field_adjugate_bounds: {len(h) - 1} coefficient matrices are needed for a field of degree {len(h) - 1}, got {a.shape[0]}")
+    H, factor = _field_hadamard(a, h)
+    return -((-H * factor.numerator) // factor.denominator)
+
+
+def _minpoly_of(field) -> list:
+    return [int(c) for c in (field.minpoly if hasattr(field, "minpoly") else field)]
+
+
+def _field_matrix(M, d: int, what: str) -> np.ndarray:
+    """a matrix of coefficient tuples (nested lists, or an object array of tuples, or an array (rows, cols, d)) -> an object array (rows, cols) whose
+    entries are tuples of d `Fraction`s"""
+    try:
+        rows = [list(r) for r in M]
+    except TypeError:
+        raise ValueError(f"{what}: a matrix of coefficient tuples is needed") from None
+    cols = len(rows[0]) if rows else (M.shape[1] if isinstance(M, np.ndarray) and M.ndim >= 2 else 0)
+    out = np.empty((len(rows), cols), dtype=object)
+    for i, r in enumerate(rows):
+        if len(r) != cols:
+            raise ValueError(f"{what}: rows of {cols} and of {len(r)} entries")
+        for j, e in enumerate(r):
+            try:
+                t = tuple(Fraction(x) for x in e)
+            except TypeError:
+                t = ()
+            if len(t) != d:
+                raise ValueError(f"{what}: every entry must be a tuple of {d} coefficients")
+            out[i, j] = t
+    return out
+
+
+def _field_fold(t, f) -> tuple:
+    """the coefficients t_0 .. t_(2d-2) of a polynomial in g reduced by the minimal polynomial f (degree d, not necessarily monic): a tuple of d Fractions"""
+    d = len(f) - 1
+    t = list(t)
+    for k in range(len(t) - 1, d - 1, -1):
+        c = t[k] if f[d] == 1 else t[k] / f[d]                       # (a monic f keeps integers integers)
+        if c:
+            for j in range(d):
+                t[k - d + j] -= c * f[j]
+    return tuple(t[:d])
+
+
+def field_matmul(A, B, field, matmul=None, device: int = 0) -> np.ndarray:
+    """The product of two matrices over QQ(g): `A` (m, k) and `B` (k, n) of coefficient tuples of `Fraction`s or integers in g (what `vectors_to_field`
+    uses), `field` a `NumberField` or the coefficient list of its minimal polynomial.  Returns an object array (m, n) of tuples of `Fraction`s.
+    With `matmul` None everything is done in `Fraction`s.  With `matmul(A, B, device=...)` (`zz_matmul`) the coefficient planes A_0 .. A_(d-1) and B_0 ..
+    B_(d-1), each operand over the common denominator of its entries, are stacked and multiplied as ONE integer product `[A_0; ..; A_(d-1)] [B_0 | .. |
+    B_(d-1)]`: block (a, b) is A_a B_b, the blocks with a + b = e add up to the coefficient of g^e, and the 2d - 1 coefficients are folded by the
+    minimal polynomial."""
+    f = _minpoly_of(field)
+    d = len(f) - 1
+    Af, Bf = _field_matrix(A, d, "field_matmul"), _field_matrix(B, d, "field_matmul")
+    m, k, n = Af.shape[0], Af.shape[1], Bf.shape[1]
+    if Bf.shape[0] != k:
+        raise ValueError(f"field_matmul: the shapes {Af.shape} and {Bf.shape} do not match")
+    out = np.empty((m, n), dtype=object)
+    if m == 0 or n == 0:
+        return out
+    if matmul is None or k == 0:
+        for i in range(m):
+            for j in range(n):
+                t = [Fraction(0)] * (2 * d - 1)
+                for l in range(k):
+                    x, y = Af[i, l], Bf[l, j]
+                    for a in range(d):
+                        if x[a]:
+                            for b in range(d):
+                                t[a + b] += x[a] * y[b]
+                out[i, j] = _field_fold(t, f)
+        return out
+    (an, al), (bn, bl) = _common_denominator(x for e in Af.flat for x in e), _common_denominator(x for e in Bf.flat for x in e)
+    an, bn = an.reshape(m, k, d), bn.reshape(k, n, d)
+    left, right = np.empty((d * m, k), dtype=object), np.empty((k, d * n), dtype=object)
+    for a in range(d):
+        left[a * m:(a + 1) * m] = an[:, :, a]
+        right[:, a * n:(a + 1) * n] = bn[:, :, a]
+    prod = _matmul_matrix(matmul, left, right, device)
+    den = al * bl
+    for i in range(m):
+        for j in range(n):
+            t = [0] * (2 * d - 1)
+            for a in range(d):
+                for b in range(d):
+                    t[a + b] += int(prod[a * m + i, b * n + j])
+            out[i, j] = _field_fold([Fraction(v, den) for v in t], f)
+    return out
+
+
+@dataclasses.dataclass
+class FieldInverse:
+    """What `inverse_field` computes for a square matrix B over QQ(g).  `inverse`: B^-1, an object array (n, n) of tuples of `Fraction`s in g.  `minpoly`,
+    `generator_scale`: the monic integer minimal polynomial of h = generator_scale g (generator_scale = |lc| of the field's minimal polynomial) in which the
+    next two are expressed.  `scale`: the positive integer D with D B = M = sum_j M_j h^j, M_j integer.  `adjugate`: adj M, an object array (n, n) of tuples
+    of d integers, and `det` = det M, a list of d integers, both exact: M adj M = det M I in Z[h], and B^-1 = scale adj M / det M.  `primes`: every prime
+    given to the device, in order, `roots` their roots of `minpoly`, row by row; `discarded`: the primes one of whose pairs was singular (they divide the
+    norm of det M) and took no part in the lifting."""
+    inverse: np.ndarray
+    adjugate: np.ndarray
+    det: list
+    scale: int
+    minpoly: list
+    generator_scale: int
+    primes: list
+    roots: list
+    discarded: list
+
+
+def _field_element_inverse(c, h) -> tuple:
+    """the inverse in QQ[x] / (h) of the element with coefficients c (h monic of degree d): the d x d `Fraction` solve (multiplication by c) y = 1;
+    `ZeroDivisionError` for a zero divisor"""
+    d = len(h) - 1
+    cols, cur = [], tuple(Fraction(v) for v in c)
+    for _ in range(d):                                               # column j: c x^j
+        cols.append(cur)
+        cur = _field_fold((Fraction(0),) + cur, h)
+    A = [[cols[j][i] for j in range(d)] + [Fraction(int(i == 0))] for i in range(d)]
+    for k in range(d):
+        piv = next((r for r in range(k, d) if A[r][k] != 0), None)
+        if piv is None:
+            raise ZeroDivisionError("the element is not invertible in the field")
+        A[k], A[piv] = A[piv], A[k]
+        A[k] = [v / A[k][k] for v in A[k]]
+        for r in range(d):
+            if r != k and A[r][k] != 0:
+                A[r] = [v - A[r][k] * w for v, w in zip(A[r], A[k])]
+    return tuple(A[i][d] for i in range(d))
+
+
+def _field_integer_form(Bf, h, lc):
+    """(scale, M): the object array (d, rows, cols) of the integers M_j with scale B = sum_j M_j h^j, h = lc g, for a matrix B of tuples of `Fraction`s in g:
+    sum_j x_j g^j = sum_j x_j lc^-j h^j, and times scale = L lc^(d-1), L the least common denominator of the coefficients, every coefficient is an integer
+    (the normal form of `checkpd_field` and `inverse_field`)"""
+    from math import gcd
+    d = len(h) - 1
+    L = 1
+    for e in Bf.flat:
+        for x in e:
+            L = L * x.denominator // gcd(L, x.denominator)
+    M = np.empty((d,) + Bf.shape, dtype=object)
+    for i in range(Bf.shape[0]):
+        for j in range(Bf.shape[1]):
+            for c in range(d):
+                M[c, i, j] = int(Bf[i, j][c] * L) * lc ** (d - 1 - c)
+    return L * lc ** (d - 1), M
+
+
+def inverse_field(B, field, device: int = 0, adjugate=None, primes=None, matmul=None, check: bool = True):
+    """The inverse of a square matrix `B` over QQ(g) (the reference's `inv(B)` over `FF`, src/rounding.jl:836), exactly and with a proven bound: a
+    `FieldInverse`.  `B`: (n, n) coefficient tuples of `Fraction`s or integers in g, n <= 128; `field` a `NumberField`.  A field of degree 1, or entries
+    that are not tuples, go to `inverse_qq` (whose result is returned).
+
+    B is cleared of denominators and rewritten in h = |lc| g exactly as `checkpd_field` does: scale B = M = sum_j M_j h^j.  det M and the entries of adj M lie
+    in Z[h] with coefficients of size at most C = `field_adjugate_bounds(M, field)`.  Split primes are drawn with `primes(field, count, start)` ->
+    `(primes, roots)` (default `split_primes`) until their product exceeds 2 C -- the fewest that do, every prime being below 2^23 -- and go to
+    `adjugate(coeff_matrices, primes, roots, device=...)` (default `field_adjugate_mod`, one device call).  A prime with a singular pair divides the norm of
+    det M; it is recorded in `discarded`, left out, and replaced by further primes.  |Norm(det M)| <= H^d (H the Hadamard bound of `_field_hadamard`), so once
+    the product of the discarded primes exceeds H^d the matrix is singular: `SingularSystemError`, a proof.  Per prime the d images give the coefficients
+    mod p by the inverse Vandermonde matrix of the roots; `crt_tree` lifts them to the symmetric range, where they are the coefficients themselves.
+    With `check`, M adj M == det M I is verified exactly through `field_matmul(..., matmul=matmul)` (`ArithmeticError` otherwise).  Finally
+    B^-1 = scale adj M / det M, the inverse of det M by a d x d `Fraction` solve, rewritten in g."""
+    d = field.degree if hasattr(field, "degree") else 1
+    rows_in = [list(r) for r in B]
+    if d < 2 or not any(isinstance(x, tuple) for r in rows_in for x in r):
+        return inverse_qq([[x[0] if isinstance(x, tuple) else x for x in r] for r in rows_in], device=device, check=check, matmul=matmul)
+    adj_fn = field_adjugate_mod if adjugate is None else adjugate
+    primes_fn = split_primes if primes is None else primes
+    h, lc = _field_monic(field)
+    Bf = _field_matrix(rows_in, d, "inverse_field")
+    n = Bf.shape[0]
+    if Bf.shape[1] != n:
+        raise ValueError(f"inverse_field: the matrix must be square, got {Bf.shape[0]} x {Bf.shape[1]}")
+    if n == 0:
+        return FieldInverse(np.empty((0, 0), dtype=object), np.empty((0, 0), dtype=object), [1] + [0] * (d - 1), 1, h, lc, [], [], [])
+    if n > MINORS_MAX_N:
+        raise ValueError(f"inverse_field: matrices of more than {MINORS_MAX_N} rows are not supported, got {n}")
+    scale, M = _field_integer_form(Bf, h, lc)
+    H, factor = _field_hadamard(M, h)
+    need = 2 * (-((-H * factor.numerator) // factor.denominator))
+    plist, rlist, discarded, good, coeffs, pending, pending_roots = [], [], [], [], [], [], []
+    while True:
+        have = _product(good) * _product(pending)
+        if have <= need:                                             # every prime is below 2^23: no fewer than this many more will do
+            count = max(1, -(-(need // have).bit_length() // 23))
+            batch, batch_roots = primes_fn(field, count, (pending or plist or [None])[-1])
+            pending += [int(p) for p in batch]
+            pending_roots += [[int(r) * lc % int(p) for r in rr] for p, rr in zip(batch, batch_roots)]     # the roots of h: lc times those of the field's polynomial
+            continue
+        if not pending:
+            break
+        for at in range(0, len(pending), MINORS_MAX_PRIMES):
+            pp, rr = pending[at:at + MINORS_MAX_PRIMES], pending_roots[at:at + MINORS_MAX_PRIMES]
+            adj, det, brk = adj_fn(M, pp, rr, device=device)
+            adj, det, brk = np.asarray(adj).reshape(len(pp), d, n * n), np.asarray(det).reshape(len(pp), d), np.asarray(brk).reshape(len(pp), d)
+            for q, p in enumerate(pp):
+                if np.any(brk[q] != 0):
+                    discarded.append(p)
+                    continue
+                Vinv = np.array(_mod_matrix_inverse([[pow(r, j, p) for j in range(d)] for r in rr[q]], p), dtype=np.int64)
+                img = np.concatenate([det[q].reshape(d, 1), adj[q]], axis=1).astype(np.int64)
+                good.append(p)
+                coeffs.append(((Vinv @ img) % p).reshape(-1))                                       # d products below 2^46 each; [coefficient][det, entries]
+        plist += pending
+        rlist += pending_roots
+        pending, pending_roots = [], []
+        if _product(discarded) > H ** d:
+            raise SingularSystemError(f"inverse_field: the matrix is singular: the split primes {discarded} divide the norm of its determinant, and their "
+                                      f"product exceeds the bound H^d on that norm")
+    coeffs, values = np.array(coeffs, dtype=np.int64), []
+    for at in range(0, coeffs.shape[1], 8192):                       # (in slices: crt_tree holds its leaves as Python integers)
+        values += crt_tree(coeffs[:, at:at + 8192], good)[0]
+    values = np.array([int(v) for v in values], dtype=object).reshape(d, 1 + n * n)
+    detc = [int(v) for v in values[:, 0]]
+    adjM = np.empty((n, n), dtype=object)
+    for i in range(n):
+        for j in range(n):
+            adjM[i, j] = tuple(int(v) for v in values[:, 1 + i * n + j])
+    if not any(detc):
+        raise ArithmeticError("inverse_field: the determinant lifted to zero although no pair was singular")
+    if check:
+        Mh = np.empty((n, n), dtype=object)
+        for i in range(n):
+            for j in range(n):
+                Mh[i, j] = tuple(int(M[c, i, j]) for c in range(d))
+        prod = field_matmul(Mh, adjM, h, matmul=matmul, device=device)
+        want, zero = tuple(Fraction(v) for v in detc), (Fraction(0),) * d
+        if any(prod[i, j] != (want if i == j else zero) for i in range(n) for j in range(n)):
+            raise ArithmeticError("inverse_field: M adj(M) != det(M) I")
+    num, den = _common_denominator(_field_element_inverse(detc, h))                              # 1 / det M = (sum_b num_b h^b) / den: the products below stay integers
+    inv = np.empty((n, n), dtype=object)
+    for i in range(n):
+        for j in range(n):
+            t = [0] * (2 * d - 1)
+            for a, x in enumerate(adjM[i, j]):
+                if x:
+                    for b in range(d):
+                        t[a + b] += x * int(num[b])
+            inv[i, j] = tuple(Fraction(scale * y * lc ** c, den) for c, y in enumerate(_field_fold(t, h)))      # sum_c y_c h^c = sum_c y_c lc^c g^c
+    return FieldInverse(inv, adjM, detc, scale, h, lc, plist, rlist, discarded)
+
+
+def _field_completions(V, field, maxprimes, device, batch, primes):
+    """the generator behind `complete_basis_field`: yields a `PivotList` for every (split prime, root) pair, in order, at which the columns of V stay
+    independent; at most `maxprimes` primes; `ValueError` when there is none"""
+    batch = rref_mod_p if batch is None else batch
+    primes_fn = split_primes if primes is None else primes
+    if int(maxprimes) < 1:
+        raise ValueError(f"complete_basis_field: maxprimes must be at least 1, got {maxprimes}")
+    h, lc = _field_monic(field)
+    d = len(h) - 1
+    Vf = _field_matrix(V, d, "complete_basis_field")
+    N, s = Vf.shape
+    if s > N:
+        raise ValueError(f"complete_basis_field: {s} vectors of {N} entries cannot be independent")
+    if s == 0:
+        yield PivotList(range(N))
+        return
+    rows = [_field_integer_form(Vf[r:r + 1], h, lc)[1][:, 0, :] for r in range(N)]           # every row over its own denominator: (d, s) integers in h
+    tried, start, accepted = [], None, False
+    for _ in range(int(maxprimes)):
+        (p,), (rr,) = primes_fn(field, 1, start)
+        p, start = int(p), int(p)
+        tried.append(p)
+        for r in rr:
+            rh = int(r) * lc % p
+            M = np.zeros((N, s + N), dtype=object)
+            for i in range(N):
+                M[i, :s] = [sum(int(rows[i][c, j]) * pow(rh, c, p) for c in range(d)) % p for j in range(s)]
+                M[i, s + i] = 1
+            pivots = [int(c) for c in batch(M, p, device=device)[0]]
+            if pivots[:s] == list(range(s)):
+                if len(pivots) != N:
+                    raise ArithmeticError(f"complete_basis_field: {len(pivots)} pivots for {N} rows at p = {p}")
+                out = PivotList([c - s for c in pivots[s:]], tried, p)
+                out.root = int(r)
+                accepted = True
+                yield out
+    if not accepted:
+        raise ValueError(f"complete_basis_field: the columns of V are dependent at every root of every prime tried ({tried})")
+
+
+def complete_basis_field(V, field, maxprimes: int = 3, device: int = 0, batch=None, primes=None) -> PivotList:
+    """`complete_basis` for vectors over QQ(g): the standard basis vectors that complete the independent columns of `V` ((N, s) coefficient tuples) to a
+    basis of QQ(g)^N, by the greedy choice of the reference (src/rounding.jl:1032-1049), decided at ONE (split prime, root) pair: g -> r is a ring map
+    to F_p, so the pivot columns of the reduced row-echelon form of the residue matrix `[V(r) mod p | I_N]` (every row of V cleared of denominators first)
+    are those over the field unless p divides a deciding minor at that root, which `basis_transformations` rules out afterwards from the inverse.  The pairs
+    are taken prime by prime (`primes(field, count, start)`, default `split_primes`; at most `maxprimes` primes) and root by root; a pair is accepted only
+    when the first s pivots are the columns 0 .. s - 1.  `batch(A, p, device=...)` -> `(pivots, rank)` replaces the device call (default `rref_mod_p`).
+    Returns a `PivotList` of N - s indices with `.p`, `.primes` and `.root` (the root of the field's minimal polynomial); `ValueError` when no pair is
+    accepted."""
+    return next(_field_completions(V, field, maxprimes, device, batch, primes))
+
+
+def _field_transform_products(P, M, field, matmul, device):
+    return field_matmul(field_matmul(P, M, field, matmul=matmul, device=device), P.T, field, matmul=matmul, device=device)
+
+
+def transform_field(M, Binv, s: int, field, matmul=None, device: int = 0) -> np.ndarray:
+    """`transform` over QQ(g): `Binv[s:, :] M Binv^T[:, s:]` for (N, N) matrices of coefficient tuples, an object array (N - s, N - s) of tuples; the two
+    products through `field_matmul` (`matmul` as there)."""
+    d = len(_minpoly_of(field)) - 1
+    Mf, Bf, s = _field_matrix(M, d, "transform_field"), _field_matrix(Binv, d, "transform_field"), int(s)
+    N = Bf.shape[0]
+    if Bf.shape[1] != N or Mf.shape != (N, N) or not 0 <= s <= N:
+        raise ValueError(f"transform_field: M and Binv must be (N, N) and 0 <= s <= N, got {Mf.shape}, {Bf.shape} and s = {s}")
+    return _field_transform_products(Bf[s:, :], Mf, field, matmul, device)
+
+
+def undo_transform_field(Mt, Binv, s: int, field, matmul=None, device: int = 0) -> np.ndarray:
+    """`undo_transform` over QQ(g): `Mt` ((N - s, N - s) coefficient tuples) padded with s zero rows and columns in front and multiplied by `Binv^T` from
+    the left and `Binv` from the right, through `field_matmul`."""
+    d = len(_minpoly_of(field)) - 1
+    Bf, Mf, s = _field_matrix(Binv, d, "undo_transform_field"), _field_matrix(Mt, d, "undo_transform_field"), int(s)
+    N = Bf.shape[0]
+    if Bf.shape[1] != N or not 0 <= s <= N or Mf.shape != (N - s, N - s):
+        raise ValueError(f"undo_transform_field: Binv must be (N, N) and Mt (N - s, N - s), got {Bf.shape}, {Mf.shape} and s = {s}")
+    padded = np.empty((N, N), dtype=object)
+    for i in range(N):
+        for j in range(N):
+            padded[i, j] = Mf[i - s, j - s] if i >= s and j >= s else (Fraction(0),) * d
+    return _field_transform_products(Bf.T, padded, field, matmul, device)
+
+
+def _basis_transformations_field(kernels, field, device, maxprimes, batch, check, matmul, adjugate, primes) -> dict:
+    """the unreduced branch of `basis_transformations` over QQ(g): B = [V | E], Binv = inverse_field(B).inverse, not normalised"""
+    d = field.degree
+    zero, one = (Fraction(0),) * d, (Fraction(1),) + (Fraction(0),) * (d - 1)
+    out = {}
+    for key, (N, vectors) in kernels.items():
+        N, s = int(N), len(vectors)
+        B = np.empty((N, N), dtype=object)
+        for i in range(N):
+            for j in range(N):
+                B[i, j] = one if i == j and s == 0 else zero
+        if s == 0:
+            out[key] = (B.T.copy(), B.copy(), 0)
+            continue
+        for c, v in enumerate(vectors):
+            if len(v) != N:
+                raise ValueError(f"basis_transformations: block {key!r}: vector {c} has {len(v)} entries for a block of size {N}")
+            column = _field_matrix([[x if isinstance(x, tuple) else (x,) + (0,) * (d - 1) for x in v]], d, "basis_transformations")
+            for i in range(N):
+                B[i, c] = column[0, i]
+        Binv = None
+        completions = _field_completions(B[:, :s], field, maxprimes, device, batch, primes)
+        for extra in completions:
+            for i in range(N):
+                for c, j in enumerate(extra):
+                    B[i, s + c] = one if i == j else zero
+            Binv = inverse_field(B, field, device=device, adjugate=adjugate, primes=primes, matmul=matmul, check=check).inverse
+            taken = set(extra)
+            if all(not any(Binv[s + c, i]) for i in range(N) if i not in taken for c, j in enumerate(extra) if j > i):
+                break
+            Binv = None
+        completions.close()
+        if Binv is None:
+            raise ArithmeticError(f"basis_transformations: block {key!r}: no pair gave the greedy completion of the kernel vectors")
+        out[key] = (B.T.copy(), Binv, s)
+    return out

@@ -445,6 +445,20 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   deg in [2, 4] (minpoly[deg] != 0), one lane per prime; -1 throughout where p divides minpoly[deg].  A prime that divides neither the leading coefficient
  *   nor the discriminant splits f into deg distinct linear factors iff the row is (0, 1, 0, ..).  nprimes in [1, 2^20]; the primes need not be distinct.
  *   CLRS_ERR_INVALID before any device call: deg, nprimes out of range, a null pointer, minpoly[deg] = 0, a modulus that is no prime in [2, 2^23).
+ * clrs_modp_field_adjugate: the determinant and the adjugate of a square matrix over a number field, M = sum_j M_j g^j with integer M_j, at every (prime,
+ *   root) pair (the device half of rounding.inverse_field, the reference's inv(B) of the basis change, src/rounding.jl:834-836), host
+ *   pointers, no context.  deg, digits ([deg][nd][n][n], the planes NOT symmetric), primes and roots as clrs_modp_minors_field takes them, and the primes
+ *   descending.  adj is [nprimes][deg][n][n]: matrix (q, i) receives det M(r) M(r)^-1 mod p in [0, p) for r = roots[q][i], p = primes[q], row-major; det
+ *   ([nprimes][deg]) receives det M(r) mod p.  A pair whose matrix is singular mod p has det 0, adj -1 throughout and breakdown[q][i] = c + 1, c the first
+ *   column that depends on the columns before it mod p; breakdown is 0 otherwise.  One workgroup per pair, the matrix resident in LDS, Gauss-Jordan with
+ *   row exchanges (the first non-zero entry of a column among the rows not yet used); every output is independent of the pivots chosen.  info[0]: the LDS
+ *   bytes of a workgroup; info[1]: workgroups launched (nprimes deg); info[2]: singular pairs; info[3]: impossibilities (a pivot, a determinant or an entry
+ *   that is no residue): non-zero gives CLRS_ERR_HIP and leaves adj, det and breakdown untouched.  CLRS_ERR_INVALID before any device call, nothing
+ *   written: deg outside [2, 4], n outside [1, 128], nd outside [1, 32767], nprimes outside [1, 65535], a null pointer, a digit outside [-2^23, 2^23], a
+ *   modulus that is no prime in [2, 2^23), primes that do not descend (a repeated prime among them), a root outside [0, p), two equal roots of one prime.
+ *   The chunks of clrs_config_set("modp_minors_chunk_bytes", b) hold 8 n^2 deg bytes of residues per prime.
+ * clrs_modp_field_adjugate_times: the milliseconds of the calling thread's last clrs_modp_field_adjugate: in the residue kernel, in the Gauss-Jordan
+ *   kernel, and from the first upload to the last download (device events).
  * clrs_zz_gemm: C = A B over the integers (the exact matrix arithmetic around the steps above: Gram matrices, normal equations, the
  *   checks A x == b), host pointers, no context.  A is [nda][m][k], B [ndb][k][n], C [ndc][m][n]: row-major planes of balanced base-2^24 digits, little-endian.
  *   Input digits lie in [-2^23, 2^23]; C receives the unique representation with every digit ((v + 2^23) mod 2^24) - 2^23.  info[0]: entries of C that do not
@@ -558,6 +572,9 @@ int clrs_modp_minors_field(int device, int n, int deg, int nd, const int32_t *di
                            int32_t *breakdown, int32_t *info);
 int clrs_modp_minors_field_times(double *residues_ms, double *ldl_ms, double *total_ms);
 int clrs_modp_field_frobenius(int device, int deg, const int64_t *minpoly, int nprimes, const int32_t *primes, int32_t *out);
+int clrs_modp_field_adjugate(int device, int n, int deg, int nd, const int32_t *digits, int nprimes, const int32_t *primes, const int32_t *roots, int32_t *adj,
+                             int32_t *det, int32_t *breakdown, int32_t *info);
+int clrs_modp_field_adjugate_times(double *residues_ms, double *gj_ms, double *total_ms);
 int clrs_zz_gemm(int device, int m, int k, int n, int nda, const int32_t *A, int ndb, const int32_t *B, int ndc, int32_t *C, int32_t *info);
 int clrs_zz_gemm_times(double *gemm_ms, double *combine_ms, double *whole_ms);
 int clrs_modp_dixon_lift_multi(int device, int n, int m, int p, int nd, const int32_t *A_digits, int nbl, const int32_t *B_limbs, int steps, int32_t *X,
