@@ -151,6 +151,8 @@ SYMBOLS = {
     "clrs_mw_rank_reveal": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i32, p_i32, p_d, p_d, p_i32, p_i32, p_d, p_d]),
     "clrs_mw_constraint_dependencies": (C.c_int, [C.c_void_p, p_d, p_i32, p_i32, p_d, p_d]),
     "clrs_mw_gemm": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(MwGemmJob), p_d, C.c_int64, p_d, C.c_int64, p_d, C.c_int64]),
+    "clrs_mw_posv": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_d, C.c_int, p_d, C.c_int, p_d, C.c_int, p_i32]),
+    "clrs_mw_posv_times": (C.c_int, [p_d, p_d, p_d]),
     "clrs_mw_kernel_vectors": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i32, p_d, p_d, C.c_int, C.c_double, C.c_int, C.c_double, p_i32, p_i32, p_i32, p_i32, p_d, p_d,
                                          p_d, p_d]),
     "clrs_mw_rationalize": (C.c_int, [C.c_int, C.c_int, C.c_int, p_d, C.c_int, C.c_double, p_d, p_d, p_i32, p_d]),

@@ -25,6 +25,7 @@
 #include "clrs_mw_ipm.hip.h"
 #include "clrs_mw_rank.hip.h"
 #include "clrs_mw_gemm.hip.h"
+#include "clrs_mw_posv.hip.h"
 #include "clrs_mw_kernel_vectors.hip.h"
 #include "clrs_mw_rational.hip.h"
 #include "clrs_mw_inst.h"
@@ -1729,6 +1730,103 @@ extern "C" int clrs_mw_gemm(int device, int limbs, int njobs, const clrs_mw_gemm
                 memcpy(C + o, back.data() + o, (size_t)q.m * sizeof(double));
             }
     }
+    return 0;
+}
+
+// ---- the SPD solve (clrs_mw_posv.hip.h): no context, host pointers, the buffers and events of one call released on every path ----
+struct MwPosvEvents {
+    std::vector<hipEvent_t> e;
+    ~MwPosvEvents() { for (hipEvent_t x : e) (void)hipEventDestroy(x); }
+    hipError_t get(size_t count) {
+        for (size_t i = 0; i < count; i++) {
+            hipEvent_t x;
+            hipError_t r = hipEventCreate(&x);
+            if (r != hipSuccess) return r;
+            e.push_back(x);
+        }
+        return hipSuccess;
+    }
+};
+static thread_local double t_posv_diag_ms = 0.0, t_posv_whole_ms = 0.0;
+static thread_local int t_posv_timing = 0;      // clrs_mw_posv_times switches the per-panel events on for this thread's later calls
+
+extern "C" int clrs_mw_posv_times(double *diag_ms, double *gemm_ms, double *whole_ms) {
+    if (!diag_ms || !gemm_ms || !whole_ms) return mw_fail(CLRS_ERR_INVALID, "posv_times: null argument");
+    t_posv_timing = 1;
+    *diag_ms = t_posv_diag_ms;
+    *gemm_ms = t_posv_whole_ms - t_posv_diag_ms;
+    *whole_ms = t_posv_whole_ms;
+    return 0;
+}
+
+extern "C" int clrs_mw_posv(int device, int limbs, int n, int nrhs, const double *A, int a_plane, const double *B, int b_plane, double *X, int x_plane,
+                            int32_t *info) {
+    if (limbs != 4 && limbs != 5 && limbs != 6 && limbs != 8 && limbs != 10) return mw_fail(CLRS_ERR_INVALID, "posv: limbs must be 4, 5, 6, 8 or 10");
+    if (n < 0 || nrhs < 0) return mw_fail(CLRS_ERR_INVALID, "posv: negative size");
+    const i64 nn = (i64)n * n, nr = (i64)n * nrhs;
+    if (a_plane < nn || b_plane < nr || x_plane < nr) return mw_fail(CLRS_ERR_INVALID, "posv: a plane is smaller than its matrix");
+    if (nr == 0) return 0;
+    if (!A || !B || !X || !info) return mw_fail(CLRS_ERR_INVALID, "posv: null argument");
+    t_posv_diag_ms = t_posv_whole_ms = 0.0;
+    const MwPosvPlan q = mw_posv_plan(n, nrhs);
+    MWCHECK(hipSetDevice(device));
+    MwRankBufs bufs;
+    MwPosvEvents ev;
+    double *d_pool = nullptr;
+    MwGemmJob *d_jobs = nullptr;
+    int *d_tiles = nullptr, *d_status = nullptr;
+    MWCHECK(bufs.get(&d_pool, (size_t)q.plane * limbs));
+    MWCHECK(bufs.get(&d_jobs, q.jobs.size())); MWCHECK(bufs.get(&d_tiles, q.tiles.size())); MWCHECK(bufs.get(&d_status, 1));
+    const bool timing = t_posv_timing != 0;                   // two events per call; two more per diagonal launch only once the times were asked for
+    MWCHECK(ev.get(2 + (timing ? 2 * (size_t)q.npanels : 0)));
+    MWCHECK(hipMemset(d_pool, 0, (size_t)q.plane * limbs * sizeof(double)));
+    MWCHECK(hipMemset(d_status, 0, sizeof(int)));
+    for (int l = 0; l < limbs; l++) {
+        MWCHECK(hipMemcpy(d_pool + (size_t)l * q.plane + q.s_off, A + (size_t)l * a_plane, (size_t)nn * sizeof(double), hipMemcpyHostToDevice));
+        MWCHECK(hipMemcpy(d_pool + (size_t)l * q.plane + q.b_off, B + (size_t)l * b_plane, (size_t)nr * sizeof(double), hipMemcpyHostToDevice));
+    }
+    MWCHECK(hipMemcpy(d_jobs, q.jobs.data(), q.jobs.size() * sizeof(MwGemmJob), hipMemcpyHostToDevice));      // the tables of every launch, once
+    MWCHECK(hipMemcpy(d_tiles, q.tiles.data(), q.tiles.size() * sizeof(int), hipMemcpyHostToDevice));
+    MWCHECK(hipEventRecord(ev.e[0], nullptr));
+    for (const MwPosvLaunch &ln : q.launches) {
+        const int c0 = ln.panel * MW_POSV_T, nb = std::min(n - c0, MW_POSV_T);
+        const i64 blk = c0 + (i64)c0 * n;
+        if (ln.diag && timing) MWCHECK(hipEventRecord(ev.e[2 + 2 * ln.panel], nullptr));
+#define MW_POSV_CASE(Kc)                                                                                                                                          \
+    case Kc:                                                                                                                                                      \
+        if (ln.diag)                                                                                                                                              \
+            hipLaunchKernelGGL(k_mw_posv_diag<Kc>, dim3(1), dim3(MW_NT), MW_POSV_LDS(Kc), nullptr, d_pool, (mwi64)q.plane, (mwi64)(q.s_off + blk),                \
+                               (mwi64)(q.l_off + blk), n, (mwi64)(q.w_off + (i64)ln.panel * MW_POSV_PL), nb, c0, d_status);                                       \
+        else                                                                                                                                                      \
+            hipLaunchKernelGGL(k_mw_gemm<Kc>, dim3((unsigned)ln.ntiles), dim3(MW_NT), MW_GEMM_LDS(Kc), nullptr, d_jobs, d_tiles + 3 * (size_t)ln.tile0, d_pool,   \
+                               (mwi64)q.plane, d_pool, (mwi64)q.plane, d_pool, (mwi64)q.plane);                                                                   \
+        break;
+        switch (limbs) { MW_POSV_CASE(4) MW_POSV_CASE(5) MW_POSV_CASE(6) MW_POSV_CASE(8) MW_POSV_CASE(10) }
+#undef MW_POSV_CASE
+        MWCHECK(hipGetLastError());
+        if (ln.diag && timing) MWCHECK(hipEventRecord(ev.e[3 + 2 * ln.panel], nullptr));
+    }
+    MWCHECK(hipEventRecord(ev.e[1], nullptr));
+    MWCHECK(hipStreamSynchronize(nullptr));
+    float ms = 0.f;
+    MWCHECK(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
+    t_posv_whole_ms = ms;
+    for (int p = 0; timing && p < q.npanels; p++) {
+        MWCHECK(hipEventElapsedTime(&ms, ev.e[2 + 2 * p], ev.e[3 + 2 * p]));
+        t_posv_diag_ms += ms;
+    }
+    int status = 0;
+    MWCHECK(hipMemcpy(&status, d_status, sizeof(int), hipMemcpyDeviceToHost));
+    std::vector<double> back(status ? 0 : (size_t)nr * limbs);
+    if (!status)
+        for (int l = 0; l < limbs; l++)
+            MWCHECK(hipMemcpy(back.data() + (size_t)l * nr, d_pool + (size_t)l * q.plane + q.x_off, (size_t)nr * sizeof(double), hipMemcpyDeviceToHost));
+    for (int l = 0; l < limbs; l++) {                         // the outputs are written only once nothing can fail any more
+        if (status) memset(X + (size_t)l * x_plane, 0, (size_t)nr * sizeof(double));
+        else memcpy(X + (size_t)l * x_plane, back.data() + (size_t)l * nr, (size_t)nr * sizeof(double));
+    }
+    info[0] = status;
+    info[1] = q.npanels;
     return 0;
 }
 

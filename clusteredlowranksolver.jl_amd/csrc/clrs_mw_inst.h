@@ -40,6 +40,7 @@
     X __global__ void k_mwi_init<K>(const MwDev, const MwIpmDev, double, double);                                      \
     X __global__ void k_mw_rank_reveal<K>(const MwRankMat *, double *, double *, mwi64, double *, int *, int *, double *, mwi64);     \
     X __global__ void k_mw_gemm<K>(const MwGemmJob *, const int *, const double *, mwi64, const double *, mwi64, double *, mwi64);  \
+    X __global__ void k_mw_posv_diag<K>(double *, mwi64, mwi64, mwi64, int, mwi64, int, int, int *);                                  \
     X __global__ void k_mw_kv_scatter<K>(const MwKvBlk *, const int *, const double *, double *, mwi64);           \
     X __global__ void k_mw_rationalize<K>(const double *, mwi64, const mwi64 *, int, double, double *, double *, int *, double *);
 

@@ -9,6 +9,7 @@
 #include "clrs_mw_ipm.hip.h"
 #include "clrs_mw_rank.hip.h"
 #include "clrs_mw_gemm.hip.h"
+#include "clrs_mw_posv.hip.h"
 #include "clrs_mw_kernel_vectors.hip.h"
 #include "clrs_mw_rational.hip.h"
 #include "clrs_mw_inst.h"

@@ -450,6 +450,35 @@ def gemm_batch(jobs, limbs: int, device: int = 0):
     return [np.ascontiguousarray(np.transpose(Cp[:, co:co + m * n].reshape(limbs, n, m), (0, 2, 1))) for m, n, k, ao, bo, co in shapes]
 
 
+def posv(A, B, limbs: int, device: int = 0):
+    """The solution of A X = B for a dense symmetric positive definite A in `limbs` limbs on the device, one library call (clrs_mw_posv, DESIGN.md
+    section 26): `A` planar (planes <= limbs, n, n), of which only the lower triangle is read, `B` planar (planes, n, nrhs), zero padded to `limbs` as in
+    `gemm_batch`.  Returns (X, info): X planar (limbs, n, nrhs) and info = (0, number of panels).  Raises ArithmeticError naming the column whose pivot
+    was not positive.  Results are reproducible bit for bit and a column of X does not depend on the other right-hand sides."""
+    limbs = int(limbs)
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64)
+    if A.ndim != 3 or B.ndim != 3 or A.shape[0] > limbs or B.shape[0] > limbs or A.shape[1] != A.shape[2] or B.shape[1] != A.shape[1]:
+        raise ValueError("posv: operands must be planar (planes <= limbs, n, n) and (planes <= limbs, n, nrhs)")
+    n, nrhs = A.shape[1], B.shape[2]
+    Ap, Bp, Xp = np.zeros((limbs, max(n * n, 1))), np.zeros((limbs, max(n * nrhs, 1))), np.zeros((limbs, max(n * nrhs, 1)))
+    Ap[:A.shape[0], :n * n] = np.transpose(A, (0, 2, 1)).reshape(A.shape[0], -1)          # column-major, leading dimension n
+    Bp[:B.shape[0], :n * nrhs] = np.transpose(B, (0, 2, 1)).reshape(B.shape[0], -1)
+    info = np.zeros(2, dtype=np.int32)
+    _lib.check(_lib.load().clrs_mw_posv(int(device), limbs, n, nrhs, _dp(Ap), Ap.shape[1], _dp(Bp), Bp.shape[1], _dp(Xp), Xp.shape[1],
+                                        info.ctypes.data_as(_lib.p_i32)))
+    if info[0]:
+        raise ArithmeticError(f"posv: the pivot of column {int(info[0]) - 1} is not positive")
+    return np.ascontiguousarray(np.transpose(Xp[:, :n * nrhs].reshape(limbs, nrhs, n), (0, 2, 1))), info
+
+
+def posv_times():
+    """(diag_ms, gemm_ms, whole_ms) of this thread's last `posv`: the device time in the diagonal launches, in the product launches, and of all launches.
+    The events around the diagonal launches are recorded only in calls after this thread's first `posv_times()`: call it once before the `posv` to be timed."""
+    d, g, w = C.c_double(), C.c_double(), C.c_double()
+    _lib.check(_lib.load().clrs_mw_posv_times(C.byref(d), C.byref(g), C.byref(w)))
+    return d.value, g.value, w.value
+
+
 def shard_problem(full: FlatSDP, rank: int, world: int, parts=None):
     """The sub-problem of rank `rank` (its clusters by `partition_clusters`, all free variables) and what `solvesdp_mw` must tell the
     library about the whole: (shard, shard_info)."""

@@ -79,12 +79,21 @@ def delsarte_exact(n, d, costheta, prec=DEFAULT_PREC) -> ClusteredLowRankSDP:
                                    b=np.zeros(0), names={"free": [], "blocks": [[b.name for b in blocks]]})
 
 
-def delsarte_exact_problem(n, d, costheta):
+def delsarte_exact_problem(n, d, costheta, field=None):
     """`delsarte_exact` over QQ, the problem `rounding.exact_solution` rounds to: the same four-decimal samples, the Chebyshev and Gegenbauer recurrences of
-    polytools in `Fraction`s.  `delsarte_exact_problem(n, d, costheta).to_sdp(prec)` is `delsarte_exact(n, d, costheta, prec)`."""
+    polytools in `Fraction`s.  `delsarte_exact_problem(n, d, costheta).to_sdp(prec)` is `delsarte_exact(n, d, costheta, prec)`.
+    With `field` (a `rounding.NumberField`) `costheta` is the tuple of its coefficients in g -- `(0, 1/5)` over x^2 - 5 for 1 / sqrt(5), `(1/4, 1/4)` for
+    1 / (sqrt(5) - 1) -- and the weights of block "B" are field elements; every other number stays rational."""
     from fractions import Fraction as F
-    from ..rounding import ExactBlock, ExactLowRank, ExactProblem
-    ct = F(costheta)
+    from ..rounding import ExactBlock, ExactLowRank, ExactProblem, field_array
+    if field is not None:
+        ctf = tuple(F(c) for c in costheta)
+        if len(ctf) != field.degree:
+            raise ValueError(f"delsarte_exact_problem: costheta needs {field.degree} coefficients")
+        weight = lambda x: field_array([tuple((1 + x) * (c - (x if k == 0 else 0)) for k, c in enumerate(ctf))])
+    else:
+        ct = F(costheta)
+        weight = lambda x: [(1 + x) * (ct - x)]
     with mp.workprec(DEFAULT_PREC):
         xs = [F(int(mp.nint(x * 10 ** 4)), 10 ** 4) for x in sample_points_chebyshev(2 * d)]
     ns = len(xs)
@@ -106,7 +115,7 @@ def delsarte_exact_problem(n, d, costheta):
         Cs.append(np.array([[F(1)]], dtype=object))
     blocks.append(ExactBlock(1, d + 1, {(0, 0): {p: ExactLowRank([F(1)], V[p:p + 1, :d + 1], V[p:p + 1, :d + 1]) for p in range(ns)}}, "A"))
     Cs.append(np.full((d + 1, d + 1), F(0), dtype=object))
-    blocks.append(ExactBlock(1, d, {(0, 0): {p: ExactLowRank([(1 + xs[p]) * (ct - xs[p])], V[p:p + 1, :d], V[p:p + 1, :d]) for p in range(ns)}}, "B"))
+    blocks.append(ExactBlock(1, d, {(0, 0): {p: ExactLowRank(weight(xs[p]), V[p:p + 1, :d], V[p:p + 1, :d]) for p in range(ns)}}, "B"))
     Cs.append(np.full((d, d), F(0), dtype=object))
     return ExactProblem(False, F(1), [blocks], [np.zeros((ns, 0), dtype=object)], [np.full(ns, F(-1), dtype=object)], [Cs], np.zeros(0, dtype=object),
-                        {"free": [], "blocks": [[b.name for b in blocks]]})
+                        {"free": [], "blocks": [[b.name for b in blocks]]}, field)

@@ -46,7 +46,13 @@ clrs_modp_minors_field; `split_primes`, `field_frobenius`,
 `is_valid_solution(..., field=...)`), and so is the basis change (`B = [V | E]` and its inverse over QQ(g), src/rounding.jl:834-836, 1017-1050: the determinant and
 the adjugate as elements of Z[g] from the inverses of the residue matrices at every (split prime, root) pair, clrs_modp_field_adjugate, DESIGN.md section 25;
 `inverse_field`, `FieldInverse`, `field_adjugate_mod`, `field_adjugate_bounds`, `field_matmul`, `complete_basis_field`, `transform_field`, `undo_transform_field`,
-`basis_transformations(..., field=...)`); the system over the field and the reduction of its kernel vectors are not.
+`basis_transformations(..., field=...)`).  The system over the field is built too: an `ExactProblem` may carry a `field` and coefficient tuples
+(`field_array`; `to_sdp` embeds them at g; `problems.delsarte_exact_problem(..., field=)`), `linear_system(field=)` assembles it with one `assemble` call per
+low-rank block on the coefficient planes stacked along the terms, `convert_system` / `xrational_to_field` (src/rounding.jl:1256-1282, 1332-1342) turn it into a
+system over QQ and back, `field_least_squares` is the reference's roundx(A, b, x, g, deg) (src/rounding.jl:537-568: regularised normal equations of condition
+number about 1e30, their products by clrs_mw_gemm and their solve by clrs_mw_posv, a blocked multi-word Cholesky on the device, `mw.posv`, DESIGN.md section
+26), `get_rational_system(field=)` and `exact_solution(field=)` run the chain.  The reduction of the field's kernel vectors is not built: the field branch
+needs `RoundingSettings(reduce_kernelvectors=False)`.
 
 The system the projection solves is assembled from an `ExactProblem` (the problem over QQ; `to_sdp` gives the numeric one) by `linear_system`
 (`partial_linearsystem`, src/interface.jl:1354-1535): per low-rank block one call of clrs_zz_lowrank_system, a row-wise Gram of long
@@ -72,7 +78,7 @@ __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vecto
            "ExactProblem", "ExactSolution", "system_index", "linear_system", "select_columns", "vectorize_solution", "get_rational_system", "exact_solution",
            "ReductionError", "lll_first_rung", "lll_batch", "lll", "kernel_lattice", "reduce_kernel_vectors", "NumberField", "FieldRounding", "round_to_field",
            "field_relations_lll", "kernel_vectors_field_batch", "vectors_to_field", "split_primes", "field_frobenius", "leading_minors_field_mod", "field_minor_bounds",
-           "FieldPDCertificate", "checkpd_field"]
+           "FieldPDCertificate", "checkpd_field", "convert_system", "xrational_to_field", "field_least_squares", "field_array"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -92,6 +98,7 @@ class RoundingSettings:
     reduce_kernelvectors: bool = True       # LLL reduction of the kernel vectors (src/rounding.jl:860-1060): basis_transformations takes it with `reduce=`, and refuses it without
     unimodular_transform: bool = True       # with the reduction: the whole basis change unimodular (src/rounding.jl:960-963); False: only the kernel vectors are replaced
     normalize_transformation: bool = True   # rows of Binv times the lcm of their denominators, columns of B divided by it (src/rounding.jl:844-850)
+    regularization: float = 1e-30           # of the least-squares problem of roundx(A, b, x, g, deg) over a number field (src/rounding.jl:537)
     approximation_decimals: int = 40        # the numeric solution is cut to this many decimals before the projection (roundx, src/rounding.jl:515)
     redundancyfactor: int = 10              # select_columns takes about this many columns per constraint; negative: all (src/rounding.jl:95-153)
 
@@ -2004,7 +2011,9 @@ def _fraction_array(a, shape=None) -> np.ndarray:
     """anything -> an object array of `Fraction`s (of the given shape)"""
     src = np.asarray(a, dtype=object)
     out = np.empty(src.shape, dtype=object)
-    out.flat = [Fraction(v) for v in src.flat]
+    for idx in np.ndindex(*src.shape):                                                                         # (tuples: elements of a number field, kept)
+        v = src[idx]
+        out[idx] = tuple(Fraction(x) for x in v) if isinstance(v, tuple) else Fraction(v)
     return out if shape is None else out.reshape(shape)
 
 
@@ -2059,9 +2068,10 @@ class ExactProblem:
     C: list
     b: np.ndarray
     names: dict = dataclasses.field(default_factory=dict)
+    field: object = None          # a `NumberField`: every number may then be a tuple of `degree` `Fraction`s, the coefficients in g (object arrays whose ELEMENTS are tuples: `field_array`)
 
     def __post_init__(self):
-        self.constant = Fraction(self.constant)
+        self.constant = _fraction_array([self.constant] if not isinstance(self.constant, tuple) else field_array([self.constant]))[0]
         self.b = _fraction_array(self.b).reshape(-1)
         self.c = [_fraction_array(x).reshape(-1) for x in self.c]
         self.B = [_fraction_array(x, (len(cj), self.b.size)) for x, cj in zip(self.B, self.c)]
@@ -2085,13 +2095,17 @@ class ExactProblem:
             if src.size == 0:
                 return np.zeros(src.shape)
             out = np.empty(src.shape, dtype=object)
-            out.flat = [mp.mpf(v.numerator) / mp.mpf(v.denominator) for v in src.flat]
+            q = lambda v: mp.mpf(v.numerator) / mp.mpf(v.denominator)
+            gp = self.field.power_values(prec=int(prec)) if self.field is not None else None
+            for idx in np.ndindex(*src.shape):                       # a field element is embedded at field.g
+                v = src[idx]
+                out[idx] = mp.fsum(q(c) * g for c, g in zip(v, gp) if c) if isinstance(v, tuple) else q(v)
             return out
 
         with mp.workprec(int(prec)):
             ent = lambda e: LowRankMat(num(e.lam), num(e.vs), num(e.ws)) if isinstance(e, ExactLowRank) else HiLo.of(num(e))
             blocks = [[Block(bl.m, bl.delta, {rs: {p: ent(e) for p, e in d.items()} for rs, d in bl.entries.items()}, bl.name) for bl in cl] for cl in self.blocks]
-            return ClusteredLowRankSDP(bool(self.maximize), float(self.constant), blocks, [num(x) for x in self.B], [num(x) for x in self.c],
+            return ClusteredLowRankSDP(bool(self.maximize), float(num([self.constant])[0]), blocks, [num(x) for x in self.B], [num(x) for x in self.c],
                                        [[num(x) for x in cl] for cl in self.C], num(self.b), self.names)
 
 
@@ -2109,13 +2123,13 @@ class ExactSolution:
     Bs: dict
 
 
-def _kept_rows(problem, Bs):
-    """per block in flat order: (P, n') with P = Binv[s:, :] ((n', N) `Fraction`s; None: the identity)"""
+def _kept_rows(problem, Bs, d=None):
+    """per block in flat order: (P, n') with P = Binv[s:, :] ((n', N) `Fraction`s, or coefficient tuples of `d` of them; None: the identity)"""
     out = []
     for bi, (_, bl) in enumerate(problem.flat_blocks()):
         if Bs is not None and bi in Bs:
             _, Binv, s = Bs[bi]
-            P = _object_matrix(Binv, "linear_system", Fraction)[int(s):, :]
+            P = (_object_matrix(Binv, "linear_system", Fraction) if d is None else _field_matrix(Binv, d, "linear_system"))[int(s):, :]
             if P.shape[1] != bl.n:
                 raise ValueError(f"linear_system: the transformation of block {bi} has {P.shape[1]} columns for a block of size {bl.n}")
             out.append((P, P.shape[0]))
@@ -2124,10 +2138,11 @@ def _kept_rows(problem, Bs):
     return out
 
 
-def system_index(problem, Bs=None) -> list:
+def system_index(problem, Bs=None, field=None) -> list:
     """The columns of `linear_system`: `(block, a, b)`, a <= b row-major, block by block in flat order (blocks whose transformation keeps no dimension give
     none), then `("free", k)`."""
-    index = [(bi, a, b) for bi, (_, nk) in enumerate(_kept_rows(problem, Bs)) for a in range(nk) for b in range(a, nk)]
+    d = None if field is None else len(_minpoly_of(field)) - 1
+    index = [(bi, a, b) for bi, (_, nk) in enumerate(_kept_rows(problem, Bs, d)) for a in range(nk) for b in range(a, nk)]
     return index + [("free", k) for k in range(problem.b.size)]
 
 
@@ -2139,7 +2154,7 @@ def _lcm_of(values) -> int:
     return l
 
 
-def linear_system(problem, Bs=None, columns=None, assemble=None, matmul=None, device: int = 0):
+def linear_system(problem, Bs=None, columns=None, assemble=None, matmul=None, device: int = 0, field=None):
     """The reference's `linearsystem` / `partial_linearsystem` (src/interface.jl:1354-1535) over QQ for an `ExactProblem`: `(A, b, index)` with
     `A x = b` the constraints in the variables x = (entries (a <= b) of the blocks, free variables).  Rows: cluster by cluster, constraint by constraint;
     columns: `system_index(problem, Bs)`, or its entries `columns` (indices into it) in the given order; `b` the concatenated `c[j]`.  `A` is an object array
@@ -2151,8 +2166,13 @@ def linear_system(problem, Bs=None, columns=None, assemble=None, matmul=None, de
     common multiple of their denominators, P_l by that of its own, `U = P_l [lam v]`, `W = P_l [w]` as integer products (`matmul(A, B, device=...)`, e.g.
     `zz_matmul`; default: Python integers), and entry (i, (a, b)) is `assemble`'s integer over the product of the four multipliers.  Clearing denominators is
     host work of the size of the vectors; the quotient per entry is the only host work of the size of A.  The transposed partners `ClusteredLowRankSDP.check`
-    demands make the sum over the terms symmetric, which the factor 2 off the diagonal relies on.  Dense entries go through `transform`."""
+    demands make the sum over the terms symmetric, which the factor 2 off the diagonal relies on.  Dense entries go through `transform`.
+
+    With `field` (a `NumberField` or its minimal polynomial; `Bs` then from `basis_transformations(field=...)`) the numbers of the problem may be coefficient
+    tuples and `A`, `b` hold tuples (`_linear_system_field`): still one `assemble` call per low-rank block, on the coefficient planes stacked along the terms."""
     assemble = lowrank_system if assemble is None else assemble
+    if field is not None:
+        return _linear_system_field(problem, Bs, columns, assemble, matmul, device, field)
     kept = _kept_rows(problem, Bs)
     index = system_index(problem, Bs)
     take = list(range(len(index))) if columns is None else [int(c) for c in columns]
@@ -2288,13 +2308,36 @@ def vectorize_solution(Yt, y, index) -> list:
     return [Fraction(y[e[1]]) if e[0] == "free" else Fraction(Yt[e[0]][e[1], e[2]]) for e in index]
 
 
-def get_rational_system(problem, Yt, y, Bs=None, columns=None, settings: Optional[RoundingSettings] = None, assemble=None, matmul=None, device: int = 0):
+def get_rational_system(problem, Yt, y, Bs=None, columns=None, settings: Optional[RoundingSettings] = None, assemble=None, matmul=None, device: int = 0,
+                        field=None, limbs: Optional[int] = None, form: str = "auto", gemm=None, solve=None):
     """The reference's `get_rational_system` over QQ (src/rounding.jl:1284-1296): `(A_cols, rhs, x_rounded, columns)`.  x = the entries (a <= b) of the
     transformed blocks `Yt` and the free variables `y` (exact rationals) in the order of `system_index(problem, Bs)`;
     `x_rounded = floor(x 10^dec) / 10^dec` entry by entry with `dec = settings.approximation_decimals` (`roundx`, src/rounding.jl:515-517);
     `rhs = b - A x_rounded` over ALL columns of the transformed system (with `matmul`: one integer product of the rows cleared of denominators), and
-    `A_cols` its columns `columns` (default: all).  The full triangle is assembled once (`linear_system`)."""
+    `A_cols` its columns `columns` (default: all).  The full triangle is assembled once (`linear_system`).
+
+    With `field` (src/rounding.jl:1299-1330; `Yt`, `y` numeric: mpmath numbers): the full system over the field, `convert_system`, `field_least_squares` at
+    `limbs` limbs (`form`, `gemm`, `solve` as there) for `x_rounded` (m d numbers), `rhs = btot - Atot x_rounded`, and the columns `[c + m k]`, k < d, of
+    every column c."""
     settings = RoundingSettings() if settings is None else settings
+    if field is not None:
+        A, b, index = linear_system(problem, Bs=Bs, assemble=assemble, matmul=matmul, device=device, field=field)
+        Atot, btot = convert_system(A, b, field)
+        d, m = field.degree, len(index)
+        x = [y[e[1]] if e[0] == "free" else Yt[e[0]][e[1], e[2]] for e in index]
+        x_rounded = field_least_squares(Atot, btot, x, field, limbs, settings.regularization, settings.approximation_decimals, form=form, gemm=gemm, solve=solve,
+                                        device=device)
+        nrows, ncols = Atot.shape
+        if matmul is not None and nrows and ncols:
+            cleared = [_common_denominator(list(Atot[i])) for i in range(nrows)]
+            Ai = np.array([list(cl[0]) for cl in cleared], dtype=object).reshape(nrows, ncols)
+            xv, L = _common_denominator(x_rounded)
+            rhs = [btot[i] - Fraction(v, L * cleared[i][1]) for i, v in enumerate(_matmul_vector(matmul, Ai, xv, device))]
+        else:
+            rhs = [btot[i] - sum((Atot[i, c] * x_rounded[c] for c in range(ncols) if Atot[i, c] != 0), Fraction(0)) for i in range(nrows)]
+        columns = list(range(m)) if columns is None else [int(c) for c in columns]
+        columns = [c + m * k for c in columns for k in range(d)]
+        return Atot[:, columns], rhs, x_rounded, columns
     A, b, index = linear_system(problem, Bs=Bs, assemble=assemble, matmul=matmul, device=device)
     scale = 10 ** int(settings.approximation_decimals)
     x_rounded = [Fraction((v * scale).__floor__(), scale) for v in vectorize_solution(Yt, y, index)]
@@ -2342,7 +2385,8 @@ def _lift_by_columns(lift):
 
 
 def exact_solution(problem, result, settings: Optional[RoundingSettings] = None, limbs: Optional[int] = None, transformed: bool = False, rng=None,
-                   device: int = 0, batch=None, lift=None, reconstruct=None, matmul=None, minors=None, round_batch=None, assemble=None, reduce=None, verbose: bool = False) -> ExactSolution:
+                   device: int = 0, batch=None, lift=None, reconstruct=None, matmul=None, minors=None, round_batch=None, assemble=None, reduce=None, verbose: bool = False,
+                   field=None, gemm=None, solve=None, adjugate=None, primes=None) -> ExactSolution:
     """The reference's `exact_solution` over QQ (src/rounding.jl:1366-1409, 155-179) for an `ExactProblem` and a numeric solution `result` of
     `problem.to_sdp(...)` (a `SolveResult` of `solvesdp_mw`, or anything with `X`, `Y` (fp64 or planar limbs) and `y`):
 
@@ -2358,6 +2402,9 @@ def exact_solution(problem, result, settings: Optional[RoundingSettings] = None,
     `basis_transformations` then takes it column by column), `reconstruct`, `matmul`, `minors` (`checkpd`), `assemble` (`linear_system`).  `rng`: the generator of `select_columns` and `project_to_affine_space`."""
     settings = RoundingSettings() if settings is None else settings
     rng = np.random.default_rng(0) if rng is None else rng
+    if field is not None:
+        return _exact_solution_field(problem, result, settings, limbs, transformed, rng, device, batch, lift, reconstruct, matmul, minors, round_batch, assemble,
+                                     field, gemm, solve, adjugate, primes)
     block_n = problem.block_n
     kernels = kernel_vectors(block_n, result, result, limbs=limbs, settings=settings, device=device, rationalize=True, round_batch=round_batch)
     Bs = basis_transformations({bi: (int(n), vectors_to_fractions(k)) for bi, (n, k) in enumerate(zip(block_n, kernels))}, settings, device=device, batch=batch,
@@ -3587,3 +3634,339 @@ def _basis_transformations_field(kernels, field, device, maxprimes, batch, check
             raise ArithmeticError(f"basis_transformations: block {key!r}: no pair gave the greedy completion of the kernel vectors")
         out[key] = (B.T.copy(), Binv, s)
     return out
+
+
+# ---- the system over QQ(g) as a system over QQ, and its approximate solution in the extension (src/rounding.jl:1256-1282, 537-568) ----
+def convert_system(A, b, field):
+    """The reference's `convert_system` (src/rounding.jl:1256-1282): the system `A x = b` over QQ(g) -- `A` (n, m) and `b` (n,) of coefficient tuples, `field`
+    a `NumberField` or the coefficient list of its minimal polynomial, degree d -- as the system `Atot [x_0; ..; x_(d-1)] = btot` over QQ in the coefficients
+    `x = sum_j x_j g^j`: `Atot` an object array (n d, m d) of `Fraction`s, block (k, j) -- rows `n k + i`, columns `m j + c` -- the sum over i of
+    `coeff(g^(i+j), k) A_i`; `btot` the list of the coefficients of b, coefficient after coefficient."""
+    f = _minpoly_of(field)
+    d = len(f) - 1
+    Af = _field_matrix(A, d, "convert_system")
+    n, m = Af.shape
+    bf = _field_matrix([list(b)], d, "convert_system")[0] if len(b) else np.empty(0, dtype=object)
+    if bf.shape[0] != n:
+        raise ValueError(f"convert_system: b has {bf.shape[0]} entries for {n} rows")
+    power = [_field_fold([Fraction(int(t == e)) for t in range(2 * d - 1)], f) for e in range(2 * d - 1)]      # g^e in the basis 1 .. g^(d-1)
+    Atot = np.empty((n * d, m * d), dtype=object)
+    Atot.fill(Fraction(0))
+    for i in range(d):
+        for j in range(d):
+            for k in range(d):
+                ck = power[i + j][k]
+                if ck:
+                    for r in range(n):
+                        for c in range(m):
+                            if Af[r, c][i]:
+                                Atot[n * k + r, m * j + c] += ck * Af[r, c][i]
+    return Atot, [bf[r][k] for k in range(d) for r in range(n)]
+
+
+def xrational_to_field(x, field) -> list:
+    """The reference's `xrational_to_field` (src/rounding.jl:1332-1342): the concatenation `[x_0; ..; x_(d-1)]` of `convert_system` as the list of the
+    m = len(x) / d coefficient tuples `(x_0[c], .., x_(d-1)[c])`."""
+    d = len(_minpoly_of(field)) - 1
+    if len(x) % d:
+        raise ValueError(f"xrational_to_field: {len(x)} numbers are no multiple of the degree {d}")
+    m = len(x) // d
+    return [tuple(Fraction(x[m * j + c]) for j in range(d)) for c in range(m)]
+
+
+def _planar_matrix(values, rows: int, cols: int, limbs: int) -> np.ndarray:
+    """mpmath numbers, row-major -> planar (limbs, rows, cols)"""
+    from .mw import to_limbs
+    return np.ascontiguousarray(to_limbs(values, limbs).reshape(limbs, rows, cols))
+
+
+def field_least_squares(Atot, btot, x, field, limbs: int, regularization: float = 1e-30, decimals: int = 40, form: str = "auto", gemm=None, solve=None,
+                        device: int = 0) -> list:
+    """The reference's `roundx(A, b, x, g, deg)` (src/rounding.jl:537-568) at `limbs` limbs on the device: an approximate solution of the converted system
+    `Atot [x_0; ..; x_(d-1)] = btot` of `convert_system` near the numeric solution `x` (m numbers: `Fraction`s or mpmath numbers) of the system over the
+    field.  With `Acols = Atot[:, :m]`, `rhs = btot - Acols x` and `B = [Atot_j - g^j Acols]_(j >= 1)` (converted to limbs once) the coefficients
+    `y = (x_1, .., x_(d-1))` solve the regularised least-squares problem min |B y - rhs|^2 + reg |y|^2 and `x_0 = x - sum_j g^j x_j`:
+      form "primal": `(B^T B + reg I) y = B^T rhs`, order m (d - 1), the reference's form;
+      form "dual":   `(B B^T + reg I) z = rhs`, `y = B^T z`, order n d -- the same y for reg > 0;
+      form "auto":   the smaller order.
+    The Gram matrix, `B^T rhs` and `B^T z` are products of `gemm` (default `mw.gemm_batch`), the solve is `solve` (default `mw.posv`, clrs_mw_posv: the
+    system has condition number about 1 / reg).  Returns `[floor(x_0 10^dec) / 10^dec; floor(y 10^dec) / 10^dec]` as `Fraction`s, dec = `decimals`."""
+    import mpmath as mp
+    from . import mw
+    gemm = mw.gemm_batch if gemm is None else gemm
+    solve = mw.posv if solve is None else solve
+    limbs, d = int(limbs), field.degree
+    At = np.asarray(Atot, dtype=object)
+    rows, m = At.shape[0], len(x)
+    if At.ndim != 2 or At.shape[1] != m * d or len(btot) != rows or d < 2:
+        raise ValueError(f"field_least_squares: Atot must be (n d, m d) = (.., {m * d}) with one entry of btot per row and d >= 2, got {At.shape} and {len(btot)}")
+    if form not in ("auto", "primal", "dual"):
+        raise ValueError(f"field_least_squares: form must be 'auto', 'primal' or 'dual', got {form!r}")
+    if not regularization > 0:
+        raise ValueError("field_least_squares: the regularization must be positive")
+    ncol = m * (d - 1)
+    form = ("primal" if ncol <= rows else "dual") if form == "auto" else form
+    scale = 10 ** int(decimals)
+    with mp.workprec(64 * limbs + 128):
+        num = lambda v: mp.mpf(v.numerator) / mp.mpf(v.denominator) if isinstance(v, Fraction) else mp.mpf(v)
+        gp = field.power_values(prec=64 * limbs + 128)
+        xs = [num(v) for v in x]
+        Am = [[num(At[r, c]) if At[r, c] else mp.mpf(0) for c in range(m * d)] for r in range(rows)]
+        rhs = [num(btot[r]) - mp.fsum(Am[r][c] * xs[c] for c in range(m) if At[r, c]) for r in range(rows)]
+        Bm = [Am[r][m * j + c] - gp[j] * Am[r][c] for r in range(rows) for j in range(1, d) for c in range(m)]
+        Bp, rp = _planar_matrix(Bm, rows, ncol, limbs), _planar_matrix(rhs, rows, 1, limbs)
+        reg = mp.mpf(regularization)
+        order = ncol if form == "primal" else rows
+        if order == 0:
+            y = []
+        else:
+            if form == "primal":
+                G, v = gemm([(Bp, Bp, None, 1, 0, 1, 0), (Bp, rp, None, 1, 0, 1, 0)], limbs, device=device)
+            else:
+                (G,), v = gemm([(Bp, Bp, None, 0, 1, 1, 0)], limbs, device=device), rp
+            diag = mw.from_limbs(np.ascontiguousarray(G[:, range(order), range(order)]))
+            G = np.array(G, dtype=np.float64)
+            G[:, range(order), range(order)] = mw.to_limbs([t + reg for t in diag], limbs)
+            z, _ = solve(G, v, limbs, device=device)
+            if form == "dual":
+                (z,) = gemm([(Bp, z, None, 1, 0, 1, 0)], limbs, device=device) if ncol else (np.zeros((limbs, 0, 1)),)
+            y = list(mw.from_limbs(np.ascontiguousarray(np.asarray(z)[:, :, 0])))
+        x0 = [xs[c] - mp.fsum(gp[j] * y[m * (j - 1) + c] for j in range(1, d)) for c in range(m)]
+        return [Fraction(int(mp.floor(v * scale)), scale) for v in x0 + list(y)]
+
+
+# ---- the system over QQ(g) itself (src/interface.jl:1354-1535 with FF != QQ) ----
+def field_array(values, shape=None) -> np.ndarray:
+    """a (nested) list whose leaves are coefficient tuples or rationals -> an object array whose ELEMENTS are those leaves (numpy would unpack the tuples)"""
+    def leaves(v):
+        if isinstance(v, tuple) or not isinstance(v, (list, np.ndarray)):
+            return [v], ()
+        parts = [leaves(x) for x in v]
+        return [y for part in parts for y in part[0]], (len(parts),) + (parts[0][1] if parts else ())
+    flat, shp = leaves(values)
+    out = np.empty(len(flat), dtype=object)
+    for i, v in enumerate(flat):
+        out[i] = tuple(Fraction(x) for x in v) if isinstance(v, tuple) else Fraction(v)
+    return out.reshape(shp if shape is None else shape)
+
+
+def _elem(v, d: int) -> tuple:
+    """a rational or a coefficient tuple as a tuple of d `Fraction`s"""
+    if isinstance(v, tuple):
+        if len(v) != d:
+            raise ValueError(f"a field element of {len(v)} coefficients in a field of degree {d}")
+        return tuple(Fraction(x) for x in v)
+    return (Fraction(v),) + (Fraction(0),) * (d - 1)
+
+
+def _elem_mul(x, y, f) -> tuple:
+    d = len(f) - 1
+    t = [Fraction(0)] * (2 * d - 1)
+    for a in range(d):
+        if x[a]:
+            for b in range(d):
+                t[a + b] += x[a] * y[b]
+    return _field_fold(t, f)
+
+
+def _elem_matrix(M, d: int) -> np.ndarray:
+    src = np.asarray(M, dtype=object) if not isinstance(M, np.ndarray) else M
+    out = np.empty(src.shape, dtype=object)
+    for idx in np.ndindex(*src.shape):
+        out[idx] = _elem(src[idx], d)
+    return out
+
+
+def _linear_system_field(problem, Bs, columns, assemble, matmul, device, field):
+    """`linear_system` over QQ(g).  Per low-rank block `U = P [lam v]` and `W = P w` are matrices of field elements (`field_matmul`); per constraint they are
+    cleared of denominators and their d coefficient planes U_a, W_b are stacked along the term axis: row (p, e), e = 0 .. 2d - 2, of the ONE `assemble` call holds
+    the terms (t, a, b) of constraint p with a + b = e, so its entry is the coefficient of g^e, and the 2d - 1 coefficients are folded by the minimal polynomial."""
+    f = _minpoly_of(field)
+    d = len(f) - 1
+    zero = (Fraction(0),) * d
+    add = lambda x, y: tuple(u + v for u, v in zip(x, y))
+    kept = _kept_rows(problem, Bs, d)
+    index = system_index(problem, Bs, field)
+    take = list(range(len(index))) if columns is None else [int(c) for c in columns]
+    if any(not 0 <= c < len(index) for c in take):
+        raise ValueError(f"linear_system: a column outside [0, {len(index)})")
+    where = {}
+    for pos, c in enumerate(take):
+        where.setdefault(c, []).append(pos)
+    sizes = [len(cj) for cj in problem.c]
+    row0 = np.concatenate([[0], np.cumsum(sizes)]).astype(int)
+    A = np.empty((int(row0[-1]), len(take)), dtype=object)
+    A.fill(zero)
+    first = {}
+    for ci, e in enumerate(index):
+        first.setdefault(e[0], ci)
+    for bi, (j, bl) in enumerate(problem.flat_blocks()):
+        P, nk = kept[bi]
+        cols = [(a, b) for a in range(nk) for b in range(a, nk)]
+        sel = [(t, ab) for t, ab in enumerate(cols) if first.get(bi, 0) + t in where] if nk else []
+        if not sel:
+            continue
+        Pj, n, delta = sizes[j], bl.n, bl.delta
+        if bl.high_rank:
+            for p, M in bl.entries.get((0, 0), {}).items():
+                Me = _elem_matrix(M, d)
+                Mt = Me if P is None else transform_field(Me, Bs[bi][1], Bs[bi][2], field, matmul=matmul, device=device)
+                for t, (a, b) in sel:
+                    v = Mt[a, b] if a == b else add(Mt[a, b], Mt[b, a])
+                    for pos in where[first[bi] + t]:
+                        A[row0[j] + p, pos] = v
+            continue
+        terms = [[] for _ in range(Pj)]
+        for (r, s_), dct in bl.entries.items():
+            for p, e in dct.items():
+                for k in range(e.rank):
+                    terms[p].append((r, s_, k, e))
+        vcols, wcols, owner = [], [], []
+        for p in range(Pj):
+            terms[p].sort(key=lambda t: t[:3])
+            for r, s_, k, e in terms[p]:
+                v, w = [zero] * n, [zero] * n
+                lam = _elem(e.lam[k], d)
+                v[r * delta:(r + 1) * delta] = [_elem_mul(lam, _elem(x, d), f) for x in e.vs[k]]
+                w[s_ * delta:(s_ + 1) * delta] = [_elem(x, d) for x in e.ws[k]]
+                vcols.append(v); wcols.append(w); owner.append(p)
+        T = len(vcols)
+        Vf, Wf = np.empty((n, T), dtype=object), np.empty((n, T), dtype=object)
+        for t in range(T):
+            for i in range(n):
+                Vf[i, t], Wf[i, t] = vcols[t][i], wcols[t][i]
+        if P is not None and T:
+            Vf, Wf = field_matmul(P, Vf, field, matmul=matmul, device=device), field_matmul(P, Wf, field, matmul=matmul, device=device)
+        nn = Vf.shape[0]
+        rowptr, Uc, Wc, mult = [0], [], [], []
+        for p in range(Pj):
+            mine = [t for t in range(T) if owner[t] == p]
+            lv = _lcm_of(x for t in mine for i in range(nn) for x in Vf[i, t])
+            lw = _lcm_of(x for t in mine for i in range(nn) for x in Wf[i, t])
+            mult.append(lv * lw)
+            for e in range(2 * d - 1):
+                for t in mine:
+                    for a in range(max(0, e - d + 1), min(d, e + 1)):
+                        Uc.append([int(Vf[i, t][a] * lv) for i in range(nn)])
+                        Wc.append([int(Wf[i, t][e - a] * lw) for i in range(nn)])
+                rowptr.append(len(Uc))
+        Ui = np.array(Uc, dtype=object).reshape(len(Uc), nn).T
+        Wi = np.array(Wc, dtype=object).reshape(len(Wc), nn).T
+        G = np.asarray(assemble(Ui, Wi, rowptr, [ab for _, ab in sel], device=device), dtype=object)
+        if G.shape != (Pj * (2 * d - 1), len(sel)):
+            raise ArithmeticError(f"linear_system: assemble returned shape {G.shape} for {Pj * (2 * d - 1)} rows and {len(sel)} columns")
+        for p in range(Pj):
+            for q, (t, _) in enumerate(sel):
+                coeffs = [Fraction(int(G[p * (2 * d - 1) + e, q]), mult[p]) for e in range(2 * d - 1)]
+                if any(coeffs):
+                    v = _field_fold(coeffs, f)
+                    for pos in where[first[bi] + t]:
+                        A[row0[j] + p, pos] = v
+    nY = len(index) - problem.b.size
+    for k in range(problem.b.size):
+        for pos in where.get(nY + k, ()):
+            for j in range(len(sizes)):
+                for p in range(sizes[j]):
+                    A[row0[j] + p, pos] = _elem(problem.B[j][p, k], d)
+    b = [_elem(v, d) for cj in problem.c for v in cj]
+    return A, b, [index[c] for c in take]
+
+
+def _exact_solution_field(problem, result, settings, limbs, transformed, rng, device, batch, lift, reconstruct, matmul, minors, round_batch, assemble, field, gemm,
+                          solve, adjugate, primes) -> ExactSolution:
+    """`exact_solution` over QQ(g) (src/rounding.jl:1366-1409 with FF a number field): 1. `kernel_vectors(rationalize=True, field=)`; 2.
+    `basis_transformations(field=)`; 3. `Yt = P Y P^T`, P = B^T[s:, :] embedded at g, numerically in `limbs` limbs (`gemm`, default `mw.gemm_batch`); 4.
+    `select_columns`; 5. `get_rational_system(field=)` and the QQ `project_to_affine_space` on the converted system, `extra += 2` as over QQ; 6.
+    `xrational_to_field`; 7. `checkpd_field` of every transformed block (`minors`, `primes`); 8. `undo_transform_field`; 9. the objective as a field element.
+    `Y`, `y` and `objective` of the result hold coefficient tuples.  The reduction of kernel vectors over a field is not built: `NotImplementedError` unless
+    `settings.reduce_kernelvectors` is false."""
+    import mpmath as mp
+    from . import mw
+    if settings.reduce_kernelvectors:
+        raise NotImplementedError("exact_solution: the reduction of kernel vectors over a number field is not built; pass RoundingSettings(reduce_kernelvectors=False)")
+    if limbs is None:
+        limbs = np.atleast_2d(np.asarray(result.Y)).shape[0]             # the planes the solution carries
+    if int(limbs) not in LIMBS:
+        raise ValueError(f"exact_solution: field= needs a solution in limbs, or limbs in {LIMBS}")
+    gemm = mw.gemm_batch if gemm is None else gemm
+    f = _minpoly_of(field)
+    d, limbs = len(f) - 1, int(limbs)
+    zero = (Fraction(0),) * d
+    add = lambda x, y: tuple(u + v for u, v in zip(x, y))
+    block_n = problem.block_n
+    kernels = kernel_vectors(block_n, result, result, limbs=limbs, settings=settings, device=device, rationalize=True, round_batch=round_batch, field=field)
+    Bs = basis_transformations({bi: (int(n), vectors_to_field(k)) for bi, (n, k) in enumerate(zip(block_n, kernels))}, settings, device=device, batch=batch,
+                               matmul=matmul, field=field, adjugate=adjugate, primes=primes)
+    Yp = np.atleast_2d(np.asarray(result.Y, dtype=np.float64))[:limbs]
+    off = np.concatenate([[0], np.cumsum(np.asarray(block_n, dtype=np.int64) ** 2)])
+    with mp.workprec(64 * limbs + 128):
+        gp = field.power_values(prec=64 * limbs + 128)
+        q = lambda v: mp.mpf(v.numerator) / mp.mpf(v.denominator)
+        jobs, keys = [], []
+        for bi, (Bt, _, s_) in Bs.items():
+            n, nk = int(block_n[bi]), int(block_n[bi]) - int(s_)
+            if nk == 0:
+                continue
+            Pm = [mp.fsum(q(c) * g for c, g in zip(_elem(Bt[i, j], d), gp) if c) for i in range(int(s_), n) for j in range(n)]
+            Pp = _planar_matrix(Pm, nk, n, limbs)
+            Yb = np.zeros((limbs, n, n))
+            Yb[:Yp.shape[0]] = np.transpose(Yp[:, off[bi]:off[bi + 1]].reshape(Yp.shape[0], n, n), (0, 2, 1))
+            jobs.append((Pp, (Yb + np.transpose(Yb, (0, 2, 1))) / 2, None, 0, 0, 1, 0))
+            keys.append((bi, Pp))
+        half = gemm(jobs, limbs, device=device) if jobs else []
+        full = gemm([(T, Pp, None, 0, 1, 1, 0) for T, (_, Pp) in zip(half, keys)], limbs, device=device) if jobs else []
+        Yt = {}
+        for (bi, _), M in zip(keys, full):
+            vals = mw.from_limbs(np.ascontiguousarray(M.reshape(limbs, -1)))
+            Yt[bi] = np.array(list(vals), dtype=object).reshape(M.shape[1], M.shape[2])
+        yv = np.atleast_2d(np.asarray(getattr(result, "y", np.zeros(0)), dtype=np.float64))
+        y = [mp.fsum(mp.mpf(float(v)) for v in yv[:, k]) for k in range(problem.b.size)]
+    index = system_index(problem, Bs, field)
+    m = len(index)
+    nconstraints = sum(len(cj) for cj in problem.c)
+    objective = []
+    for bi, (j, bl) in enumerate(problem.flat_blocks()):
+        nk = int(block_n[bi]) - int(Bs[bi][2])
+        if not nk:
+            continue
+        l = bi - sum(len(cl) for cl in problem.blocks[:j])
+        Ct = transform_field(_elem_matrix(problem.C[j][l], d), Bs[bi][1], Bs[bi][2], field, matmul=matmul, device=device)
+        objective += [any(Ct[a, b]) or any(Ct[b, a]) for a in range(nk) for b in range(a, nk)]
+    objective += [any(_elem(v, d)) for v in problem.b]
+    extra = 0
+    while True:
+        columns = select_columns(index, settings.redundancyfactor + extra, rng, nconstraints=nconstraints, objective=objective)
+        A, rhs, x, cols = get_rational_system(problem, Yt, y, Bs, columns, settings, assemble=assemble, matmul=matmul, device=device, field=field, limbs=limbs,
+                                              gemm=gemm, solve=solve)
+        x_extra, correct_slacks, finished = project_to_affine_space(A, rhs, settings=settings, rng=rng, device=device, batch=batch, lift=lift,
+                                                                    reconstruct=reconstruct, matmul=matmul)
+        if finished:
+            break
+        if len(columns) >= m:
+            raise ArithmeticError("exact_solution: the system is inconsistent but all columns were taken")
+        extra += 2
+    for pos, c in enumerate(cols):
+        x[c] += x_extra[pos]
+    xf = xrational_to_field(x, field)
+    sol_t, free = {}, [zero] * problem.b.size
+    for bi, (_, _, s_) in Bs.items():
+        nk = int(block_n[bi]) - int(s_)
+        sol_t[bi] = np.empty((nk, nk), dtype=object)
+    for e, v in zip(index, xf):
+        if e[0] == "free":
+            free[e[1]] = v
+        else:
+            sol_t[e[0]][e[1], e[2]] = sol_t[e[0]][e[2], e[1]] = v
+    certificates = [checkpd_field(sol_t[bi], field, device=device, minors=minors, primes=primes) for bi in sol_t if sol_t[bi].shape[0]]
+    success = bool(correct_slacks) and all(cert.pd for cert in certificates)
+    full = [undo_transform_field(sol_t[bi], Bs[bi][1], Bs[bi][2], field, matmul=matmul, device=device) for bi in sorted(sol_t)]
+    value = _elem(problem.constant, d)
+    for k, v in enumerate(problem.b):
+        value = add(value, _elem_mul(_elem(v, d), free[k], f))
+    for (j, l), M in zip(((j, l) for j, cl in enumerate(problem.blocks) for l in range(len(cl))), full):
+        for a in range(M.shape[0]):
+            for b in range(M.shape[0]):
+                c = _elem(problem.C[j][l][a, b], d)
+                if any(c) and any(M[a, b]):
+                    value = add(value, _elem_mul(c, M[a, b], f))
+    return ExactSolution(success, [sol_t[bi] for bi in sorted(sol_t)] if transformed else full, free, value, bool(correct_slacks), certificates, Bs)

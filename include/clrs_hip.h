@@ -363,6 +363,18 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   C <- beta C; m = 0 or n = 0 is a no-op.  CLRS_ERR_INVALID (message: clrs_last_error): limbs not on offer, alpha / beta out of range, a negative size or offset,
  *   a leading dimension smaller than the rows it holds, a matrix that leaves its plane, null pools with a non-empty job, or two jobs whose C ranges
  *   [c_off, c_off + (n - 1) ldc + m) overlap (the ranges as intervals: interleaved outputs are refused too).
+ * clrs_mw_posv: the solution X of A X = B for a dense symmetric positive definite A in `limbs` limbs (4, 5, 6, 8 or 10), no context, host pointers (DESIGN.md
+ *   section 26; the regularised normal equations of the reference's roundx, src/rounding.jl:537-568).  A is planar [limbs][a_plane]: an n x n column-major matrix
+ *   of which only the lower triangle is read; B is [limbs][b_plane] and X [limbs][x_plane]: n x nrhs column-major, leading dimension n.  A left-looking blocked
+ *   Cholesky with panels of 16 columns: the diagonal blocks by k_mw_posv_diag (one workgroup, L11 and its inverse from one elimination), every other step a
+ *   product by the kernel of clrs_mw_gemm, the launches in a fixed order on one stream, so results are reproducible bit for bit and the columns of X do not
+ *   depend on nrhs.  info[0] = 0, or 1 + j with j the first column whose pivot was not positive (or not finite): the first n nrhs entries of every plane of X
+ *   are then 0.  info[1]: the number of panels.  Only those entries of X and info[0 .. 1] are written.  n = 0 or nrhs = 0 touches nothing.  CLRS_ERR_INVALID
+ *   before any device call, outputs untouched: limbs not on offer, n < 0 or nrhs < 0, a_plane < n n, b_plane or x_plane < n nrhs, a null pointer with
+ *   n nrhs > 0.  Every device buffer of the call is released on every path.
+ * clrs_mw_posv_times: the device times of this thread's last clrs_mw_posv in milliseconds: the diagonal launches, the product launches (the rest of the span)
+ *   and the span from the first launch to the last.  The events around the diagonal launches are recorded only in calls made after this thread's first
+ *   clrs_mw_posv_times (until then diag_ms is 0 and gemm_ms the whole span): a call that nobody times records two events.
  * clrs_mw_kernel_vectors: kernel vectors of the PSD blocks of a solution (step 1 of the reference's exact_solution, detecteigenvectors, src/rounding.jl:575-642;
  *   DESIGN.md section 12), host pointers, no context.  X and Y are planar [limbs][plane] in the xy layout: block b is n[b] x n[b] column-major at offset
  *   sum_{b' < b} n[b']^2 (plane >= sum n^2).  Per block one branch, chosen from limb plane 0: dual (branch[b] = 1) when use_dual != 0 and max |X_b| <= dual_max
@@ -553,6 +565,8 @@ typedef struct clrs_mw_gemm_job {
 } clrs_mw_gemm_job;
 int clrs_mw_gemm(int device, int limbs, int njobs, const clrs_mw_gemm_job *jobs, const double *A, int64_t a_plane, const double *B, int64_t b_plane, double *C,
                  int64_t c_plane);
+int clrs_mw_posv(int device, int limbs, int n, int nrhs, const double *A, int a_plane, const double *B, int b_plane, double *X, int x_plane, int32_t *info);
+int clrs_mw_posv_times(double *diag_ms, double *gemm_ms, double *whole_ms);
 int clrs_mw_kernel_vectors(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual, double dual_max,
                            int32_t *branch, int32_t *perm, int32_t *rank, int32_t *count, double *V, double *resid_max, double *v_max, double *pivot_resid);
 int clrs_mw_rationalize(int device, int limbs, int count, const double *v, int plane, double errbound, double *num, double *den, int32_t *status, double *vq);

@@ -720,6 +720,34 @@ function rationalize(v::AbstractVector{BigFloat}; prec::Integer=precision(BigFlo
 end
 
 """
+    posv(A::AbstractMatrix{BigFloat}, B::AbstractVecOrMat{BigFloat}; prec=precision(BigFloat), device=0)
+
+Solve `A X = B` for a dense symmetric positive definite `A` on the device (`clrs_mw_posv`, DESIGN.md section 26) at `limbs_for(prec)` words per number: a
+blocked Cholesky whose diagonal blocks are eliminated by one workgroup each and whose other steps are multi-word products.  Only the lower triangle of `A`
+is read.  Raises when a pivot is not positive, naming its column.
+"""
+function posv(A::AbstractMatrix{BigFloat}, B::AbstractVecOrMat{BigFloat}; prec::Integer=precision(BigFloat), device::Integer=0)
+    K = limbs_for(prec)
+    K >= 4 || error("posv: prec = $prec selects $K limbs; the multi-word kernels need at least 4 (prec >= 158)")
+    n = size(A, 1); nrhs = size(B, 2)
+    size(A, 2) == n && size(B, 1) == n || error("posv: A must be n x n and B n x nrhs")
+    Aw = zeros(Float64, max(n * n, 1), K); Bw = zeros(Float64, max(n * nrhs, 1), K); Xw = zeros(Float64, max(n * nrhs, 1), K)
+    for c in 1:n, r in c:n
+        limbs_of!(Aw, r + (c - 1) * n, A[r, c], K)
+    end
+    for c in 1:nrhs, r in 1:n
+        limbs_of!(Bw, r + (c - 1) * n, B[r, c], K)
+    end
+    info = zeros(Int32, 2)
+    check(ccall((:clrs_mw_posv, libclrs[]), Cint,
+                (Cint, Cint, Cint, Cint, Ptr{Float64}, Cint, Ptr{Float64}, Cint, Ptr{Float64}, Cint, Ptr{Int32}),
+                device, K, n, nrhs, Aw, size(Aw, 1), Bw, size(Bw, 1), Xw, size(Xw, 1), info))
+    info[1] == 0 || error("posv: the pivot of column $(info[1] - 1) (counted from 0) is not positive")
+    X = [BigFloat(sum(BigFloat(Xw[r + (c - 1) * n, l]) for l in K:-1:1); precision=prec) for r in 1:n, c in 1:nrhs]
+    return B isa AbstractVector ? vec(X) : X
+end
+
+"""
     round_to_field(v::AbstractVector{BigFloat}, g::BigFloat, deg::Integer; prec=precision(BigFloat), bits=1000, errbound=1e-15, nd=0, device=0)
 
 The reference's `roundx(x, g, deg)` (src/rounding.jl:519-534) for `deg` = 2 .. 4 on the device (`clrs_mw_field_round`, DESIGN.md section 23), at
