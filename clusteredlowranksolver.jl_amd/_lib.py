@@ -180,6 +180,8 @@ SYMBOLS = {
     "clrs_zz_lll_times": (C.c_int, [p_d, p_d]),
     "clrs_mw_field_round": (C.c_int, [C.c_int, C.c_int, C.c_int, p_d, C.c_int, p_d, C.c_int, C.c_int, C.c_double, C.c_int, p_i32, p_i32, p_i32, p_d, p_d, p_i32]),
     "clrs_mw_field_round_times": (C.c_int, [p_d, p_d]),
+    "clrs_mw_minpoly": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, p_d, C.c_int, C.c_int, C.c_double, C.c_int, p_i32, p_i32, p_i32, p_d, p_i32]),
+    "clrs_mw_minpoly_times": (C.c_int, [p_d, p_d]),
     "clrs_mw_kernel_vectors_field": (C.c_int, [C.c_int, C.c_int, C.c_int, p_i32, p_d, p_d, C.c_int, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, p_d, C.c_int,
                                                C.c_int, p_i32, p_i32, p_i32, p_i32, p_d, p_d, p_d, p_d, p_i32, p_i32, p_i32, p_d, p_d, p_i32, p_d]),
     "clrs_mw_schur_solve": (C.c_int, [C.c_void_p, p_d, p_d, p_d, p_d]),
@@ -247,7 +249,7 @@ def _hipcc(args):
 
 # translation units of libclrs_hip.so: (object, source, extra flags, predicate selecting the files it depends on)
 _UNITS = (
-    ("clrs_hip.o", "clrs_hip.hip", (), lambda f: not f.startswith(("clrs_mw", "clrs_modp", "clrs_zz"))),
+    ("clrs_hip.o", "clrs_hip.hip", (), lambda f: not f.startswith(("clrs_mw", "clrs_modp", "clrs_zz", "clrs_minpoly"))),
     # the elimination mod p, the p-adic lifting on it, the reconstruction and the leading minors mod many primes (clrs_modp_rref, clrs_modp_dixon_lift, clrs_modp_dixon_lift_multi, clrs_modp_dixon_reconstruct, clrs_modp_minors, clrs_modp_minors_field, clrs_modp_field_frobenius, clrs_modp_field_adjugate) and the exact integer matrix product (clrs_zz_gemm): a small unit of its own, no multi-word flags
     ("clrs_modp.o", "clrs_modp.hip", (), lambda f: f.startswith("clrs_modp")),
     # the batched LLL reduction (clrs_zz_lll): exact integer rows steered by K-limb floating point, so no contraction here either; it reads the digit arithmetic
@@ -257,6 +259,9 @@ _UNITS = (
     # the rounding to a number field by integer relations (clrs_mw_field_round): one lane per number; it reads the arithmetic of the LLL unit
     ("clrs_mw_field_round.o", "clrs_mw_field_round.hip", ("-ffp-contract=off",),
      lambda f: f.startswith("clrs_mw_field_round") or f in ("clrs_zz_lll_arith.h", "clrs_modp_zz_arith.h", "clrs_mw_arith.h")),
+    # the minimal polynomials of find_field (clrs_mw_minpoly): the same lanes on the powers of each number; it reads the arithmetic of the unit above
+    ("clrs_minpoly.o", "clrs_minpoly.hip", ("-ffp-contract=off",),
+     lambda f: f.startswith("clrs_minpoly") or f in ("clrs_mw_field_round_arith.h", "clrs_zz_lll_arith.h", "clrs_modp_zz_arith.h", "clrs_mw_arith.h")),
     ("clrs_mw.o", "clrs_mw.hip", ("-ffp-contract=off", "-DMW_SPLIT_UNITS"), lambda f: f.startswith("clrs_mw") and not f.startswith("clrs_mw_field_round")),
     # the device code of the larger limb counts, one unit each (explicit instantiations: clrs_mw_inst.h), compiled side by side
     *((f"clrs_mw_k{k}.o", "clrs_mw_inst.hip", ("-ffp-contract=off", f"-DMW_INST_K={k}"),

@@ -54,6 +54,10 @@ number about 1e30, their products by clrs_mw_gemm and their solve by clrs_mw_pos
 26), `get_rational_system(field=)` and `exact_solution(field=)` run the chain.  The reduction of the field's kernel vectors is not built: the field branch
 needs `RoundingSettings(reduce_kernelvectors=False)`.
 
+The field itself is found from the solution (src/find_field.jl): `select_vals` picks one generic entry per kernel vector, `minimal_polynomials` searches an
+integer relation among the powers of each, degree by degree, on the device (clrs_mw_minpoly; `minpoly_relations_lll` is the same contract
+through clrs_zz_lll), `find_common_minpoly` joins the generators into one `NumberField`, `find_field` runs the three, and `to_field` writes a number in the field.
+
 The system the projection solves is assembled from an `ExactProblem` (the problem over QQ; `to_sdp` gives the numeric one) by `linear_system`
 (`partial_linearsystem`, src/interface.jl:1354-1535): per low-rank block one call of clrs_zz_lowrank_system, a row-wise Gram of long
 integers with the digit index in the k-extent of the fp64 MFMA: `lowrank_system`, `system_index`, `select_columns` (src/rounding.jl:95-153),
@@ -78,7 +82,8 @@ __all__ = ["RoundingSettings", "KernelVectorError", "BlockKernel", "kernel_vecto
            "ExactProblem", "ExactSolution", "system_index", "linear_system", "select_columns", "vectorize_solution", "get_rational_system", "exact_solution",
            "ReductionError", "lll_first_rung", "lll_batch", "lll", "kernel_lattice", "reduce_kernel_vectors", "NumberField", "FieldRounding", "round_to_field",
            "field_relations_lll", "kernel_vectors_field_batch", "vectors_to_field", "split_primes", "field_frobenius", "leading_minors_field_mod", "field_minor_bounds",
-           "FieldPDCertificate", "checkpd_field", "convert_system", "xrational_to_field", "field_least_squares", "field_array"]
+           "FieldPDCertificate", "checkpd_field", "convert_system", "xrational_to_field", "field_least_squares", "field_array", "MinPolySearch",
+           "minimal_polynomials", "minpoly_relations_lll", "select_vals", "find_common_minpoly", "find_field", "to_field"]
 
 WRONG_VECTOR_MESSAGE = "wrong vector detected"
 CLINDEP_MESSAGE = "clindep failed to find a relation"          # src/rounding.jl:508
@@ -2555,6 +2560,52 @@ def field_default_digits(bits: int, limbs: int) -> int:
     return min(LLL_MAX_DIGITS, field_top_bits(bits, limbs) // (2 * DIGIT_BITS) + 3)
 
 
+def _relation_ladder(us, D: int, P: int, errbound: float, lll, device):
+    """The rung loop of `field_relations_lll` and `minpoly_relations_lll`: `us[i]` the D mpmath numbers of number i (None: not finite, status 2).  Per rung
+    p = 1, 6, 11, .. <= P one batched `lll` call over the numbers still open, each on [I | floor(2^p u)] from scratch; the first row a is accepted when
+    |sum a_k u_k| < errbound in the caller's mpmath precision.  Returns (rel (count, D) object, status, rung, err): status 0 wherever a row was accepted,
+    whatever its entries; 1 ladder exhausted; 3 / 4 where `lll` raised `ReductionError`."""
+    import mpmath as mp
+    count = len(us)
+    rel, status = np.zeros((count, D), dtype=object), np.full(count, -1, np.int32)
+    rung, err = np.zeros(count, np.int32), np.zeros(count)
+    for i, u in enumerate(us):
+        if u is None:
+            status[i] = FIELD_NOT_FINITE
+    p = 1
+    while p <= P and np.any(status == -1):
+        opened = [i for i in range(count) if status[i] == -1]
+        lattices = []
+        for i in opened:
+            A = np.zeros((D, D + 1), dtype=object)
+            for r in range(D):
+                A[r, r], A[r, D] = 1, int(mp.floor(mp.ldexp(us[i][r], p)))
+            lattices.append(A)
+        try:
+            outs = lll(lattices, device=device)
+        except ReductionError:
+            outs = []
+            for A in lattices:                                             # (one lattice failed: find out which)
+                try:
+                    outs.append(lll([A], device=device)[0])
+                except ReductionError as e:
+                    outs.append(FIELD_OVERFLOW if "digits" in str(e) else FIELD_STEER)
+        for i, out in zip(opened, outs):
+            rung[i] = p
+            if isinstance(out, int):
+                status[i] = out
+                continue
+            a = [int(x) for x in out[0, :D]]
+            e = abs(mp.fsum(x * u for x, u in zip(a, us[i])))
+            err[i] = float(e)
+            if e < errbound:
+                rel[i] = a
+                status[i] = FIELD_FOUND
+        p += 5
+    status[status == -1] = FIELD_EXHAUSTED
+    return rel, status, rung, err
+
+
 def field_relations_lll(values, field: NumberField, limbs: int, errbound: float = 1e-15, bits: int = 1000, device: int = 0, lll=None) -> FieldRounding:
     """The contract of `round_to_field` through `lll_batch` (clrs_zz_lll): per rung p = 1, 6, 11, .. one batched call over the numbers still open, each on
     the lattice [I | floor(2^p u)] from scratch; the first row is accepted on the host, in mpmath, when |sum a_i u_i| < errbound.  Degrees 2 .. 8; limited
@@ -2573,46 +2624,18 @@ def field_relations_lll(values, field: NumberField, limbs: int, errbound: float 
     v, count = _field_values(values, limbs, "field_relations_lll")
     D, P = deg + 1, field_top_bits(bits, limbs)
     field.powers(limbs)                                                         # (refuses a g not known to the ladder's bits)
-    rel, status = np.zeros((count, D), dtype=object), np.full(count, -1, np.int32)
-    rung, err, vqs = np.zeros(count, np.int32), np.zeros(count), [mp.mpf(0)] * count
+    vqs = [mp.mpf(0)] * count
     with mp.workprec(64 * limbs + 128):
         gp = [mp.mpf(x) for x in from_limbs(field.powers(limbs))]
         finite = np.all(np.isfinite(v[:, :count]), axis=0)
         us = [[x] + gp if finite[i] else None for i, x in enumerate(from_limbs(v[:, :count]))]
-        status[~finite] = FIELD_NOT_FINITE
-        p = 1
-        while p <= P and np.any(status == -1):
-            opened = [i for i in range(count) if status[i] == -1]
-            lattices = []
-            for i in opened:
-                A = np.zeros((D, D + 1), dtype=object)
-                for r in range(D):
-                    A[r, r], A[r, D] = 1, int(mp.floor(mp.ldexp(us[i][r], p)))
-                lattices.append(A)
-            try:
-                outs = lll(lattices, device=device)
-            except ReductionError:
-                outs = []
-                for A in lattices:                                             # (one lattice failed: find out which)
-                    try:
-                        outs.append(lll([A], device=device)[0])
-                    except ReductionError as e:
-                        outs.append(FIELD_OVERFLOW if "digits" in str(e) else FIELD_STEER)
-            for i, out in zip(opened, outs):
-                rung[i] = p
-                if isinstance(out, int):
-                    status[i] = out
-                    continue
-                a = [int(x) for x in out[0, :D]]
-                e = abs(mp.fsum(x * u for x, u in zip(a, us[i])))
-                err[i] = float(e)
-                if e < errbound:
-                    rel[i] = a
-                    status[i] = FIELD_FOUND if a[0] != 0 else FIELD_NO_FIELD
-                    if a[0] != 0:
-                        vqs[i] = -mp.fsum(x * u for x, u in zip(a[1:], gp)) / a[0]
-            p += 5
-        status[status == -1] = FIELD_EXHAUSTED
+        rel, status, rung, err = _relation_ladder(us, D, P, errbound, lll, device)
+        for i in np.flatnonzero(status == FIELD_FOUND):
+            a = rel[i]
+            if a[0] == 0:
+                status[i] = FIELD_NO_FIELD
+            else:
+                vqs[i] = -mp.fsum(x * u for x, u in zip(a[1:], gp)) / a[0]
         vq = to_limbs(vqs, limbs) if count else np.zeros((limbs, 0))
     zeros = np.zeros(count, np.int32)
     return FieldRounding(_field_coeffs(rel, status), rel, status, rung, err, vq, zeros, zeros.copy(), np.ones(count, np.int32))
@@ -3970,3 +3993,314 @@ def _exact_solution_field(problem, result, settings, limbs, transformed, rng, de
                 if any(c) and any(M[a, b]):
                     value = add(value, _elem_mul(c, M[a, b], f))
     return ExactSolution(success, [sol_t[bi] for bi in sorted(sol_t)] if transformed else full, free, value, bool(correct_slacks), certificates, Bs)
+
+
+# ---- find_field: the number field of a solution from minimal polynomials of kernel entries (src/find_field.jl; clrs_mw_minpoly) ---------
+MINPOLY_KERNEL_DEGREES = (1, 2, 3, 4)     # what k_mw_minpoly is instantiated for
+MINPOLY_POWER_LIMIT = 2.0 ** 22           # FR_V_LIMIT: every power of a number must stay below this
+
+
+@dataclasses.dataclass
+class MinPolySearch:
+    """What `minimal_polynomials` returns.  Per number i: `degree[i]` the degree its search closed at (0: none up to `max_degree`); `minpoly[i]` the
+    polynomial as Python ints, low to high, primitive, leading coefficient > 0 (None where `degree` is 0).  Per number and tried degree d (column d - 1):
+    `status` (the codes of clrs_mw_minpoly; -1 not tried), `rung` (the bits of the rung the number ended at), `err` (the residual there) and `path`
+    (0 the kernel, 1 `relations`, -1 not tried).  `rel[i][d - 1]`: the relation as found, or None."""
+    degree: np.ndarray
+    minpoly: list
+    status: np.ndarray
+    rung: np.ndarray
+    err: np.ndarray
+    path: np.ndarray
+    rel: list
+
+
+def _minpoly_call_device(limbs, deg, count, v, plane, bits, errbound, nd, device=0):
+    """one call of clrs_mw_minpoly: returns (rel (nd, deg + 1, plane) int32, status, rung, err, info (2, plane))"""
+    p1 = max(plane, 1)
+    rel, status, rung = np.zeros((nd, deg + 1, p1), np.int32), np.zeros(p1, np.int32), np.zeros(p1, np.int32)
+    err, info = np.zeros(p1), np.zeros((2, p1), np.int32)
+    pi, pd = (lambda a: a.ctypes.data_as(_lib.p_i32)), (lambda a: a.ctypes.data_as(_lib.p_d))
+    _lib.check(_lib.load().clrs_mw_minpoly(int(device), int(limbs), int(deg), int(count), pd(v), int(plane), int(bits), float(errbound), int(nd), pi(rel), pi(status),
+                                           pi(rung), pd(err), pi(info)))
+    return rel, status, rung, err, info
+
+
+def _primitive(a) -> list:
+    """an integer relation as a polynomial: divided by its content, leading coefficient > 0"""
+    a = [int(x) for x in a]
+    g = _gcd_of(a) or 1
+    sign = -1 if a[-1] < 0 else 1
+    return [sign * x // g for x in a]
+
+
+def minpoly_relations_lll(values, degree: int, limbs: int, errbound: float = 1e-15, bits: Optional[int] = None, device: int = 0, lll=None):
+    """The contract of one clrs_mw_minpoly call through `lll_batch` (clrs_zz_lll), as `field_relations_lll` is for `round_to_field`: per rung p = 1, 6,
+    11, .. one batched call over the numbers still open, each on [I | floor(2^p (1, v, .., v^degree))] from scratch; the first row is accepted on the host, in
+    mpmath, when |sum a_k v^k| < errbound.  Degrees 1 .. 8.  Returns (rel (count, degree + 1) Python integers low to high, status, rung, err) with the
+    statuses of the kernel (5: a_0 = 0 or a_degree = 0).  The rescue of `minimal_polynomials` for statuses 3 and 4, its path for degrees 5 .. 8, and an
+    independent device-side cross-check of k_mw_minpoly.  `lll` replaces `lll_batch` (the tests' host build)."""
+    import mpmath as mp
+    from .mw import from_limbs
+    limbs, deg = int(limbs), int(degree)
+    if limbs not in LIMBS:
+        raise ValueError(f"minpoly_relations_lll: limbs must be one of {LIMBS}, got {limbs}")
+    if not 1 <= deg <= FIELD_LLL_MAX_DEGREE:
+        raise ValueError(f"minpoly_relations_lll: the degree must lie in [1, {FIELD_LLL_MAX_DEGREE}], got {deg}")
+    bits = 100 * deg if bits is None else int(bits)
+    if not errbound > 0 or bits < 1:
+        raise ValueError("minpoly_relations_lll: errbound must be positive and bits at least 1")
+    lll = lll_batch if lll is None else lll
+    v, count = _field_values(values, limbs, "minpoly_relations_lll")
+    D, P = deg + 1, field_top_bits(bits, limbs)
+    with mp.workprec(64 * limbs + 128):
+        finite = np.all(np.isfinite(v[:, :count]), axis=0)
+        us = [[mp.mpf(x) ** k for k in range(D)] if finite[i] else None for i, x in enumerate(from_limbs(v[:, :count]))]
+        large = [u is not None and any(abs(x) >= MINPOLY_POWER_LIMIT for x in u) for u in us]
+        rel, status, rung, err = _relation_ladder([None if big else u for u, big in zip(us, large)], D, P, errbound, lll, device)
+    for i in range(count):
+        if large[i]:
+            status[i] = FIELD_OVERFLOW
+        elif status[i] == FIELD_FOUND and (rel[i, 0] == 0 or rel[i, deg] == 0):
+            status[i] = FIELD_NO_FIELD
+    return rel, status, rung, err
+
+
+def minimal_polynomials(values, limbs: int, max_degree: int = 4, bits: Optional[int] = None, errbound: float = 1e-15, max_coeff: int = 10 ** 5, device: int = 0,
+                        call=None, relations=None, nd: Optional[int] = None, min_degree: int = 1) -> MinPolySearch:
+    """Minimal polynomials of numbers on the device (clrs_mw_minpoly, one lane per number): `values` planar (planes <= limbs, count) or fp64 (count,).
+    Degree by degree d = `min_degree`, .., `max_degree`, one call over the numbers still open: per number the first rung p = 1, 6, 11, .. <= min(bits,
+    53 limbs - 16) at which the first row a of the LLL-reduced basis of [I | floor(2^p (1, v, .., v^d))] has |sum a_k v^k| < errbound.  A number is closed at
+    the first d whose relation is found (status 0) with max |a_k| <= max_coeff (the inner loop of the reference's select_vals, src/find_field.jl:23-40);
+    a number that is not finite is closed with degree 0 at once, and one that is 0 to errbound (status 5 at degree 1: 0 + a_1 v ~ 0) with the polynomial
+    x.  Status 5 at any other degree is "nothing at this degree".  `bits` defaults to 100 max_degree.  Degrees 1 .. 4 run in the kernel; numbers it ends with
+    status 3 or 4, and degrees 5 .. 8, go to `relations` (default `minpoly_relations_lll`; False: nowhere, and max_degree > 4 is then a ValueError).  `nd`:
+    the base-2^24 digits per lattice entry (default `field_default_digits`); `call` replaces the device call (the tests' host build)."""
+    limbs, max_degree, min_degree = int(limbs), int(max_degree), int(min_degree)
+    if limbs not in LIMBS:
+        raise ValueError(f"minimal_polynomials: limbs must be one of {LIMBS}, got {limbs}")
+    if not 1 <= min_degree <= max_degree <= FIELD_LLL_MAX_DEGREE:
+        raise ValueError(f"minimal_polynomials: 1 <= min_degree <= max_degree <= {FIELD_LLL_MAX_DEGREE} is required, got {min_degree} and {max_degree}")
+    if relations is False and max_degree > MINPOLY_KERNEL_DEGREES[-1]:
+        raise ValueError(f"minimal_polynomials: the kernel takes degrees {MINPOLY_KERNEL_DEGREES}, got max_degree = {max_degree}")
+    bits = 100 * max_degree if bits is None else int(bits)
+    if not errbound > 0 or bits < 1:
+        raise ValueError("minimal_polynomials: errbound must be positive and bits at least 1")
+    relations = minpoly_relations_lll if relations is None else relations
+    call = _minpoly_call_device if call is None else call
+    v, count = _field_values(values, limbs, "minimal_polynomials")
+    nd = field_default_digits(bits, limbs) if nd is None else int(nd)
+    out = MinPolySearch(np.zeros(count, np.int32), [None] * count, np.full((count, max_degree), -1, np.int32), np.zeros((count, max_degree), np.int32),
+                        np.zeros((count, max_degree)), np.full((count, max_degree), -1, np.int32), [[None] * max_degree for _ in range(count)])
+    opened = np.arange(count)
+    for d in range(min_degree, max_degree + 1):
+        if not opened.size:
+            break
+        m = opened.size
+        sub = np.ascontiguousarray(v[:, opened])
+        if d in MINPOLY_KERNEL_DEGREES:
+            reld, status, rung, err, _ = call(limbs, d, m, sub, m, bits, float(errbound), nd, device=device)
+            status, rung, err, path = status[:m].copy(), rung[:m].copy(), err[:m].copy(), np.zeros(m, np.int32)
+            rel = planes_to_ints(reld[:, :, :m]).T.copy()
+            again = np.flatnonzero((status == FIELD_STEER) | (status == FIELD_OVERFLOW))
+            if again.size and relations is not False:
+                r = relations(sub[:, again], d, limbs, errbound=errbound, bits=bits, device=device)
+                rel[again], status[again], rung[again], err[again], path[again] = r[0], r[1], r[2], r[3], 1
+        else:
+            rel, status, rung, err = relations(sub, d, limbs, errbound=errbound, bits=bits, device=device)
+            path = np.ones(m, np.int32)
+        out.status[opened, d - 1], out.rung[opened, d - 1], out.err[opened, d - 1], out.path[opened, d - 1] = status, rung, err, path
+        keep = []
+        for t, i in enumerate(opened):
+            a = [int(x) for x in rel[t]]
+            out.rel[i][d - 1] = a if status[t] in (FIELD_FOUND, FIELD_NO_FIELD) else None
+            if status[t] == FIELD_FOUND and max(abs(x) for x in a) <= max_coeff:
+                out.degree[i], out.minpoly[i] = d, _primitive(a)
+            elif d == 1 and status[t] == FIELD_NO_FIELD and a[0] == 0:             # (0 + a_1 v ~ 0: v is 0 to this accuracy, with minimal polynomial x)
+                out.degree[i], out.minpoly[i] = 1, [0, 1]
+            elif status[t] != FIELD_NOT_FINITE:
+                keep.append(i)
+        opened = np.asarray(keep, dtype=np.int64)
+    return out
+
+
+def _solution_blocks(block_n_or_sdp, dualsol, primalsol, limbs, what):
+    """(block sizes, limbs, X, Y planar) of a solution, as `kernel_vectors` reads its arguments"""
+    if hasattr(block_n_or_sdp, "block_n"):
+        block_n = block_n_or_sdp.block_n
+    elif hasattr(block_n_or_sdp, "blocks"):
+        from .sdp import flatten
+        block_n = flatten(block_n_or_sdp).block_n
+    else:
+        block_n = block_n_or_sdp
+    block_n = np.ascontiguousarray(block_n, np.int32).reshape(-1)
+    primalsol = dualsol if primalsol is None else primalsol
+    if limbs is None:
+        planes = max(np.asarray(a).shape[0] if np.asarray(a).ndim == 2 else 1 for a in (dualsol.X, primalsol.Y))
+        limbs = 5 if planes == 1 else planes
+    limbs = int(limbs)
+    if limbs not in LIMBS:
+        raise ValueError(f"{what}: limbs must be one of {LIMBS}, got {limbs}")
+    plane = int(np.sum(block_n.astype(np.int64) ** 2))
+    return block_n, limbs, _planes(dualsol.X, limbs, plane, "X"), _planes(primalsol.Y, limbs, plane, "Y")
+
+
+def select_vals(block_n_or_sdp, dualsol, primalsol=None, limbs: Optional[int] = None, valbound: float = 1e-15, errbound: float = 1e-15, sizebound: float = 1e6,
+                device: int = 0, batch=None):
+    """The numbers `find_field` looks for minimal polynomials of (the reference's select_vals, src/find_field.jl:1-22): one generic entry per kernel vector
+    of every block.  ONE `kernel_vectors_batch` call without the checks of `kernel_vectors` (tau = errbound, use_dual, dual_max = sizebound); its echelon
+    form [I W] is the reference's Rp = R11^-1 R (dual branch: the row space of X_b; primal branch: the kernel of Y_b, where the reference takes an SVD), over
+    the pivots of the diagonally pivoted elimination instead of those of a column-norm QR.  Per vector the first entry outside the identity part, in `perm`
+    order, whose head exceeds `valbound` in magnitude.  Returns (values planar (limbs, m), origins: m tuples (block, vector, row))."""
+    if not valbound >= 0 or not errbound > 0 or not sizebound > 0:
+        raise ValueError("select_vals: valbound must not be negative, errbound and sizebound must be positive")
+    block_n, limbs, X, Y = _solution_blocks(block_n_or_sdp, dualsol, primalsol, limbs, "select_vals")
+    batch = kernel_vectors_batch if batch is None else batch
+    out = batch(block_n, X, Y, limbs, float(errbound), True, float(sizebound), device=device)
+    cols, origins = [], []
+    for b, k in enumerate(out):
+        n, perm = int(block_n[b]), np.asarray(k.perm)
+        free = perm[k.rank:] if k.branch == "dual" else perm[:k.rank]           # (the rows of W: everything outside the identity part)
+        vec = np.asarray(k.vectors)
+        for c in range(k.count):
+            row = next((int(r) for r in free if abs(vec[0, int(r), c]) > valbound), None)
+            if row is not None:
+                cols.append(vec[:, row, c])
+                origins.append((b, c, row))
+    values = np.ascontiguousarray(np.stack(cols, axis=1)) if cols else np.zeros((limbs, 0))
+    return values, origins
+
+
+def _refined_field(minpoly, near, limbs: int) -> NumberField:
+    """QQ(g) with g the real root of `minpoly` nearest the numeric value `near`, at 64 limbs + 128 bits (mpmath: all roots, then Newton on the chosen one).
+    `ArithmeticError` when no root is real or the nearest real root is not unique at that accuracy."""
+    import mpmath as mp
+    prec = 64 * int(limbs) + 128
+    c = [int(x) for x in minpoly]
+    with mp.workprec(prec + 64):
+        near = mp.mpf(near)
+        if len(c) == 2:
+            return NumberField(c, mp.mpf(-c[0]) / c[1], prec=prec)
+        roots = mp.polyroots([mp.mpf(x) for x in reversed(c)], maxsteps=500, extraprec=2 * prec)
+        scale = max(1, max(abs(r) for r in roots))
+        real = sorted((mp.re(r) for r in roots if abs(mp.im(r)) <= mp.ldexp(scale, -prec // 2)), key=lambda r: abs(r - near))
+        if not real:
+            raise ArithmeticError("find_field: the minimal polynomial of the generator has no real root")
+        if len(real) > 1 and abs(real[1] - near) - abs(real[0] - near) <= mp.ldexp(scale, -prec // 2):
+            raise ArithmeticError("find_field: the real root of the minimal polynomial nearest the generator is not unique")
+        g = real[0]
+        for _ in range(8):                                                       # Newton: the root to the working precision
+            f, df = mp.polyval(list(reversed(c)), g, derivative=True)
+            if df == 0:
+                raise ArithmeticError("find_field: the generator is a multiple root of its minimal polynomial")
+            g = g - f / df
+        return NumberField(c, g, prec=prec)
+
+
+def find_common_minpoly(generators, limbs: int, max_coeff: int = 10 ** 5, bits: Optional[int] = None, errbound: float = 1e-15, max_degree: int = 4, device: int = 0,
+                        call=None, relations=None, round_call=None, round_relations=None) -> NumberField:
+    """One field that holds every generator (the loop of the reference's find_common_minpoly, src/find_field.jl:46-84).  `generators`: tuples (v, degree,
+    minpoly) with v the limbs of a number (1-d fp64, at most `limbs` long) or an mpmath number, and its minimal polynomial as `minimal_polynomials` gives
+    it.  Starts from the generator of largest degree with the smallest sum |coeffs| (ties: the first); g is refined at once to the real root of its minimal
+    polynomial nearest the numeric value, so `decompose(v, g, d)` is `round_to_field` on a `NumberField` (accepted when found with every |a| < max_coeff).
+    All remaining generators are decomposed against the current g in one batched call, and again only after g changed.  A generator that does not
+    decompose extends the field: g <- g + v, and `minimal_polynomials` looks at degrees max(d, d_v) .. d + d_v; `ArithmeticError` when that range leaves
+    `max_degree`.  A generator of larger degree than g in which g decomposes replaces g.  No generators: the degree-1 field `NumberField([-1, 1], 1)`.
+    `call`, `relations`: those of `minimal_polynomials`; `round_call`, `round_relations`: `call` and `relations` of `round_to_field`."""
+    import mpmath as mp
+    from .mw import from_limbs, to_limbs
+    limbs, max_degree = int(limbs), int(max_degree)
+    bits = 100 * max_degree if bits is None else int(bits)
+    prec = 64 * limbs + 128
+
+    def number(v):
+        if isinstance(v, (np.ndarray, list, tuple)):
+            return from_limbs(np.asarray(v, np.float64).reshape(-1, 1))[0]
+        return mp.mpf(v)
+
+    with mp.workprec(prec):
+        gens = [(+number(v), int(d), [int(x) for x in poly]) for v, d, poly in generators]
+        gens = [g for g in gens if g[1] >= 2]
+        if not gens:
+            return NumberField([-1, 1], 1)
+        start = max(range(len(gens)), key=lambda i: (gens[i][1], -sum(abs(x) for x in gens[i][2]), -i))
+        g, d, poly = gens[start]
+        field = _refined_field(poly, g, limbs)
+        rest = [x for i, x in enumerate(gens) if i != start]
+
+        def decomposes(values, fld):
+            r = round_to_field(to_limbs(values, limbs), fld, limbs, errbound=errbound, bits=bits, device=device, call=round_call, relations=round_relations)
+            return [r.status[i] == FIELD_FOUND and all(abs(int(x)) < max_coeff for x in r.rel[i]) for i in range(len(values))]
+
+        while rest:
+            small = [x for x in rest if x[1] <= d]
+            ok = dict(zip((id(x) for x in small), decomposes([x[0] for x in small], field))) if small else {}
+            changed = False
+            for pos, x in enumerate(rest):
+                v, dv, pv = x
+                if dv <= d and ok[id(x)]:
+                    continue
+                if dv > d:                                                       # g may lie in QQ(v)
+                    fv = _refined_field(pv, v, limbs)
+                    if decomposes([field.g], fv)[0]:
+                        g, d, poly, field = v, dv, pv, fv
+                        rest, changed = rest[pos + 1:], True
+                        break
+                lo, hi = max(d, dv), d + dv
+                if hi > max_degree:
+                    raise ArithmeticError("find_field: the common field has degree above max_degree")
+                g = field.g + v
+                s = minimal_polynomials(to_limbs([g], limbs), limbs, max_degree=hi, bits=bits, errbound=errbound, max_coeff=max_coeff - 1, device=device,
+                                        call=call, relations=relations, min_degree=lo)
+                if s.degree[0] == 0:
+                    raise ArithmeticError("find_field: no minimal polynomial of the extended generator was found")
+                d, poly = int(s.degree[0]), s.minpoly[0]
+                field = _refined_field(poly, g, limbs)
+                rest, changed = rest[pos + 1:], True
+                break
+            if not changed:
+                break
+        return field
+
+
+def find_field(block_n_or_sdp, dualsol, primalsol=None, max_degree: int = 4, valbound: float = 1e-15, errbound: float = 1e-15, bits: Optional[int] = None,
+               max_coeff: int = 10 ** 5, limbs: Optional[int] = None, device: int = 0, batch=None, call=None, relations=None, round_call=None,
+               round_relations=None) -> NumberField:
+    """Heuristically the number field the kernel of a solution is defined over (the reference's find_field, src/find_field.jl:97-108; DESIGN.md section
+    27): `select_vals` -> `minimal_polynomials` (on the device, clrs_mw_minpoly) -> `find_common_minpoly`.  Returns a `NumberField` whose generator is
+    known to 64 limbs + 128 bits, ready for `kernel_vectors(field=...)`, `basis_transformations(field=...)`, `exact_solution(field=...)`; with no generator
+    of degree >= 2 the degree-1 field `NumberField([-1, 1], 1)`, which those route to the path over QQ.  `bits` defaults to 100 max_degree.  `batch`: the
+    device call of `select_vals`; `call`, `relations`, `round_call`, `round_relations`: those of `find_common_minpoly`."""
+    block_n, limbs, _, _ = _solution_blocks(block_n_or_sdp, dualsol, primalsol, limbs, "find_field")
+    bits = 100 * int(max_degree) if bits is None else int(bits)
+    values, _ = select_vals(block_n, dualsol, primalsol, limbs=limbs, valbound=valbound, errbound=errbound, device=device, batch=batch)
+    s = minimal_polynomials(values, limbs, max_degree=max_degree, bits=bits, errbound=errbound, max_coeff=max_coeff, device=device, call=call, relations=relations)
+    gens = [(values[:, i], int(s.degree[i]), s.minpoly[i]) for i in range(values.shape[1]) if s.degree[i] >= 2]
+    return find_common_minpoly(gens, limbs, max_coeff=max_coeff, bits=bits, errbound=errbound, max_degree=max_degree, device=device, call=call,
+                               relations=relations, round_call=round_call, round_relations=round_relations)
+
+
+def to_field(values, field: NumberField, limbs: Optional[int] = None, bits: int = 100, errbound: float = 1e-15, device: int = 0, call=None, relations=None) -> list:
+    """Numbers as elements of `field` (the reference's to_field, src/find_field.jl:124-129): `round_to_field`, returning per number the tuple of
+    `Fraction`s (x_0, .., x_(deg-1)), value = sum_k x_k g^k.  `values`: planar limbs, fp64, or a sequence of mpmath numbers; `limbs` defaults to the planes of
+    a planar input, else 5.  `ValueError` "clindep failed to find a relation" where a value has no relation.  A field of degree 1 goes through `rationalize`."""
+    from .mw import to_limbs
+    a = np.asarray(values)
+    if a.dtype == object:
+        limbs = 5 if limbs is None else int(limbs)
+        v = to_limbs(a.reshape(-1), limbs)
+    else:
+        a = np.asarray(values, dtype=np.float64)
+        a = a.reshape(1, -1) if a.ndim <= 1 else a
+        limbs = (a.shape[0] if a.shape[0] in LIMBS else 5) if limbs is None else int(limbs)
+        v = a
+    if field.degree == 1:
+        num, den, status, _ = rationalize(v, limbs, errbound=errbound, device=device)
+        if np.any(status != 0):
+            raise ValueError(f"{CLINDEP_MESSAGE}: value {int(np.flatnonzero(status != 0)[0])} (status {int(status[status != 0][0])})")
+        return [(Fraction(int(n), int(q)),) for n, q in zip(num, den)]
+    r = round_to_field(v, field, limbs, errbound=errbound, bits=bits, device=device, call=call, relations=relations)
+    bad = np.flatnonzero(r.status != FIELD_FOUND)
+    if bad.size:
+        raise ValueError(f"{CLINDEP_MESSAGE}: value {int(bad[0])} (status {int(r.status[bad[0]])})")
+    return [tuple(r.coeffs[i]) for i in range(r.coeffs.shape[0])]

@@ -552,7 +552,23 @@ int clrs_mw_get_S(clrs_mw_ctx *ctx, double *S_out, double *AY_out);   /* S_j and
  *   CLRS_ERR_INVALID as for clrs_mw_kernel_vectors, and for round_errbound not positive, deg outside [2, 4], bits < 1, nd outside [1, 20], a null output,
  *   a power of g that is not finite or not below 2^22.
  * clrs_mw_field_round_times: the milliseconds of the calling thread's last clrs_mw_field_round: in k_mw_field_round over all launches, and from the first
- *   upload to the last download (device events). */
+ *   upload to the last download (device events).
+ * clrs_mw_minpoly: for each of `count` multi-word numbers v an integer polynomial of degree deg = 1 .. 4 with root v, by an integer relation among the
+ *   number's own powers (the reference's min_poly(v, d) -> clindep -> lindep, src/find_field.jl:111-113, src/rounding.jl:481-509):
+ *   the numeric core of find_field.  Host pointers, no context; v planar [limbs][plane].  The powers u = (1, v, v^2, .., v^deg) are formed once by the
+ *   multi-word product, u_k = u_(k-1) v.  Per number the first rung p = 1, 6, 11, .. <= min(bits, 53 limbs - 16) at which the first row a of an
+ *   LLL-reduced basis ((delta, eta) = (0.99, 0.51)) of [I | floor(2^p u)] has |a_0 + a_1 u_1 + .. + a_deg u_deg| < errbound, evaluated in `limbs` limbs
+ *   from the powers as formed.  The ladder, the lattice arithmetic, the caps and the workspace discipline are those of clrs_mw_field_round; the digits of
+ *   the fixed-point images of the powers are the lane's own.  rel is [nd][deg + 1][plane] int32, coefficients low to high: digit s of a_k of number i at
+ *   rel[(s * (deg + 1) + k) * plane + i]; status [plane]: 0 found; 1 no rung gave a relation; 2 a limb of v is NaN or Inf; 3 the Gram-Schmidt data were
+ *   unusable or a cap was hit; 4 an entry left its nd digits, or a power has |u_k| >= 2^22; 5 the accepted relation has a_deg = 0 or a_0 = 0 (v satisfies a
+ *   relation of lower degree to this accuracy, or is 0).  rung [plane]: the bits of the rung the number ended at; err [plane]: the residual there (0 for
+ *   statuses 2, 3, 4); info [2][plane]: exchanges, rungs visited.  rel is 0 unless the status is 0 or 5.  Entry i < count of every plane is written and
+ *   nothing behind them.  Launches are cut as for clrs_mw_field_round (clrs_config_set("field_round_launch_rungs", n)); the result does not depend on n.
+ *   CLRS_ERR_INVALID before any device call, outputs untouched: limbs other than 4, 5, 6, 8, 10, deg outside [1, 4], count < 0, plane < count, errbound
+ *   not positive, bits < 1, nd outside [1, 20], a null pointer with count > 0.  count == 0 touches nothing.  Every device buffer is released on every path.
+ * clrs_mw_minpoly_times: the milliseconds of the calling thread's last clrs_mw_minpoly: in k_mw_minpoly over all launches, and from the first upload to
+ *   the last download (device events). */
 #define CLRS_MODP_MINORS_MAX_N 128
 int clrs_mw_constraint_gram(clrs_mw_ctx *ctx, double *G_out);
 int clrs_mw_free_gram(clrs_mw_ctx *ctx, double *Q_out);
@@ -603,6 +619,9 @@ int clrs_zz_lll_times(double *kernel_ms, double *whole_ms);
 int clrs_mw_field_round(int device, int limbs, int deg, const double *gpow, int count, const double *v, int plane, int bits, double errbound, int nd,
                         int32_t *rel, int32_t *status, int32_t *rung, double *err, double *vq, int32_t *info);
 int clrs_mw_field_round_times(double *kernel_ms, double *whole_ms);
+int clrs_mw_minpoly(int device, int limbs, int deg, int count, const double *v, int plane, int bits, double errbound, int nd, int32_t *rel, int32_t *status,
+                    int32_t *rung, double *err, int32_t *info);
+int clrs_mw_minpoly_times(double *kernel_ms, double *whole_ms);
 int clrs_mw_kernel_vectors_field(int device, int limbs, int nblk, const int32_t *n, const double *X, const double *Y, int plane, double tau, int use_dual,
                                  double dual_max, double round_errbound, int deg, const double *gpow, int bits, int nd, int32_t *branch, int32_t *perm,
                                  int32_t *rank, int32_t *count, double *V, double *resid_max, double *v_max, double *pivot_resid, int32_t *rel, int32_t *status,

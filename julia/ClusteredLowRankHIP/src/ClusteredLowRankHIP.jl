@@ -782,6 +782,36 @@ function round_to_field(v::AbstractVector{BigFloat}, g::BigFloat, deg::Integer; 
 end
 
 """
+    minpoly(v::AbstractVector{BigFloat}, d::Integer; prec=precision(BigFloat), bits=100 * d, errbound=1e-15, nd=0, device=0)
+
+The reference's `min_poly(v, d)` (src/find_field.jl:111-113) for `d` = 1 .. 4 on the device (`clrs_mw_minpoly`, DESIGN.md section 27), at `limbs_for(prec)`
+words per number: per number the first rung p = 1, 6, 11, .. <= min(bits, 53 limbs - 16) at which the first row `a` of an LLL-reduced basis of
+`[I | floor(2^p (1, v, .., v^d))]` has `|a[1] + a[2] v + .. + a[d+1] v^d| < errbound`.  Returns `(coeffs, status, rung)`: `coeffs[i]` the `d + 1` integers
+low to high (zeros unless `status[i]` is 0 or 5); `status[i]` 0 found, 1 ladder exhausted, 2 not finite, 3 steering failed or a cap was hit, 4 an entry left
+its `nd` digits or a power is 2^22 or more, 5 `a[1] == 0` or `a[d+1] == 0`: nothing at this degree; `rung[i]` the bits of the rung the number ended at.
+"""
+function minpoly(v::AbstractVector{BigFloat}, d::Integer; prec::Integer=precision(BigFloat), bits::Integer=100 * d, errbound::Real=1e-15, nd::Integer=0,
+                 device::Integer=0)
+    K = limbs_for(prec)
+    K >= 4 || error("minpoly: prec = $prec selects $K limbs; the multi-word kernels need at least 4 (prec >= 158)")
+    1 <= d <= 4 || error("minpoly: the degree must lie in 1:4, got $d")
+    cnt = length(v); plane = max(cnt, 1); D = d + 1
+    top = 1 + 5 * div(min(bits, 53 * K - 16) - 1, 5)
+    ndig = nd > 0 ? Int(nd) : min(20, div(top, 48) + 3)
+    vw = zeros(Float64, plane, K)
+    for i in 1:cnt
+        isfinite(v[i]) ? limbs_of!(vw, i, v[i], K) : (vw[i, 1] = Float64(v[i]))
+    end
+    rel = zeros(Int32, plane, D, ndig); status = zeros(Int32, plane); rung = zeros(Int32, plane); err = zeros(Float64, plane); info = zeros(Int32, plane, 2)
+    check(ccall((:clrs_mw_minpoly, libclrs[]), Cint,
+                (Cint, Cint, Cint, Cint, Ptr{Float64}, Cint, Cint, Cdouble, Cint, Ptr{Int32}, Ptr{Int32}, Ptr{Int32}, Ptr{Float64}, Ptr{Int32}),
+                device, K, d, cnt, vw, plane, bits, Float64(errbound), ndig, rel, status, rung, err, info))
+    a(i, k) = sum(BigInt(rel[i, k, s]) << (24 * (s - 1)) for s in 1:ndig)
+    coeffs = [[a(i, k) for k in 1:D] for i in 1:cnt]
+    return coeffs, status[1:cnt], rung[1:cnt]
+end
+
+"""
     find_pivots_modular(A::AbstractMatrix{<:Integer}, p::Integer; device=0)
     find_pivots_modular(A::AbstractMatrix{<:Integer}; maxprimes=3, device=0)
 
